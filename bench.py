@@ -17,6 +17,8 @@ communicator, bdx_allreduce_counts).  Weak scaling: every rank owns its own shar
 Run:  python bench.py [--gpus N --steps K --warmup W --config C2]
 With N > 1 and no torchrun environment the script starts its own N ranks (python -m torch.distributed.run)
 before anything touches the GPU, and exits with their code.  Prints ONE JSON line on rank 0.
+``--dump-outputs DIR`` also writes what the last timed step computed as DIR/<name>.npy (at most 64 MB; inputs are
+seeded, so two builds run with the same arguments can be compared output for output).
 """
 from __future__ import annotations
 
@@ -52,7 +54,12 @@ def _parse():
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline duration")
     ap.add_argument("--allow-wrong-results", action="store_true",
                     help="tuning only (tools/phase_*.sh: phase-skip timing experiments of a -DBDX_TUNING build give wrong results by design): skip the counter-vector consistency checks of the headline run")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _self_launch(args) -> int:
@@ -217,6 +224,45 @@ def _profile_counters(config: str, n: int):
     except Exception:
         pass
     return traffic, src_s, valu
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, per_read: dict, counts, seed: int) -> dict:
+    """Write the headline path's results — the per-read int32 verdict vectors a caller of bdx_classify_device receives
+    (bc1 / bc2 / keep_start / keep_end, whichever the config produces) and the counter vector — as DIR/<name>.npy.
+    Verdicts are barcode indices, -1 / 0 sentinels or 1-based positions inside a read, so float32 holds them exactly;
+    the counters go out as float64.  If the vectors would exceed DUMP_LIMIT_BYTES in all, every one of them is cut to
+    the same fixed sample of reads — chosen only by (number of reads, seed), so two builds dump the same reads — and
+    read_index.npy (float64) names them.  Returns a summary for the result line."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(per_read.values())))
+    header = 128  # (np.save header of a 1-D array)
+    fixed = 8 * len(counts) + header * (len(per_read) + 2)
+    arrays = {}
+    if fixed + 4 * len(per_read) * n <= DUMP_LIMIT_BYTES:
+        idx = None
+    else:
+        k = (DUMP_LIMIT_BYTES - fixed) // (4 * len(per_read) + 8)
+        idx = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, size=k, replace=False))
+        arrays["read_index"] = idx.astype(np.float64)
+    for name, v in per_read.items():
+        v = np.asarray(v) if idx is None else np.asarray(v)[idx]
+        arrays[name] = v.astype(np.float32)
+        assert np.array_equal(arrays[name].astype(np.int64), v.astype(np.int64)), f"{name}: a value float32 cannot hold exactly"
+    arrays["counts"] = np.asarray(counts).astype(np.float64)
+    stale = os.path.join(out_dir, "read_index.npy")
+    if idx is None and os.path.exists(stale):  # (left by an earlier, sampled dump into the same directory)
+        os.remove(stale)
+    files = []
+    for name, a in arrays.items():
+        files.append(f"{name}.npy")
+        np.save(os.path.join(out_dir, files[-1]), a)
+    return {"dir": out_dir, "files": files, "reads": n, "reads_written": n if idx is None else int(len(idx)),
+            "bytes": sum(os.path.getsize(os.path.join(out_dir, f)) for f in files)}
 
 
 def run_leg(name: str, dev, dev_index: int, steps: int = 5, warmup: int = 2, sample: int = 50_000):
@@ -463,6 +509,11 @@ def main():
         assert counts[0] == n * world, (counts[0], n * world)
         assert counts[1] + counts[2] + counts[3] == counts[0] and counts[4:].sum() == counts[1], "counter vector inconsistent"
 
+    # what the last timed step left in the result vectors (rank 0's shard; the counters are the all-reduced ones)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in d_out.items()}, counts, synth.SEED)
+
     info = hc.launch_info()
     path = hc.kernel_path
 
@@ -623,6 +674,8 @@ def main():
             "extra_configs": extra,
             "e2e": e2e,
         }
+        if dumped is not None:
+            line["outputs_dump"] = dumped
         print(json.dumps(line), flush=True)
 
     hc.close()

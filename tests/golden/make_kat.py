@@ -1,5 +1,5 @@
 """Writes tests/golden/kat.json: the known-answer vectors of the reference's own unit tests,
-transcribed BY HAND from /root/reference/test/unit/*.jl (inputs and expected outputs only —
+transcribed BY HAND from the reference's test/unit/*.jl (inputs and expected outputs only —
 data, not source).  No reference code is executed (there is no Julia runtime in the build
 container); this script only serialises the table below.  "Inf" encodes Float64 Inf.
 

@@ -1,5 +1,5 @@
 """Pins the CPU oracle (and the host-side range DSL) to the reference's own known-answer
-tests: every @test of /root/reference/test/unit/{alignment,trimming,hamming,exact}.jl,
+tests: every @test of the reference's test/unit/{alignment,trimming,hamming,exact}.jl,
 transcribed in tests/golden/kat.json (see tests/golden/make_kat.py)."""
 import pytest
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box): tools/kstats.sh <tag> [bench.py args] — kernel-trace summary of a short bench run, printed
 tag=${1:?tag}; shift
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp || exit 1
 mkdir -p gpurun_out/$tag
 rocprofv3 --kernel-trace --stats -d gpurun_out/$tag -o p --output-format csv -- python bench.py --no-cpu-baseline --no-host-path --no-other-configs --steps 10 --warmup 2 "$@" > gpurun_out/$tag/run.log 2>&1 || exit 1
 python - "$tag" <<'P'

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box): tools/kstats_cfg.sh <tag> <ONLY pattern> [N] — kernel-trace summary of one case of tools/bench_configs.py
 tag=${1:?tag}; only=${2:?pattern}; n=${3:-2000000}
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp || exit 1
 mkdir -p gpurun_out/$tag
 export ONLY="$only" N=$n
 rocprofv3 --kernel-trace --stats -d gpurun_out/$tag -o p --output-format csv -- python tools/bench_configs.py > gpurun_out/$tag/run.log 2>&1 || exit 1

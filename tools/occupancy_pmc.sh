@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box): tools/occupancy_pmc.sh — mean resident waves of the wave kernel under the geometries of tools/occupancy_probe.sh
 # (SQ_WAVE_CYCLES / SQ_BUSY_CYCLES per launch, relative to the product geometry)
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp || exit 1
 A="--no-cpu-baseline --no-host-path --no-other-configs --e2e-reads 0 --steps 2 --warmup 1"
 L6=$PWD/tests/redgreen/libbiodemux_hip_occ6.so
 one() {

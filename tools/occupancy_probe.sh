@@ -3,7 +3,7 @@
 # compiled for 6 / 5 waves per SIMD (side libraries under tests/redgreen/: bdx_wave.hip compiled with
 # -DBDX_WAVE_BOUNDS=__launch_bounds__(512,6) / (640,5), linked with the product objects) against the product build
 # (4 per SIMD, 114 VGPRs), each with the geometry that fills its residency.
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$(dirname "$0")/.." || exit 1
 B="python bench.py --no-cpu-baseline --no-host-path --no-other-configs --e2e-reads 0 --steps 20 --warmup 5"
 show() { python -c "
 import json,sys

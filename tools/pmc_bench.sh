@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box): tools/pmc_bench.sh <tag> [bench.py args] — SQ counters per kernel of a short bench.py run (per read of the batch)
 tag=${1:?tag}; shift
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp || exit 1
 mkdir -p gpurun_out/$tag
 A="--no-cpu-baseline --no-host-path --no-other-configs --e2e-reads 0 --steps 2 --warmup 1"
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU -d gpurun_out/$tag/a -o p --output-format csv -- python bench.py $A "$@" > gpurun_out/$tag/a.log 2>&1 || exit 1

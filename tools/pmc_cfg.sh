@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box): tools/pmc_cfg.sh <tag> <ONLY pattern> [N] — SQ counters of one case of tools/bench_configs.py, per kernel and launch
 tag=${1:?tag}; only=${2:?pattern}; n=${3:-2000000}
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp || exit 1
 mkdir -p gpurun_out/$tag
 export ONLY="$only" N=$n
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU -d gpurun_out/$tag/a -o p --output-format csv -- python tools/bench_configs.py > gpurun_out/$tag/a.log 2>&1 || exit 1

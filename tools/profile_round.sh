@@ -5,7 +5,7 @@
 #   python tools/summarize_prof.py <tag> <reads per launch> gpurun_out/<tag>_stats gpurun_out/<tag>_fetch gpurun_out/<tag>_write gpurun_out/<tag>_sq
 tag=${1:?tag}
 shift
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp || exit 1
 # (the profiled runs carry ONE config: the short legs of the default run launch the same kernel instantiations on other batches)
 P="--no-cpu-baseline --no-host-path --no-other-configs --e2e-reads 0"
 python bench.py "$@" > gpurun_out/${tag}_bench.json.log 2> gpurun_out/${tag}_bench.err || exit 1
