@@ -20,7 +20,7 @@ import numpy as np
 from .classification import DemuxStats, filename_for
 from .config import DemuxConfig, build_config
 from .fileio import read_fastq
-from . import nativeio
+from . import deviceio, nativeio
 from .hipabi import HipClassifier
 from .reporting import canonical_duration, generate_summary_report
 
@@ -148,10 +148,12 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
 
     Keyword arguments and defaults are the reference's (core.jl:365-391 / :504-528).
     ``_io`` selects the host-side reader/writer: "native" (csrc/bdx_io.cpp, threads), "python" (the
-    plain reference implementation below) or "auto" (native when the library was built).
+    plain reference implementation below), "auto" (native when the library was built) or "device" (index, pack,
+    split by output file and gather on the GPU, deviceio.py: needs the HIP classifier).
     ``_classifier_factory`` is a test seam: the parity tests on CPU pass the oracle here to
     check this file contract; the product default is the HIP classifier and nothing else.
-    ``_timings`` (a dict) receives the busy seconds of the native pipeline's stages (bench.py's end-to-end figure).
+    ``_timings`` (a dict) receives the busy seconds of the native pipeline's stages (bench.py's end-to-end figure; with
+    _io="device": upload_s, device_s, download_s, write_s and batches).
     Returns the DemuxStats scalar counters (the reference returns nothing)."""
     if len(args) == 3:
         fastq1, barcode_file, output_directory = args
@@ -209,6 +211,8 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         o["barcode_start_range2"], o["barcode_end_range2"], o["trim_side"], o["trim_side2"], o["summary"],
         o["summary_format"], o["matching_algorithm"])
 
+    if _io == "device" and _classifier_factory is not None:  # (no silent fallback to the host pipeline)
+        raise ValueError("_io='device': the device FASTQ pipeline needs the HIP classifier (no _classifier_factory)")
     # summary=true: the HIP classifier collects the histograms of classification.jl:827-865 on the device
     # (bdx_get_stats); a test-injected classifier without such tables hands over per-pass outputs instead
     classifier = _classifier_factory(config) if _classifier_factory else HipClassifier(config, device=device)
@@ -222,12 +226,15 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
             hist.add_pass_outputs(out, float(config.min_delta))
 
     try:
-        if _io not in ("auto", "native", "python"):
-            raise ValueError("_io must be 'auto', 'native' or 'python'")
+        if _io not in ("auto", "native", "python", "device"):
+            raise ValueError("_io must be 'auto', 'native', 'python' or 'device'")
         use_native = _io == "native" or (_io == "auto" and nativeio.available())
         if _timings is not None:
             _timings["pre_s"] = (_dt.datetime.now() - start_time).total_seconds()  # everything before the first batch can be read
-        if use_native:
+        if _io == "device":
+            deviceio.demux_device(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifier, _batch_reads,
+                                  _timings)
+        elif use_native:
             t_call = _dt.datetime.now()
             nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifier, _batch_reads,
                                   on_batch, _timings)

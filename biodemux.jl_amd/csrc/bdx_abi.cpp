@@ -2347,6 +2347,7 @@ void bdx_destroy(bdx_ctx *ctx) {
             ctx->st_sum[p][w].release();
         }
     ctx->st_flag.release();
+    for (DevBuf &b : ctx->fq) b.release();
     delete ctx;
 }
 

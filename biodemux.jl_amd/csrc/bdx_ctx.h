@@ -7,6 +7,8 @@
 
 #include "bdx_internal.h"
 
+#define BDX_FQ_SCRATCH 12  // scratch buffers of the device FASTQ pipeline (bdx_fastq.hip)
+
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
@@ -158,6 +160,7 @@ struct bdx_ctx {
     // multi-GPU: communicator + the reduced counter vector (bdx_comm.cpp)
     bdx_comm_state *comm = nullptr;
     DevBuf counts_sum;
+    DevBuf fq[BDX_FQ_SCRATCH];  // scratch of the device FASTQ pipeline (bdx_fastq.hip)
     std::string err;
     std::string path;
     int64_t launches = 0;

@@ -432,6 +432,20 @@ void bdx_fq_release(bdx_fq_file *f, int64_t upto) {
     if (n > 0) madvise((void *)f->data, (size_t)n, MADV_DONTNEED);
 }
 
+// Blocks until at least `target` bytes of the input are there or the stream has ended (plain files: at once):
+// *avail = bytes readable from bdx_fq_data, *final = 1 when that is the whole input.  -1 when the stream failed.
+int32_t bdx_fq_wait(bdx_fq_file *f, int64_t target, int64_t *avail, int32_t *final) {
+    bool fin, bad;
+    const int64_t a = wait_available(f, target, &fin, &bad);
+    *avail = bad ? 0 : a;
+    *final = fin ? 1 : 0;
+    if (bad) {
+        g_io_err = f->err;
+        return -1;
+    }
+    return 0;
+}
+
 // Line index of the bytes [start, size): fills line_off[k] / line_len[k] for up to 4*max_reads
 // lines (len excludes "\n" and a preceding "\r").  Returns the number of RECORDS (a trailing
 // partial record counts; its missing lines get offset = size, len = 0) and stores the cursor
@@ -630,6 +644,109 @@ int32_t bdx_fq_demux_write_range(const bdx_fq_file *src, const int64_t *line_off
                             class_lo, class_hi);
 }
 
+// Gzip output: every 4 MiB piece of every class's bytes is deflated as a gzip member of its own by whichever thread is
+// free (members concatenate to a valid .gz; one big class — `unknown` — would otherwise serialise a whole batch behind one
+// zlib stream); the members of a file are then appended in order.
+struct GzMember {
+    int c;
+    const uint8_t *src;
+    size_t len;
+    std::vector<uint8_t> out;
+    int bad = 0;
+};
+
+static void add_gz_members(std::vector<GzMember> &members, int c, const uint8_t *src, size_t total) {
+    const size_t piece = (size_t)1 << 22;
+    for (size_t off = 0; off < total; off += piece) {
+        GzMember mb;
+        mb.c = c;
+        mb.src = src + off;
+        mb.len = std::min(piece, total - off);
+        members.push_back(std::move(mb));
+    }
+}
+
+static void deflate_gz_members(std::vector<GzMember> &members, int nthreads) {
+    if (members.empty()) return;
+    std::atomic<size_t> nextm{0};
+    const int TM = std::max(1, std::min<int>(nthreads, (int)members.size()));
+    parallel_for(TM, [&](const int) {
+            for (;;) {
+                const size_t i = nextm.fetch_add(1);
+                if (i >= members.size()) break;
+                GzMember &mb = members[i];
+                z_stream zs;
+                memset(&zs, 0, sizeof(zs));
+                if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) {
+                    mb.bad = 1;
+                    continue;
+                }
+                // Every member carries its own compressed size in a gzip "extra" subfield ('D','X', 4 bytes LE;
+                // the BGZF idea with a 32-bit size): any gzip reader skips it, bdx_fq_open uses it to walk
+                // the member chain and inflate the members in parallel.
+                static unsigned char extra[8] = {'D', 'X', 4, 0, 0, 0, 0, 0};
+                gz_header hd;
+                memset(&hd, 0, sizeof(hd));
+                hd.os = 255;
+                hd.extra = extra;
+                hd.extra_len = 8;
+                deflateSetHeader(&zs, &hd);
+                mb.out.resize(deflateBound(&zs, (uLong)mb.len) + 64);
+                zs.next_in = (Bytef *)mb.src;
+                zs.avail_in = (uInt)mb.len;
+                zs.next_out = mb.out.data();
+                zs.avail_out = (uInt)mb.out.size();
+                if (deflate(&zs, Z_FINISH) != Z_STREAM_END) mb.bad = 1;
+                mb.out.resize(mb.out.size() - zs.avail_out);
+                deflateEnd(&zs);
+                // header: 10 fixed bytes, XLEN (2), then the subfield SI1 SI2 LEN(2) DATA(4) -> data at 16..19
+                if (!mb.bad && mb.out.size() >= 20 && (mb.out[3] & 4) && mb.out[12] == 'D' && mb.out[13] == 'X') {
+                    const uint32_t cs = (uint32_t)mb.out.size();
+                    for (int b = 0; b < 4; ++b) mb.out[16 + b] = (uint8_t)(cs >> (8 * b));
+                } else {
+                    mb.bad = 1;
+                }
+            }
+        });
+}
+
+// appends the members of class c to `path`; false on any failure
+static bool append_gz_members(const char *path, const std::vector<GzMember> &members, int c) {
+    FILE *fp = fopen(path, "ab");
+    if (!fp) return false;
+    bool ok = true;
+    for (const GzMember &mb : members)
+        if (mb.c == c && (mb.bad || fwrite(mb.out.data(), 1, mb.out.size(), fp) != mb.out.size())) ok = false;
+    if (fclose(fp) != 0) ok = false;
+    return ok;
+}
+
+// gzip forced, or a path ending in ".gz" (core.jl:127)
+static bool gz_path(const char *path, int32_t force_gzip) {
+    std::string low(path);
+    std::transform(low.begin(), low.end(), low.begin(), ::tolower);
+    return force_gzip || (low.size() >= 3 && low.compare(low.size() - 3, 3, ".gz") == 0);
+}
+
+// appends len bytes to a plain file with write(2); false on any failure
+static bool append_plain(const char *path, const uint8_t *p, int64_t left) {
+    const int fd = open(path, O_WRONLY | O_APPEND | O_CREAT, 0644);
+    if (fd < 0) return false;
+    bool ok = true;
+    while (left > 0) {
+        const ssize_t w = write(fd, p, (size_t)left);
+        if (w < 0 && errno == EINTR) continue;
+        if (w <= 0) {
+            ok = false;
+            break;
+        }
+        p += w;
+        left -= w;
+    }
+    if (close(fd) != 0) ok = false;
+    return ok;
+}
+
 static int32_t demux_write_impl(const bdx_fq_file *src, const int64_t *line_off, const int32_t *line_len, int64_t nrec,
                                 const int32_t *cls, int32_t n_classes, const char *const *class_paths,
                                 const int32_t *keep_start, const int32_t *keep_end, int32_t trim, int32_t force_gzip,
@@ -753,9 +870,7 @@ static int32_t demux_write_impl(const bdx_fq_file *src, const int64_t *line_off,
     static const int64_t IOV_LIMIT = getenv("BDX_IO_IOV_LIMIT") ? atoll(getenv("BDX_IO_IOV_LIMIT")) : (int64_t)8 << 20;  // classes with more bytes than this in a batch are gathered
     for (int c : todo) {
         Dest &ds = dest[(size_t)c];
-        std::string low(class_paths[c]);
-        std::transform(low.begin(), low.end(), low.begin(), ::tolower);
-        ds.gz = force_gzip || (low.size() >= 3 && low.compare(low.size() - 3, 3, ".gz") == 0);
+        ds.gz = gz_path(class_paths[c], force_gzip);
         if (!ds.gz && cplain[(size_t)c] && csize[(size_t)c] <= IOV_LIMIT) {
             std::vector<struct iovec> &v = iov_keep[(size_t)c];
             if (v.size() < (size_t)crecs[(size_t)c]) v.resize((size_t)crecs[(size_t)c]);
@@ -821,70 +936,12 @@ static int32_t demux_write_impl(const bdx_fq_file *src, const int64_t *line_off,
             });
     }
     tm3 = now();
-    // pass 3: gzip output — every 4 MiB piece of every class is deflated as a gzip member of its own by whichever thread
-    // is free (members concatenate to a valid .gz; one big class — `unknown` — would otherwise serialise the whole batch
-    // behind one zlib stream), then the members of a file are appended in order.
-    struct Member {
-        int c;
-        size_t off, len;
-        std::vector<uint8_t> out;
-        int bad = 0;
-    };
-    std::vector<Member> members;
+    // pass 3: gzip output (every 4 MiB piece of every gzip class is a member of its own)
+    std::vector<GzMember> members;
     if (!any_fail)
         for (int c : todo)
-            if (dest[(size_t)c].gz) {
-                const size_t total = (size_t)csize[(size_t)c], piece = (size_t)1 << 22;
-                for (size_t off = 0; off < total; off += piece) {
-                    Member mb;
-                    mb.c = c;
-                    mb.off = off;
-                    mb.len = std::min(piece, total - off);
-                    members.push_back(std::move(mb));
-                }
-            }
-    if (!members.empty()) {
-        std::atomic<size_t> nextm{0};
-        const int TM = std::max(1, std::min<int>(nthreads, (int)members.size()));
-        parallel_for(TM, [&](const int) {
-                for (;;) {
-                    const size_t i = nextm.fetch_add(1);
-                    if (i >= members.size()) break;
-                    Member &mb = members[i];
-                    z_stream zs;
-                    memset(&zs, 0, sizeof(zs));
-                    if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) {
-                        mb.bad = 1;
-                        continue;
-                    }
-                    // Every member carries its own compressed size in a gzip "extra" subfield ('D','X', 4 bytes LE;
-                    // the BGZF idea with a 32-bit size): any gzip reader skips it, bdx_fq_open uses it to walk
-                    // the member chain and inflate the members in parallel.
-                    static unsigned char extra[8] = {'D', 'X', 4, 0, 0, 0, 0, 0};
-                    gz_header hd;
-                    memset(&hd, 0, sizeof(hd));
-                    hd.os = 255;
-                    hd.extra = extra;
-                    hd.extra_len = 8;
-                    deflateSetHeader(&zs, &hd);
-                    mb.out.resize(deflateBound(&zs, (uLong)mb.len) + 64);
-                    zs.next_in = (Bytef *)(dest[(size_t)mb.c].base + mb.off);
-                    zs.avail_in = (uInt)mb.len;
-                    zs.next_out = mb.out.data();
-                    zs.avail_out = (uInt)mb.out.size();
-                    if (deflate(&zs, Z_FINISH) != Z_STREAM_END) mb.bad = 1;
-                    mb.out.resize(mb.out.size() - zs.avail_out);
-                    deflateEnd(&zs);
-                    // header: 10 fixed bytes, XLEN (2), then the subfield SI1 SI2 LEN(2) DATA(4) -> data at 16..19
-                    if (!mb.bad && mb.out.size() >= 20 && (mb.out[3] & 4) && mb.out[12] == 'D' && mb.out[13] == 'X') {
-                        const uint32_t cs = (uint32_t)mb.out.size();
-                        for (int b = 0; b < 4; ++b) mb.out[16 + b] = (uint8_t)(cs >> (8 * b));
-                    } else {
-                        mb.bad = 1;
-                    }
-                }
-            });
-    }
+            if (dest[(size_t)c].gz) add_gz_members(members, c, dest[(size_t)c].base, (size_t)csize[(size_t)c]);
+    deflate_gz_members(members, nthreads);
     // finish: the plain files (largest first: the unmatched reads' buffer is one long write) and the members of the
     // gzip files (consecutive in `members`), each file appended by one thread
     {
@@ -899,14 +956,7 @@ static int32_t demux_write_impl(const bdx_fq_file *src, const int64_t *line_off,
                     const int c = order[k];
                     Dest &ds = dest[(size_t)c];
                     if (ds.gz) {
-                        FILE *fp = fopen(class_paths[c], "ab");
-                        if (!fp) {
-                            ds.fail = 1;
-                            continue;
-                        }
-                        for (const Member &mb : members)
-                            if (mb.c == c && (mb.bad || fwrite(mb.out.data(), 1, mb.out.size(), fp) != mb.out.size())) ds.fail = 1;
-                        if (fclose(fp) != 0) ds.fail = 1;
+                        if (!append_gz_members(class_paths[c], members, c)) ds.fail = 1;
                         continue;
                     }
                     const int fd = open(class_paths[c], O_WRONLY | O_APPEND | O_CREAT, 0644);
@@ -960,6 +1010,54 @@ static int32_t demux_write_impl(const bdx_fq_file *src, const int64_t *line_off,
                 (tm1 - tm0) * 1e3, (tm2 - tm1) * 1e3, (tm3 - tm2) * 1e3, (now() - tm3) * 1e3, (long long)nrec);
     for (int c : todo)
         if (dest[(size_t)c].fail) {
+            g_io_err = std::string("cannot write ") + class_paths[c];
+            return -1;
+        }
+    return 0;
+}
+
+// One batch's per-class blocks (a device gather, bdx_fq_gather_device): class c's block of class_bytes[c] bytes
+// follows the blocks of classes 0 .. c-1 in `buf` and is appended to class_paths[c] — one write per plain file, the
+// 4 MiB 'D','X'-tagged members of demux_write_impl for gzip output.  Classes without bytes create no file (their path
+// may be NULL).  Threads work across files and members; each file is appended by one thread.
+int32_t bdx_fq_write_blocks(const uint8_t *buf, const int64_t *class_bytes, int32_t n_classes, const char *const *class_paths,
+                            int32_t force_gzip, int32_t nthreads) {
+    std::vector<int64_t> start((size_t)std::max(n_classes, 0) + 1, 0);
+    std::vector<int> todo;
+    for (int c = 0; c < n_classes; ++c) {
+        if (class_bytes[c] < 0) {
+            g_io_err = "negative block size";
+            return -1;
+        }
+        start[(size_t)c + 1] = start[(size_t)c] + class_bytes[c];
+        if (class_bytes[c] > 0) {
+            if (!class_paths[c]) {
+                g_io_err = "no path for a class with records";
+                return -1;
+            }
+            todo.push_back(c);
+        }
+    }
+    std::vector<GzMember> members;
+    std::vector<char> gz((size_t)std::max(n_classes, 0), 0);
+    for (int c : todo)
+        if ((gz[(size_t)c] = gz_path(class_paths[c], force_gzip))) add_gz_members(members, c, buf + start[(size_t)c], (size_t)class_bytes[c]);
+    deflate_gz_members(members, nthreads);
+    std::sort(todo.begin(), todo.end(), [&](int x, int y) { return class_bytes[x] > class_bytes[y]; });
+    std::vector<char> fail((size_t)std::max(n_classes, 0), 0);
+    std::atomic<size_t> nextc{0};
+    parallel_for(std::max(1, std::min<int>(nthreads, (int)todo.size())), [&](const int) {
+        for (;;) {
+            const size_t k = nextc.fetch_add(1);
+            if (k >= todo.size()) break;
+            const int c = todo[k];
+            const bool ok = gz[(size_t)c] ? append_gz_members(class_paths[c], members, c)
+                                          : append_plain(class_paths[c], buf + start[(size_t)c], class_bytes[c]);
+            if (!ok) fail[(size_t)c] = 1;
+        }
+    });
+    for (int c : todo)
+        if (fail[(size_t)c]) {
             g_io_err = std::string("cannot write ") + class_paths[c];
             return -1;
         }

@@ -1,0 +1,366 @@
+"""Device FASTQ pipeline (``execute_demultiplexing(..., _io="device")``): FASTQ text goes to the GPU and per-output-file
+FASTQ blocks come back.  Line index, packing, the stable split by output file (core.jl:139-148) and the gather of the
+trimmed records (core.jl:162-173) run as kernels (csrc/bdx_fastq.hip, C-ABI bdx_fq_*_device); the host only copies
+bytes and appends one block per file and batch (csrc/bdx_io.cpp bdx_fq_write_blocks).
+
+Batches of ``batch_reads`` records flow through three overlapped stages:
+  upload thread   byte window of batch k+1 from the input (pageable copies on a copy stream)
+  calling thread  index -> pack -> classify -> gather of batch k on the context's stream, then the download of its blocks
+  writer thread   waits for batch k-1's download and appends its blocks (one write per file, in batch order: per-file
+                  order is input order)
+Same files, bytes, counters and reports as nativeio.demux_native.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import queue
+import threading
+import time
+from concurrent.futures import ThreadPoolExecutor
+from typing import Optional
+
+import numpy as np
+
+from . import nativeio
+from .classification import filename_for
+from .hipabi import BdxError, pinned_empty
+
+_H2D, _D2H = 1, 2  # hipMemcpyKind
+_NONBLOCKING = 1   # hipStreamNonBlocking
+_NO_TIMING = 2     # hipEventDisableTiming
+
+
+class _Runtime:
+    """The few HIP runtime calls the pipeline makes, resolved through libbiodemux_hip.so (the runtime it links, so the
+    device pointers and streams are the ones its C-ABI uses)."""
+
+    def __init__(self, lib):
+        vp = C.c_void_p
+        sig = {
+            "hipSetDevice": [C.c_int],
+            "hipMalloc": [C.POINTER(vp), C.c_size_t],
+            "hipFree": [vp],
+            "hipMemcpyAsync": [vp, vp, C.c_size_t, C.c_int, vp],
+            "hipStreamCreateWithFlags": [C.POINTER(vp), C.c_uint],
+            "hipStreamDestroy": [vp],
+            "hipStreamSynchronize": [vp],
+            "hipEventCreateWithFlags": [C.POINTER(vp), C.c_uint],
+            "hipEventRecord": [vp, vp],
+            "hipEventSynchronize": [vp],
+            "hipEventDestroy": [vp],
+        }
+        for name, args in sig.items():
+            fn = getattr(lib, name)
+            fn.restype = C.c_int
+            fn.argtypes = args
+            setattr(self, name, fn)
+        lib.hipGetErrorString.restype = C.c_char_p
+        lib.hipGetErrorString.argtypes = [C.c_int]
+        self._err = lib.hipGetErrorString
+
+    def check(self, rc: int, what: str) -> None:
+        if rc != 0:
+            raise BdxError(f"{what} failed: {self._err(rc).decode()}")
+
+    def stream(self) -> int:
+        s = C.c_void_p()
+        self.check(self.hipStreamCreateWithFlags(C.byref(s), _NONBLOCKING), "hipStreamCreateWithFlags")
+        return s.value
+
+    def event(self) -> int:
+        e = C.c_void_p()
+        self.check(self.hipEventCreateWithFlags(C.byref(e), _NO_TIMING), "hipEventCreateWithFlags")
+        return e.value
+
+
+class _DevBuf:
+    def __init__(self, rt: _Runtime):
+        self.rt, self.p, self.cap = rt, 0, 0
+
+    def ensure(self, nbytes: int) -> int:
+        if nbytes > self.cap:
+            self.free()
+            want = max(256, int(nbytes * 1.25))  # (room for the next batches' slightly longer windows)
+            p = C.c_void_p()
+            self.rt.check(self.rt.hipMalloc(C.byref(p), want), f"hipMalloc({want})")
+            self.p, self.cap = p.value, want
+        return self.p
+
+    def free(self) -> None:
+        if self.p:
+            self.rt.hipFree(self.p)
+        self.p, self.cap = 0, 0
+
+
+_io_lib = None
+
+
+def _io():
+    """libbdx_io.so with the entries the device pipeline uses on top of nativeio's."""
+    global _io_lib
+    if _io_lib is None:
+        L = nativeio._load()
+        vp = C.c_void_p
+        L.bdx_fq_data.restype = vp
+        L.bdx_fq_data.argtypes = [vp]
+        L.bdx_fq_wait.restype = C.c_int32
+        L.bdx_fq_wait.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.bdx_fq_write_blocks.restype = C.c_int32
+        L.bdx_fq_write_blocks.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.c_int32]
+        _io_lib = L
+    return _io_lib
+
+
+class _Input:
+    """One FASTQ input: its host bytes (mapped, or inflated in the background) and its device side (two byte windows, the
+    line table of the current batch)."""
+
+    def __init__(self, path: str, rt: _Runtime, batch_reads: int):
+        self.f = nativeio.FastqFile(path)
+        self.cursor = 0
+        self.avg_record = 330.0  # bytes per record, learned from the batches so far
+        self.text = [_DevBuf(rt), _DevBuf(rt)]
+        self.win = [(0, 0), (0, 0)]  # per window slot: (bytes, final)
+        self.d_off = _DevBuf(rt)
+        self.d_len = _DevBuf(rt)
+        self.d_off.ensure(4 * batch_reads * 8)
+        self.d_len.ensure(4 * batch_reads * 4)
+
+    def close(self):
+        for b in (*self.text, self.d_off, self.d_len):
+            b.free()
+        self.f.close()
+
+
+def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
+                 classifier, batch_reads: int, timings: Optional[dict] = None) -> None:
+    """Device counterpart of nativeio.demux_native (same arguments but ``on_batch``: the HIP classifier keeps the
+    summary tables itself).  ``classifier`` must be the HIP classifier."""
+    if not hasattr(classifier, "classify_device"):
+        raise ValueError("the device FASTQ pipeline (_io='device') needs the HIP classifier")
+    t_wall = time.perf_counter()
+    busy = {"upload_s": 0.0, "device_s": 0.0, "download_s": 0.0, "write_s": 0.0, "batches": 0}
+    L = _io()
+    rt = _Runtime(classifier.lib)
+    dev = int(getattr(classifier, "device", 0))
+    rt.check(rt.hipSetDevice(dev), "hipSetDevice")
+    T = nativeio._threads()
+    batch_reads = max(1, int(batch_reads))
+    stride = max(1, len(config.bc_seqs2)) if config.is_dual else 1
+    n_classes = 2 + len(config.bc_seqs) * stride
+    do_trim = config.trim_side is not None or config.trim_side2 is not None
+    gz = int(bool(config.gzip_output))
+    paired = fastq2 is not None
+    # output streams of a batch: (input, prefix, trim) — core.jl:175-196
+    if paired and config.classify_both:
+        outs = [(0, prefix1, do_trim), (1, prefix2, False)]
+    elif paired:
+        outs = [(1, prefix2, False)]
+    else:
+        outs = [(0, prefix1, do_trim)]
+
+    ins = []
+    s_main = s_copy = 0
+    events = []
+    dbufs = []
+    errors = []
+    q_w: "queue.Queue" = queue.Queue(maxsize=1)
+    free: "queue.Queue" = queue.Queue()
+    up = ThreadPoolExecutor(max_workers=1, thread_name_prefix="bdx-upload")
+    fut = None
+    writer = None
+    try:
+        ins.append(_Input(fastq1, rt, batch_reads))
+        if paired:
+            ins.append(_Input(fastq2, rt, batch_reads))
+        s_main, s_copy = rt.stream(), rt.stream()
+        classifier.set_stream(s_main)
+        d_seq, d_seq_off, d_out = _DevBuf(rt), _DevBuf(rt), _DevBuf(rt)
+        d_v = {k: _DevBuf(rt) for k in ("bc1", "bc2", "keep_start", "keep_end")}
+        dbufs = [d_seq, d_seq_off, d_out, *d_v.values()]
+        d_seq_off.ensure((batch_reads + 1) * 8)
+        for b in d_v.values():
+            b.ensure(batch_reads * 4)
+        n_slots = 2  # download / write buffers: batch k is downloaded while k-1 is written
+        events = [rt.event() for _ in range(n_slots)]
+        hbuf = [None] * n_slots
+        for s in range(n_slots):
+            free.put(s)
+
+        def upload(inp: _Input, slot: int, want: int):
+            """bytes [cursor, cursor + want) of the input (what is there of them) -> the device window `slot`"""
+            t0 = time.perf_counter()
+            rt.check(rt.hipSetDevice(dev), "hipSetDevice")
+            avail, fin = C.c_int64(0), C.c_int32(0)
+            if L.bdx_fq_wait(inp.f.h, inp.cursor + want, C.byref(avail), C.byref(fin)) != 0:
+                raise OSError(L.bdx_io_last_error().decode())
+            end = min(avail.value, inp.cursor + want)
+            nbytes = max(0, end - inp.cursor)
+            final = bool(fin.value) and end >= avail.value
+            dst = inp.text[slot].ensure(nbytes + 64)
+            if nbytes:
+                src = L.bdx_fq_data(inp.f.h) + inp.cursor
+                rt.check(rt.hipMemcpyAsync(dst, src, nbytes, _H2D, s_copy), "hipMemcpyAsync (upload)")
+                rt.check(rt.hipStreamSynchronize(s_copy), "hipStreamSynchronize (upload)")
+            inp.win[slot] = (nbytes, final)
+            busy["upload_s"] += time.perf_counter() - t0
+
+        def want_bytes(inp: _Input) -> int:
+            return int(batch_reads * inp.avg_record * 1.05) + 65536
+
+        def upload_all(slot: int):
+            for inp in ins:
+                upload(inp, slot, want_bytes(inp))
+
+        def write_loop():
+            while True:
+                item = q_w.get()
+                if item is None:
+                    return
+                slot, blocks = item
+                try:
+                    if errors:
+                        continue
+                    t0 = time.perf_counter()
+                    rt.check(rt.hipEventSynchronize(events[slot]), "hipEventSynchronize (download)")
+                    t1 = time.perf_counter()
+                    base = hbuf[slot].ctypes.data
+                    for off, cb, prefix in blocks:
+                        if L.bdx_fq_write_blocks(base + off, cb.ctypes.data, n_classes, _paths(prefix, cb), gz, T) != 0:
+                            raise OSError(L.bdx_io_last_error().decode())
+                    busy["download_s"] += t1 - t0
+                    busy["write_s"] += time.perf_counter() - t1
+                except BaseException as e:  # noqa: BLE001 - forwarded to the caller
+                    errors.append(e)
+                finally:
+                    free.put(slot)
+
+        def _paths(prefix, cb):
+            arr = (C.c_char_p * n_classes)()
+            for c in np.flatnonzero(cb):
+                c = int(c)
+                if c == 0:
+                    b1, b2 = 0, 0
+                elif c == 1:
+                    b1, b2 = -1, 0
+                else:
+                    b1, b2 = divmod(c - 2, stride)
+                    b1, b2 = b1 + 1, (b2 + 1 if config.is_dual else 0)
+                arr[c] = os.path.join(output_directory, prefix + "." + filename_for(config, b1, b2)).encode()
+            return arr
+
+        writer = threading.Thread(target=write_loop, name="bdx-device-writer")
+        writer.start()
+        lib = classifier.lib
+        h = classifier.h
+
+        def check(rc):
+            if rc != 0:
+                raise BdxError(lib.bdx_last_error(h).decode())
+
+        slot = 0
+        fut = up.submit(upload_all, slot)
+        while True:
+            fut.result()
+            fut = None
+            if errors:
+                break
+            t0 = time.perf_counter()
+            ns, nexts = [], []
+            for inp in ins:
+                want = want_bytes(inp)
+                while True:
+                    nbytes, final = inp.win[slot]
+                    n, nxt = C.c_int64(0), C.c_int64(0)
+                    check(lib.bdx_fq_index_device(h, inp.text[slot].p, nbytes, int(final), batch_reads, inp.d_off.p,
+                                                  inp.d_len.p, C.byref(n), C.byref(nxt)))
+                    if n.value >= batch_reads or final:
+                        break
+                    want = 2 * max(want, nbytes)  # a record did not fit: a larger window
+                    busy["device_s"] += time.perf_counter() - t0
+                    upload(inp, slot, want)
+                    t0 = time.perf_counter()
+                ns.append(n.value)
+                nexts.append(nxt.value)
+            n = min(ns)
+            last = paired and ns[0] != ns[1]  # lock-step pairs: stop at the shorter file (core.jl:48)
+            if n == 0:
+                break
+            for inp, nx, k in zip(ins, nexts, ns):  # (the index's cursor is relative to the window = the input's cursor)
+                if k:
+                    inp.avg_record = nx / k
+                inp.cursor += nx
+                inp.f.release(inp.cursor)  # uploaded: the host pages of this batch can go
+            r1 = ins[0]
+            wins = [inp.win[slot][0] for inp in ins]
+            if not last:
+                fut = up.submit(upload_all, slot ^ 1)
+            # pack -> ONE classify call -> the gathers
+            nb1 = wins[0]
+            d_seq.ensure(nb1 + 64)
+            check(lib.bdx_fq_pack_device(h, r1.text[slot].p, nb1, r1.d_off.p, r1.d_len.p, n, d_seq.p, d_seq.cap,
+                                         d_seq_off.p, None))
+            classifier.classify_device(d_seq.p, d_seq_off.p, n, **{k: b.p for k, b in d_v.items()})
+            out_cap = sum(wins[i] + 64 for i, _, _ in outs)
+            d_out.ensure(out_cap)
+            blocks, pos = [], 0
+            for i, prefix, trim in outs:
+                inp = ins[i]
+                cb = np.zeros(n_classes, dtype=np.int64)
+                check(lib.bdx_fq_gather_device(h, inp.text[slot].p, wins[i], inp.d_off.p, inp.d_len.p, n, d_v["bc1"].p,
+                                               d_v["bc2"].p, stride, n_classes, d_v["keep_start"].p, d_v["keep_end"].p,
+                                               int(bool(trim)), d_out.p + pos, d_out.cap - pos, cb.ctypes.data))
+                blocks.append((pos, cb, prefix))
+                pos += int(cb.sum())
+            busy["device_s"] += time.perf_counter() - t0
+            busy["batches"] += 1
+            # download into a free host slot (the writer hands them back); the writer waits for the copy
+            while True:
+                try:
+                    hs = free.get(timeout=0.05)
+                    break
+                except queue.Empty:
+                    if errors:
+                        break
+            if errors:
+                break
+            if hbuf[hs] is None or len(hbuf[hs]) < pos:
+                hbuf[hs] = pinned_empty(max(pos, 1) + (max(pos, 1) >> 3), np.uint8)
+            if pos:
+                rt.check(rt.hipMemcpyAsync(hbuf[hs].ctypes.data, d_out.p, pos, _D2H, s_main), "hipMemcpyAsync (download)")
+            rt.check(rt.hipEventRecord(events[hs], s_main), "hipEventRecord")
+            q_w.put((hs, blocks))
+            if last:
+                break
+            slot ^= 1
+    except BaseException as e:  # noqa: BLE001
+        errors.append(e)
+    finally:
+        if fut is not None:  # (the upload thread may still write a device window)
+            try:
+                fut.result()
+            except BaseException:  # noqa: BLE001
+                pass
+        up.shutdown(wait=True)
+        if writer is not None:
+            q_w.put(None)
+            writer.join()
+        if s_main:
+            rt.hipStreamSynchronize(s_main)
+            classifier.set_stream(None)
+        for b in dbufs:
+            b.free()
+        for inp in ins:
+            inp.close()
+        for e in events:
+            rt.hipEventDestroy(e)
+        for s in (s_main, s_copy):
+            if s:
+                rt.hipStreamDestroy(s)
+    if timings is not None:
+        busy["wall_s"] = time.perf_counter() - t_wall
+        busy["threads"] = T
+        timings.update(busy)
+    if errors:
+        raise errors[0]

@@ -36,6 +36,8 @@ ABI_SYMBOLS = [
     "bdx_stats_shape", "bdx_get_stats",
     "bdx_window_uploads", "bdx_band_launches", "bdx_wave_launches", "bdx_pair_launches", "bdx_pipelined_calls", "bdx_staged_downloads", "bdx_last_list_reads", "bdx_rejected_windows",
     "bdx_debug_rejected_windows_total",
+    # device FASTQ pipeline (bdx_fastq.hip)
+    "bdx_fq_index_device", "bdx_fq_pack_device", "bdx_fq_gather_device",
 ]
 STATS_WHICH = {"pos": 0, "len": 1, "raw": 2}
 BDX_COMM_ID_BYTES = 128
@@ -229,6 +231,14 @@ def load_library(path: Optional[str] = None):
     L.bdx_rejected_windows.argtypes = [vp]
     L.bdx_debug_rejected_windows_total.restype = C.c_int64
     L.bdx_debug_rejected_windows_total.argtypes = []
+    L.bdx_fq_index_device.restype = C.c_int32
+    L.bdx_fq_index_device.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, vp, vp, C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int64)]
+    L.bdx_fq_pack_device.restype = C.c_int32
+    L.bdx_fq_pack_device.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
+    L.bdx_fq_gather_device.restype = C.c_int32
+    L.bdx_fq_gather_device.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32,
+                                       vp, C.c_int64, vp]
     if path is None:
         _lib = L
     return L

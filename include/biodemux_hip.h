@@ -250,6 +250,39 @@ int32_t bdx_get_reduced_counts(bdx_ctx *ctx, int64_t *out, int64_t n);
 void *bdx_host_alloc(size_t bytes);
 void bdx_host_free(void *p);
 
+/* Device FASTQ pipeline: FASTQ text already in device memory becomes per-output-file FASTQ blocks without a host
+ * round trip (the reference's reader_task / writer_task, core.jl:43-110, :118-224, on the device).  Each step has the
+ * contract of a host function of the project's FASTQ library (csrc/bdx_io.cpp), which the tests hold it to.  All three
+ * run on the context's stream and device and synchronise it before they return.  Line offsets are byte offsets
+ * relative to d_text; a record is 4 lines (header, sequence, plus, quality).
+ *
+ * bdx_fq_index_device: line table of d_text[0, text_len) for up to max_reads records (4 * max_reads entries of
+ * d_line_off / d_line_len).  A line's length excludes "\n" and a "\r" before it.  final == 0 (more text follows):
+ * only complete records.  final != 0: an unterminated last line counts, and a truncated last record is padded with
+ * (off = text_len, len = 0) lines.  *n_records: records indexed; *next: the offset after the last line consumed. */
+int32_t bdx_fq_index_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_len, int32_t final, int64_t max_reads,
+                            int64_t *d_line_off, int32_t *d_line_len, int64_t *n_records, int64_t *next);
+
+/* bdx_fq_pack_device: the sequence lines of records [0, n) packed as the chunk bdx_classify_device takes:
+ * d_seq_off[0] = 0, d_seq_off[i + 1] = d_seq_off[i] + length of read i (n + 1 entries).  d_seq holds seq_cap bytes
+ * (the sum of the lengths is at most text_len); *seq_bytes (optional) receives that sum. */
+int32_t bdx_fq_pack_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_len, const int64_t *d_line_off,
+                           const int32_t *d_line_len, int64_t n, uint8_t *d_seq, int64_t seq_cap, int64_t *d_seq_off,
+                           int64_t *seq_bytes);
+
+/* bdx_fq_gather_device: the output of one stream of a batch (R1 or R2).  Record i goes to class 0 (bc1 == 0,
+ * unknown), 1 (bc1 < 0, ambiguous) or 2 + (bc1 - 1) * stride + (max(bc2, 1) - 1); d_out receives the records
+ * class by class, in input order inside a class, each as header "\n" seq[a..b] "\n" plus "\n" qual[a..b'] "\n"
+ * ("\r" is never written).  trim != 0 and keep_start != -1: a = max(keep_start, 1), b = min(keep_end, seq length),
+ * b' = min(b, quality length), empty when a > b (core.jl:162-173); otherwise the lines are written whole.
+ * class_bytes (HOST memory, n_classes entries) receives the bytes of every class's block: the blocks follow each
+ * other in class order from d_out[0].  Fails with BDX_E_INVALID (class_bytes still filled) when they need more
+ * than out_cap bytes; text_len + 4 is always enough. */
+int32_t bdx_fq_gather_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_len, const int64_t *d_line_off,
+                             const int32_t *d_line_len, int64_t n, const int32_t *d_bc1, const int32_t *d_bc2,
+                             int32_t stride, int32_t n_classes, const int32_t *d_keep_start, const int32_t *d_keep_end,
+                             int32_t trim, uint8_t *d_out, int64_t out_cap, int64_t *class_bytes);
+
 /* Introspection for bench/tests: name of the kernel path a classify call will take, and numbers of the
  * last launch.  "generic": exact kernel only; "bitpar+verify": bit-vector sweep of every pair, then the exact
  * stage; "qgram+bitpar+verify": single-piece q-gram seeds in front of the sweep; "qgram2+bitpar+verify":
