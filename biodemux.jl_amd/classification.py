@@ -8,7 +8,8 @@ evaluated by the gfx950 kernel through the C-ABI (never on the CPU).
   find_best_matching_bc     classification.jl:722
   determine_filename        classification.jl:871
   DemuxStats / merge_stats  classification.jl:736-767 / reporting.jl:1-58 (scalar counters from the
-                            device; pos/len/score histograms accumulated on the host)
+                            device; pos/len/score histograms accumulated on the host, SURVEY §8f-3;
+                            merge_stats_tables sums the device tables of several contexts of one process)
 
 Argument order and meaning follow the Julia signatures so the parity tests read like the
 reference's own unit tests.  ``ref_search_range`` is a ``(first, last)`` tuple or a Python
@@ -278,6 +279,34 @@ def merge_stats(stats_list: List[DemuxStats]) -> DemuxStats:
                 for k, v in dd.items():
                     t[k] = t.get(k, 0) + v
     return m
+
+
+def merge_stats_tables(tables_list: List[dict]) -> dict:
+    """Sum the statistics tables of several device contexts (HipClassifier.stats_tables) on the host, for
+    DemuxStats.add_device_tables.  Each context sized its tables for the reads it saw, so the heights and ``key0``
+    differ: per pass and table the sum covers the union of the key ranges, [min key0, max(key0 + rows))."""
+    import numpy as np
+
+    merged: dict = {}
+    for p in tables_list[0]:
+        merged[p] = {}
+        for name in tables_list[0][p]:
+            parts = [t[p][name] for t in tables_list]
+            widths = {tab.shape[1] for tab, _ in parts}
+            if len(widths) != 1:
+                raise ValueError(f"statistics tables of pass {p} ({name}) disagree on the number of barcodes: {sorted(widths)}")
+            nb = widths.pop()
+            live = [(tab, key0) for tab, key0 in parts if tab.shape[0]]  # (a context that saw no batch has no rows)
+            if not live:
+                merged[p][name] = (np.zeros((0, nb), dtype=np.int64), parts[0][1])
+                continue
+            lo = min(key0 for _, key0 in live)
+            hi = max(key0 + tab.shape[0] for tab, key0 in live)
+            out = np.zeros((hi - lo, nb), dtype=np.int64)
+            for tab, key0 in live:
+                out[key0 - lo:key0 - lo + tab.shape[0]] += tab
+            merged[p][name] = (out, lo)
+    return merged
 
 
 def isinf(x: float) -> bool:

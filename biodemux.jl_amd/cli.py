@@ -16,6 +16,17 @@ from typing import List, Optional
 _FASTQ_ENDINGS = (".fastq", ".fq", ".fastq.gz", ".fq.gz")  # cli.jl:147 (case-sensitive, as there)
 
 
+def _device_indices(text: str) -> List[int]:
+    """``--devices 0,1,2`` -> [0, 1, 2] (an index may repeat: several contexts on one GPU)."""
+    try:
+        devs = [int(x) for x in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected a comma list of HIP device indices such as 0,1 (got {text!r})")
+    if any(d < 0 for d in devs):
+        raise argparse.ArgumentTypeError(f"device indices are >= 0 (got {text!r})")
+    return devs
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="biodemux_jl_amd", description="BioDemuX demultiplexing on MI355X (HIP backend)")
     p.add_argument("fastq1", help="Path to the first FASTQ file (Read 1) OR directory containing FASTQ files")
@@ -52,6 +63,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--matching-algorithm", default="semiglobal", help="Matching algorithm (semiglobal, hamming, exact)")
     p.add_argument("--log", "-l", action="store_true", help="Enable logging to stderr")
     p.add_argument("--device", type=int, default=0, help="HIP device index (this backend only)")
+    p.add_argument("--devices", type=_device_indices, default=None,
+                   help="Comma list of HIP device indices to deal the batches over, e.g. 0,1,2 (this backend only; "
+                        "not with --device)")
     return p
 
 
@@ -64,8 +78,11 @@ def main(argv: Optional[List[str]] = None, _execute=None) -> int:
     from .core import execute_demultiplexing
 
     run = _execute or execute_demultiplexing
+    parser = build_parser()
     try:
-        a = build_parser().parse_args(argv)
+        a = parser.parse_args(argv)
+        if a.devices is not None and a.device != 0:
+            parser.error("--devices cannot be combined with --device")
     except SystemExit as e:  # argparse has already printed the message
         return int(e.code or 0)
     try:
@@ -80,6 +97,8 @@ def main(argv: Optional[List[str]] = None, _execute=None) -> int:
             summary=a.summary, summary_format=a.summary_format, matching_algorithm=a.matching_algorithm, log=a.log)
         if _execute is None:
             common["device"] = a.device
+        if a.devices is not None:
+            common["devices"] = a.devices
 
         def paired(f1, f2):
             run(f1, f2, a.barcode_file, a.output_directory, output_prefix1=a.output_prefix1,

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import datetime as _dt
 import gzip
+import operator
 import os
 import re
 import sys
@@ -17,7 +18,7 @@ from typing import Callable, Dict, List, Optional
 
 import numpy as np
 
-from .classification import DemuxStats, filename_for
+from .classification import DemuxStats, filename_for, merge_stats_tables
 from .config import DemuxConfig, build_config
 from .fileio import read_fastq
 from . import deviceio, nativeio
@@ -81,9 +82,13 @@ def _log(msg: str):
 
 
 def _demux(fastq1: str, fastq2: Optional[str], config: DemuxConfig, output_directory: str, prefix1: str,
-           prefix2: str, classifier, batch_reads: int, on_batch=None) -> None:
+           prefix2: str, classifier, batch_reads: int, on_batch=None, batches_per_device: Optional[list] = None) -> None:
+    """``classifier`` may be a list of N classifiers: batch k then goes to classifier k % N, one batch at a time (the
+    plain statement of what nativeio's dealer does with threads); ``batches_per_device`` receives the counts."""
     writer = _Writer(output_directory, config)
     do_trim = config.trim_side is not None or config.trim_side2 is not None  # core.jl:240
+    classifiers = list(classifier) if isinstance(classifier, (list, tuple)) else [classifier]
+    dealt = [0] * len(classifiers)
 
     def flush(r1: List[list], r2: Optional[List[list]]):
         if not r1:
@@ -92,7 +97,9 @@ def _demux(fastq1: str, fastq2: Optional[str], config: DemuxConfig, output_direc
         off = np.zeros(len(seqs) + 1, dtype=np.int64)
         off[1:] = np.cumsum([len(s) for s in seqs])
         blob = np.frombuffer(b"".join(seqs), dtype=np.uint8) if off[-1] else np.zeros(0, dtype=np.uint8)
-        out = classifier.classify(blob, off)  # <- the hot path: one C-ABI call per batch
+        k = sum(dealt) % len(classifiers)
+        out = classifiers[k].classify(blob, off)  # <- the hot path: one C-ABI call per batch
+        dealt[k] += 1
         if on_batch is not None:
             on_batch(out)
         bc1, bc2, ks, ke = out["bc1"], out["bc2"], out["keep_start"], out["keep_end"]
@@ -138,11 +145,58 @@ def _demux(fastq1: str, fastq2: Optional[str], config: DemuxConfig, output_direc
                 flush(b1, None)
     finally:
         writer.close()
+        if batches_per_device is not None:
+            batches_per_device[:] = dealt
+
+
+def _device_list(device: int, devices, io: str) -> List[int]:
+    """The contexts of a run: ``devices`` (several entries may name one GPU), or ``[device]``."""
+    if devices is None:
+        return [device]
+    if isinstance(devices, (str, bytes)):
+        raise TypeError("devices must be a sequence of HIP device indices, e.g. [0, 1]")
+    devs = [operator.index(d) for d in devices]
+    if not devs:
+        raise ValueError("devices is empty: name at least one HIP device")
+    if any(d < 0 for d in devs):
+        raise ValueError(f"device indices are >= 0 (got devices={devs})")
+    if device != 0:
+        raise ValueError("pass either device= or devices=, not both")
+    if len(devs) > 1 and io == "device":
+        # the device pipeline finds batch k + 1's first record only after batch k's index ran on the device: dealing
+        # batches over contexts needs another design (DESIGN §9), and falling back to the host pipeline would hide that
+        raise ValueError("_io='device' drives one device context: batch boundaries are found on the device, so batches "
+                         "cannot be dealt over several devices; use _io='native' (or 'auto') with devices=")
+    return devs
+
+
+def _open_classifiers(config: DemuxConfig, devs: List[int], factory) -> list:
+    """One context per entry of ``devs``; if one fails to open, the ones already open are closed first."""
+    out = []
+    try:
+        for d in devs:
+            out.append(factory(config) if factory else HipClassifier(config, device=d))
+    except BaseException:
+        _close_all(out)
+        raise
+    return out
+
+
+def _close_all(classifiers) -> None:
+    """close() every classifier, also when one of them fails; the first failure is raised afterwards."""
+    first = None
+    for c in classifiers:
+        try:
+            c.close()
+        except BaseException as e:  # noqa: BLE001
+            first = first or e
+    if first is not None:
+        raise first
 
 
 def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxConfig], object]] = None,
                            _batch_reads: int = DEFAULT_BATCH_READS, _io: str = "auto", device: int = 0,
-                           _timings: Optional[dict] = None, **kw):
+                           devices=None, _timings: Optional[dict] = None, **kw):
     """execute_demultiplexing(FASTQ_file, barcode_file, output_directory; kwargs...)      core.jl:500
     execute_demultiplexing(FASTQ_file1, FASTQ_file2, barcode_file, output_directory; ...)  core.jl:360
 
@@ -152,8 +206,12 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
     split by output file and gather on the GPU, deviceio.py: needs the HIP classifier).
     ``_classifier_factory`` is a test seam: the parity tests on CPU pass the oracle here to
     check this file contract; the product default is the HIP classifier and nothing else.
+    ``devices`` (a sequence of HIP device indices, None = ``[device]``): one device context per entry — repeated entries
+    put several contexts on one GPU — and the batches are dealt over them (merge_stats over the workers, core.jl:587-599);
+    output files, counters and reports are those of one context.  ``_io="device"`` takes a single device.
     ``_timings`` (a dict) receives the busy seconds of the native pipeline's stages (bench.py's end-to-end figure; with
-    _io="device": upload_s, device_s, download_s, write_s and batches).
+    _io="device": upload_s, device_s, download_s, write_s and batches; with several devices also devices,
+    classify_s_per_device and batches_per_device, classify_s being their sum).
     Returns the DemuxStats scalar counters (the reference returns nothing)."""
     if len(args) == 3:
         fastq1, barcode_file, output_directory = args
@@ -179,6 +237,8 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
     if unknown:
         raise TypeError(f"unsupported keyword argument(s): {sorted(unknown)}")
     o = {**defaults, **kw}
+    devs = _device_list(device, devices, _io)
+    multi = len(devs) > 1
 
     start_time = _dt.datetime.now()
     if o["log"]:  # core.jl:394-407 / :531-543
@@ -215,7 +275,11 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         raise ValueError("_io='device': the device FASTQ pipeline needs the HIP classifier (no _classifier_factory)")
     # summary=true: the HIP classifier collects the histograms of classification.jl:827-865 on the device
     # (bdx_get_stats); a test-injected classifier without such tables hands over per-pass outputs instead
-    classifier = _classifier_factory(config) if _classifier_factory else HipClassifier(config, device=device)
+    if multi:
+        classifiers = _open_classifiers(config, devs, _classifier_factory)
+        classifier = classifiers[0]
+    else:
+        classifier = _classifier_factory(config) if _classifier_factory else HipClassifier(config, device=devs[0])
     if _timings is not None:  # barcode table + device context: before the first batch can move
         _timings["setup_s"] = (_dt.datetime.now() - start_time).total_seconds()
     device_stats = hasattr(classifier, "stats_tables")
@@ -236,17 +300,33 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
                                   _timings)
         elif use_native:
             t_call = _dt.datetime.now()
-            nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifier, _batch_reads,
-                                  on_batch, _timings)
+            nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2,
+                                  classifiers if multi else classifier, _batch_reads, on_batch, _timings)
             if _timings is not None:  # (beyond the pipeline's own wall clock: releasing its batch buffers)
                 _timings["native_call_s"] = (_dt.datetime.now() - t_call).total_seconds()
+        elif multi:
+            dealt: List[int] = []
+            _demux(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers, _batch_reads, on_batch,
+                   dealt)
+            if _timings is not None:
+                _timings["batches_per_device"] = dealt
         else:
             _demux(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifier, _batch_reads, on_batch)
-        counts = np.asarray(classifier.counts)
-        tables = classifier.stats_tables() if (config.summary and device_stats) else None
+        if multi:  # merge_stats (reporting.jl:1-9) over the contexts: a host sum of a few KB, no collective
+            counts = np.sum([np.asarray(c.counts, dtype=np.int64) for c in classifiers], axis=0)
+            tables = (merge_stats_tables([c.stats_tables() for c in classifiers]) if (config.summary and device_stats)
+                      else None)
+            if _timings is not None:
+                _timings["devices"] = list(devs)
+        else:
+            counts = np.asarray(classifier.counts)
+            tables = classifier.stats_tables() if (config.summary and device_stats) else None
     finally:
         t_close = _dt.datetime.now()
-        classifier.close()
+        if multi:
+            _close_all(classifiers)
+        else:
+            classifier.close()
         if _timings is not None:  # releasing the device context (staging buffers, tables)
             _timings["close_s"] = (_dt.datetime.now() - t_close).total_seconds()
 
@@ -263,7 +343,7 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
             for k in ("pos_counts", "len_counts", "score_counts", "per_bc_score_counts", "per_bc_pos_counts",
                       "per_bc_len_counts"):
                 setattr(stats, f"{f}_{k}", getattr(hist, f"{f}_{k}"))
-    if config.summary:  # core.jl:493-497 / :626-630 (merge_stats over the workers: one device context here)
+    if config.summary:  # core.jl:493-497 / :626-630 (merge_stats over the workers: summed over the device contexts above)
         generate_summary_report(stats, config, output_directory, fastq1, barcode_file, fastq2, o["barcode_file2"],
                                 bc_complement=o["bc_complement"], bc_rev=o["bc_rev"], trim_side=o["trim_side"],
                                 trim_side2=o["trim_side2"], n_threads=1, duration=duration)

@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import threading
 from typing import Optional
 
 import numpy as np
@@ -136,13 +137,17 @@ class FastqFile:
 # five sets in flight).  A run takes its sets from here and puts them back: the next execute_demultiplexing of the process
 # neither allocates nor page-faults them again, and a run's return does not spend 30 ms giving 600 MB back to the kernel
 # (measured: 10 M reads, 0.326 s per call of which 0.030 s after the last batch was written).  `release_buffers()` empties it.
+# A run over several device contexts takes more sets (see demux_native) but gives back at most _BUFFER_POOL_MAX: the pool
+# keeps what one single-device run needs, not N times that.  Concurrent runs of one process share it under _BUFFER_POOL_LOCK.
 _BUFFER_POOL: list = []
 _BUFFER_POOL_MAX = 5
+_BUFFER_POOL_LOCK = threading.Lock()
 
 
 def release_buffers() -> None:
     """Drop the batch buffers kept from finished runs (a long-running host that is done demultiplexing)."""
-    del _BUFFER_POOL[:]
+    with _BUFFER_POOL_LOCK:
+        del _BUFFER_POOL[:]
 
 
 def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
@@ -150,11 +155,16 @@ def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: s
     """Native counterpart of core._demux: index -> pack -> ONE C-ABI classify call -> in-order write,
     as a three-stage pipeline (reader thread | classify on the calling thread | writer thread; the
     native calls release the GIL).  Batches flow through bounded FIFO queues, so per-file order is
-    input order exactly as with the reference's single writer task (core.jl:139-148)."""
+    input order exactly as with the reference's single writer task (core.jl:139-148).
+
+    ``classifier`` may also be a list of N > 1 classifiers (one per device context): then N classify threads take the
+    batches from the reader as they come free (first free context wins) and a reorder step hands the results to the
+    writer strictly by batch id, so the files are those of a single context.  ``on_batch`` is then called under a lock."""
     import queue
-    import threading
     import time
 
+    classifiers = list(classifier) if isinstance(classifier, (list, tuple)) else [classifier]
+    N = len(classifiers)
     busy = {"index_s": 0.0, "pack_s": 0.0, "classify_s": 0.0, "write_s": 0.0, "batches": 0}
     t_wall = time.perf_counter()
     L = _load()
@@ -174,12 +184,23 @@ def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: s
     # the verdict vectors are allocated a handful of times per run, not once per batch (fresh arrays of this size are
     # page-faulted in by whoever writes them first: ~15 % of the reader's time)
     free: "queue.Queue" = queue.Queue()
-    bufs = [(_BUFFER_POOL.pop() if _BUFFER_POOL else {}) for _ in range(5)]  # one per stage (reader, classify, writer) + one waiting in front of each of the two consumers
+    # One context: one set per stage (reader, classify, writer) + one waiting in front of each of the two consumers.
+    # N contexts: 1 being filled by the reader + 1 waiting in q_in + N in the contexts + N - 1 results parked early in the
+    # reorder step (while the oldest batch is still being classified) + 1 being written + 1 queued for the writer = 2N + 3.
+    # The count only decides how much overlaps; the dealer cannot deadlock with any count >= 1: every set is owned by a
+    # batch that was read and is not yet written.  If the reader waits for a set, let r be the oldest of those batches.
+    # Every batch before r is written, so r is never parked: it is in q_in or in a context (which classify it without
+    # waiting for anything: the reorder step and the writer's queue are unbounded, their size is bounded by the sets),
+    # or with the writer.  Either way r reaches the disk and its set comes back.
+    n_sets = 5 if N == 1 else 2 * N + 3
+    with _BUFFER_POOL_LOCK:
+        bufs = [(_BUFFER_POOL.pop() if _BUFFER_POOL else {}) for _ in range(n_sets)]
     for b in bufs:
         free.put(b)
 
     def reader():
         try:
+            bid = 0
             while True:
                 # (a batch dropped on an error path never comes back through `free`: poll, and stop once anything failed —
                 # the reader must always reach its final q_in.put(None), or the caller waits for it forever)
@@ -213,7 +234,8 @@ def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: s
                     buf["so"] = so.base
                 busy["index_s"] += t1 - t0
                 busy["pack_s"] += time.perf_counter() - t1
-                q_in.put((n, off1, ln1, off2, ln2, seq, so, f1.cursor, f2.cursor if f2 is not None else 0, buf))
+                q_in.put((bid, n, off1, ln1, off2, ln2, seq, so, f1.cursor, f2.cursor if f2 is not None else 0, buf))
+                bid += 1
                 if last:
                     break
         except BaseException as e:  # noqa: BLE001 - forwarded to the caller
@@ -240,7 +262,8 @@ def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: s
     # share a batch by class range — each file then still belongs to exactly one of them, in batch order: per-file order
     # = input order, core.jl:139-148 — which pays on file systems without shared writable mappings.)
     ranges = [(0, n_classes)]
-    q_outs = [queue.Queue(maxsize=1) for _ in ranges]
+    # (with N contexts the reorder step puts into these under its lock: they must never block — the batch sets bound them)
+    q_outs = [queue.Queue(maxsize=1 if N == 1 else 0) for _ in ranges]
     done_lock = threading.Lock()
 
     def writer(wi):
@@ -286,63 +309,119 @@ def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: s
                     break
                 free.put(item[10])
 
+    def classify_batch(cl, item):
+        """One batch through one context -> (verdicts, the writer's item, seconds in classify)."""
+        _bid, n, off1, ln1, off2, ln2, seq, so, cur1, cur2, buf = item
+        tc0 = time.perf_counter()
+        res = buf.get("out")
+        reuse = (res is not None and len(res["bc1"]) >= n and getattr(cl, "want_pass", False) is False
+                 and hasattr(cl, "lib"))  # (the HIP wrapper takes result arrays to reuse; test doubles may not)
+        if reuse:
+            out = cl.classify(seq, so, out={k: v[:n] for k, v in res.items()})  # <- the hot path: one C-ABI call per batch
+        else:
+            out = cl.classify(seq, so)
+            if set(out) == {"bc1", "bc2", "keep_start", "keep_end"}:
+                buf["out"] = out
+        dt = time.perf_counter() - tc0
+        bc1, bc2 = out["bc1"], out["bc2"]
+        cls = buf.get("cls")
+        if cls is None or len(cls) < n:
+            cls = buf["cls"] = np.empty(max(n, batch_reads), dtype=np.int32)
+        cls = cls[:n]
+        # class of a read: 0 unknown, 1 ambiguous, 2 + (bc1 - 1) * stride + (bc2 - 1) matched
+        np.subtract(bc1, 1, out=cls)
+        if stride != 1:
+            np.multiply(cls, stride, out=cls)
+            cls += np.maximum(bc2, 1)
+            cls += 1
+        else:
+            cls += 2
+        cls[bc1 == 0] = 0
+        cls[bc1 < 0] = 1
+        ks = np.ascontiguousarray(out["keep_start"], dtype=np.int32)
+        ke = np.ascontiguousarray(out["keep_end"], dtype=np.int32)
+        used = np.flatnonzero(np.bincount(cls, minlength=n_classes))
+        pending = [len(ranges)]
+        return out, (n, off1, ln1, off2, ln2, cls, ks, ke, cur1, cur2, buf, pending, used), dt
+
+    # ---- N > 1: the dealer (one classify thread per context, a reorder step in front of the writer) ----
+    per_dev_s = [0.0] * N
+    per_dev_b = [0] * N
+    parked: dict = {}  # batch id -> the writer's item, for results that finished before an older batch
+    next_id = [0]
+    order_lock = threading.Lock()
+    batch_lock = threading.Lock()  # serialises on_batch (the summary of an injected classifier)
+
+    def worker(k):
+        cl = classifiers[k]
+        while True:
+            item = q_in.get()
+            if item is None:
+                q_in.put(None)  # the end mark goes on to the next worker (at most one is ever in the queue)
+                return
+            if errors:
+                free.put(item[-1])
+                continue
+            try:
+                out, witem, dt = classify_batch(cl, item)
+                if on_batch is not None:
+                    with batch_lock:
+                        on_batch(out)
+            except BaseException as e:  # noqa: BLE001 - forwarded to the caller
+                errors.append(e)
+                free.put(item[-1])
+                continue
+            per_dev_s[k] += dt
+            per_dev_b[k] += 1
+            with order_lock:  # release strictly by batch id: per-file order = input order (core.jl:139-148)
+                parked[item[0]] = witem
+                while next_id[0] in parked:
+                    w = parked.pop(next_id[0])
+                    for qw in q_outs:
+                        qw.put(w)
+                    next_id[0] += 1
+
     tr = threading.Thread(target=reader, name="bdx-reader")
     tws = [threading.Thread(target=writer, args=(wi,), name=f"bdx-writer-{wi}") for wi in range(len(ranges))]
+    tks = [threading.Thread(target=worker, args=(k,), name=f"bdx-classify-{k}") for k in range(N)] if N > 1 else []
     tr.start()
     for tw in tws:
         tw.start()
     try:
-        while True:
-            item = q_in.get()
-            if item is None:
-                break
-            if errors:
-                free.put(item[-1])
-                continue
-            n, off1, ln1, off2, ln2, seq, so, cur1, cur2, buf = item
-            tc0 = time.perf_counter()
-            res = buf.get("out")
-            reuse = (res is not None and len(res["bc1"]) >= n and getattr(classifier, "want_pass", False) is False
-                     and hasattr(classifier, "lib"))  # (the HIP wrapper takes result arrays to reuse; test doubles may not)
-            if reuse:
-                out = classifier.classify(seq, so, out={k: v[:n] for k, v in res.items()})  # <- the hot path: one C-ABI call per batch
-            else:
-                out = classifier.classify(seq, so)
-                if set(out) == {"bc1", "bc2", "keep_start", "keep_end"}:
-                    buf["out"] = out
-            busy["classify_s"] += time.perf_counter() - tc0
-            busy["batches"] += 1
-            if on_batch is not None:
-                on_batch(out)
-            bc1, bc2 = out["bc1"], out["bc2"]
-            cls = buf.get("cls")
-            if cls is None or len(cls) < n:
-                cls = buf["cls"] = np.empty(max(n, batch_reads), dtype=np.int32)
-            cls = cls[:n]
-            # class of a read: 0 unknown, 1 ambiguous, 2 + (bc1 - 1) * stride + (bc2 - 1) matched
-            np.subtract(bc1, 1, out=cls)
-            if stride != 1:
-                np.multiply(cls, stride, out=cls)
-                cls += np.maximum(bc2, 1)
-                cls += 1
-            else:
-                cls += 2
-            cls[bc1 == 0] = 0
-            cls[bc1 < 0] = 1
-            ks = np.ascontiguousarray(out["keep_start"], dtype=np.int32)
-            ke = np.ascontiguousarray(out["keep_end"], dtype=np.int32)
-            used = np.flatnonzero(np.bincount(cls, minlength=n_classes))
-            pending = [len(ranges)]
-            for qw in q_outs:
-                qw.put((n, off1, ln1, off2, ln2, cls, ks, ke, cur1, cur2, buf, pending, used))
+        if N > 1:
+            for tk in tks:
+                tk.start()
+            for tk in tks:
+                tk.join()
+        else:
+            while True:
+                item = q_in.get()
+                if item is None:
+                    break
+                if errors:
+                    free.put(item[-1])
+                    continue
+                out, witem, dt = classify_batch(classifiers[0], item)
+                busy["classify_s"] += dt
+                busy["batches"] += 1
+                if on_batch is not None:
+                    on_batch(out)
+                for qw in q_outs:
+                    qw.put(witem)
     except BaseException as e:  # noqa: BLE001
         errors.append(e)
-        while True:
+        for tk in tks:  # (the workers drain q_in once they see the error, the reader stops on it)
+            if tk.ident is not None:
+                tk.join()
+        while True:  # (what is left: everything, or — behind the workers — the end mark they passed on)
             item = q_in.get()
             if item is None:
                 break
             free.put(item[-1])
     finally:
+        for w in parked.values():  # (only after an error: results behind a batch that never came)
+            free.put(w[10])
+        parked.clear()
         for qw in q_outs:
             qw.put(None)
         tr.join()
@@ -351,10 +430,16 @@ def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: s
         f1.close()
         if f2 is not None:
             f2.close()
-        for b in bufs:  # (every thread has been joined: nobody holds a set any more)
-            if len(_BUFFER_POOL) < _BUFFER_POOL_MAX:
-                _BUFFER_POOL.append(b)
+        with _BUFFER_POOL_LOCK:
+            for b in bufs:  # (every thread has been joined: nobody holds a set any more)
+                if len(_BUFFER_POOL) < _BUFFER_POOL_MAX:
+                    _BUFFER_POOL.append(b)
     if timings is not None:  # busy seconds of the three overlapped stages (reader = index + pack | classify | writer)
+        if N > 1:  # (classify_s: summed over the contexts, which overlap each other)
+            busy["classify_s"] = sum(per_dev_s)
+            busy["batches"] = sum(per_dev_b)
+            busy["classify_s_per_device"] = per_dev_s
+            busy["batches_per_device"] = per_dev_b
         busy["wall_s"] = time.perf_counter() - t_wall
         busy["threads"] = T
         timings.update(busy)
