@@ -1281,9 +1281,11 @@ bool size_pairs(bdx_ctx *ctx, BdxWavePlan &wp, int read_len) {
 
 // Geometry of the fused kernel for a given typical read length: the largest R whose LDS
 // footprint still lets two workgroups share a CU (8 waves/CU), else whatever fits.
+// set: the filter set planned (0: full budgets, 1: tier 1).
 // force_slot: list mode (tier 0 of the tiered budgets) — the reads are scattered, every read is staged into a slot
-bool size_bitpar(bdx_ctx *ctx, int read_len, long long n_reads, bool force_slot = false) {
-    BdxBitparPlan &bp = ctx->F().bplan;
+bool size_bitpar(bdx_ctx *ctx, int set, int read_len, long long n_reads, bool force_slot = false) {
+    BdxFilterSet &F = ctx->fs[set];
+    BdxBitparPlan &bp = F.bplan;
     if (!bp.enabled) return false;
     if (read_len < 1) read_len = 1;
     if (ctx->dev.vlen) force_slot = true;  // window upload: only each read's window is there
@@ -1339,20 +1341,20 @@ bool size_bitpar(bdx_ctx *ctx, int read_len, long long n_reads, bool force_slot 
     const int slot = slot_mode ? ((wmax + 15 + 16 + 15) & ~15) : 0;
     bp.slot_bytes = slot;
     bp.seed_span = slot_mode ? wmax : read_len;
-    if (ctx->F().splan.enabled && ctx->F().splan.diag) {
+    if (F.splan.enabled && F.splan.diag) {
         // index width for this read length, and the sweep queue for the expected number of flagged pairs
         if (bp.seed_span > 312) {  // the widest index holds 320 positions: weak single seeds if they apply, else the plain sweep
-            ctx->F().splan = ctx->F().splan_alt;  // (disabled if weak seeds do not apply either)
-            ctx->F().splan_alt = BdxSeedPlan{};
-            return size_bitpar(ctx, read_len, n_reads, force_slot);
+            F.splan = F.splan_alt;  // (disabled if weak seeds do not apply either)
+            F.splan_alt = BdxSeedPlan{};
+            return size_bitpar(ctx, set, read_len, n_reads, force_slot);
         }
         bp.diag_nw = bp.seed_span <= 152 ? 5 : 10;
         const double L = (double)(bp.seed_span < 32 ? 32 : bp.seed_span);
-        const double flagged = ctx->F().splan.diag_flag_coef * ((L - 3.0) / 256.0) * ((L - 3.0) / 256.0) / (L + 24.0) +
-                               (double)(ctx->F().splan.n_always[0] + ctx->F().splan.n_always[1]);
+        const double flagged = F.splan.diag_flag_coef * ((L - 3.0) / 256.0) * ((L - 3.0) / 256.0) / (L + 24.0) +
+                               (double)(F.splan.n_always[0] + F.splan.n_always[1]);
         bp.diag_qcap = (int)(flagged * 1.3) + 12;  // per read (a sub-batch shares 4..8 reads' worth)
     }
-    const bool diag = ctx->F().splan.enabled && ctx->F().splan.diag;
+    const bool diag = F.splan.enabled && F.splan.diag;
     const int tries[7] = {256, 128, 64, 32, 16, 8, 4};
     int best_R = 0, best_blocks = 0, best_stage = 0;
     for (int R : tries) {
@@ -1360,14 +1362,14 @@ bool size_bitpar(bdx_ctx *ctx, int read_len, long long n_reads, bool force_slot 
         if (forced && R != forced) continue;
         if (!forced && R > r_cap) continue;
         if (bp.word_bytes == 16 && (R > 64 || R < 16)) continue;  // (128-bit sweep words: instantiated for tiles of 64 / 32 / 16 reads)
-        if (!forced && !ctx->F().splan.enabled && R > 64 && read_len <= 1024) continue;  // sweep-all: 64-read tiles measured best
+        if (!forced && !F.splan.enabled && R > 64 && read_len <= 1024) continue;  // sweep-all: 64-read tiles measured best
         size_t st = slot_mode ? (size_t)R * (size_t)slot : (size_t)R * (size_t)read_len + 64;
         st = (st + 15) & ~(size_t)15;
         if (st > (size_t)1 << 20) continue;
         bp.reads_per_block = R;
         bp.stage_bytes = (int)st;
         bp.read_len_hint_for_lds = read_len;
-        const size_t lds = bdx_bitpar_lds_bytes(ctx->dev, bp, ctx->plan, &ctx->F().splan);
+        const size_t lds = bdx_bitpar_lds_bytes(ctx->dev, bp, ctx->plan, &F.splan);
         if (lds > LDS_MAX) continue;
         int blocks = (int)(LDS_MAX / (((lds + 1279) / 1280) * 1280));  // LDS is allocated in 1280-byte granules (measured: 54128 B -> 2 per CU, 51872 B -> 3)
         // Measured on MI355X (tools/probe.py): tile size matters more than residency once 3
@@ -1384,9 +1386,9 @@ bool size_bitpar(bdx_ctx *ctx, int read_len, long long n_reads, bool force_slot 
     if (best_R && diag && best_blocks < 2) {
         // the index leaves room for one workgroup per CU only (very many barcodes): weak single seeds if they
         // apply, else the plain sweep
-        ctx->F().splan = ctx->F().splan_alt;  // (disabled if weak seeds do not apply either)
-        ctx->F().splan_alt = BdxSeedPlan{};
-        return size_bitpar(ctx, read_len, n_reads, force_slot);
+        F.splan = F.splan_alt;  // (disabled if weak seeds do not apply either)
+        F.splan_alt = BdxSeedPlan{};
+        return size_bitpar(ctx, set, read_len, n_reads, force_slot);
     }
     if (best_R) {
         bp.reads_per_block = best_R;
@@ -1395,16 +1397,16 @@ bool size_bitpar(bdx_ctx *ctx, int read_len, long long n_reads, bool force_slot 
         bp.read_len_hint_for_lds = read_len;
         return true;
     }
-    if (ctx->F().splan.enabled) {
+    if (F.splan.enabled) {
         // the seed tables do not fit next to everything else (very many barcodes): the two-intact-pieces index
         // gives way to the weak single seeds kept beside it; those give way to the plain sweep; plan again
-        if (ctx->F().splan.diag && ctx->F().splan_alt.enabled) {
-            ctx->F().splan = ctx->F().splan_alt;
-            ctx->F().splan_alt = BdxSeedPlan{};
+        if (F.splan.diag && F.splan_alt.enabled) {
+            F.splan = F.splan_alt;
+            F.splan_alt = BdxSeedPlan{};
         } else {
-            ctx->F().splan.enabled = 0;
+            F.splan.enabled = 0;
         }
-        return size_bitpar(ctx, read_len, n_reads, force_slot);
+        return size_bitpar(ctx, set, read_len, n_reads, force_slot);
     }
     bp.reads_per_block = 0;
     bp.read_len_hint = 0;
@@ -2353,7 +2355,14 @@ void bdx_destroy(bdx_ctx *ctx) {
 
 int32_t bdx_set_stream(bdx_ctx *ctx, void *hip_stream) {
     if (!ctx) return BDX_E_INVALID;
-    ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+    if (s != ctx->stream) {
+        // the scratch half the next call takes was cleared by a launch on the old stream, which the new one is not ordered
+        // after: the next call clears its scratch words itself
+        ctx->scratch_clean[0] = ctx->scratch_clean[1] = false;
+        ctx->scratch_zeroed = false;
+    }
+    ctx->stream = s;
     return BDX_OK;
 }
 
@@ -2369,6 +2378,392 @@ int32_t bdx_sync(bdx_ctx *ctx) {
     return BDX_OK;
 }
 
+// ---- one filtered classify call: plan (every size_* call), reserve (buffers, poison, scratch), enqueue ----------------
+// The fused kernel filters; the exact DP runs at full width in the generic kernel:
+//  * split (trimming / summary / weighted costs / N-scoring / Hamming / exact): every read's candidate mask (+ column
+//    windows) goes through HBM, the generic kernel gives every verdict;
+//  * known-score configs: the fused kernel also gives the verdict of (nearly) every read by replaying the reducer; the few
+//    it cannot settle are listed and evaluated by the generic kernel in list mode;
+//  * tiered budgets (known-score configs whose full budget is too large for selective single seeds): tier 1 — capped
+//    budgets, single seeds — runs over the whole batch and settles every read whose verdict cannot depend on a barcode
+//    beyond the cap; tier 0 — the full budget — then runs in list mode over the rest.
+// A call runs up to five stages in this order: front, tier 1's exact launch, middle, full-budget filter, exact.
+
+// Front stage.  Tiered: tier 1 over every read of the batch — bitpar (the fused kernel), wave / wave_win / wave_end (the wave
+// kernel answers what it can settle and lists the rest), wave_split (the wave kernel as a filter: tier 1's exact launch settles
+// and lists), pairs (the same-diagonal pairs mode as a filter).  Plain configs: wave, wave_win or wave_end in front of the same
+// filter set in list mode.
+enum class Front { none, bitpar, wave, wave_win, wave_split, wave_end, pairs };
+// Middle stage: the pairs mode of the wave kernel (bdx_pairs.hip).  end: known-end / known-alignment form over tier 1's
+// list; list: known-score form over it; split: tier 0's filter over it; all: the only filter, over every read.
+enum class Middle { none, end, list, split, all };
+enum class Full { none, wave_split, bitpar };  // the full-budget filter (none: the pairs mode already filtered)
+enum class Exact { known, split, split_list };  // the generic kernel: over the fused kernel's hand-over list / dense / over a list
+
+struct CallPlan {
+    int npass = 1, tier_len = 0, batch_len = 0;  // tier_len > 0: tiered; batch_len: the read length the launches were planned for
+    bool split = false, windows = false, dense_w = false;
+    int short_lb[2] = {0, 0};
+    Front front = Front::none;
+    bool t1_exact = false;  // tier 1's exact launch
+    Middle middle = Middle::none;
+    Full full = Full::bitpar;
+    Exact exact = Exact::known;
+    bool carry = false, aln = false;  // carried passes (d_carry); the known-end forms run as the known-alignment class
+    BdxWavePlan *wfront = nullptr, *wmid = nullptr;  // the wave plans the front / middle stage launch
+};
+
+static int plan_call(bdx_ctx *ctx, const BdxDevOut &o, bool stats, long long n_reads, int batch_len, int tier_len, CallPlan &p) {
+    if (n_reads > 0xFFFFFFF0LL) return fail(ctx, BDX_E_INVALID, "more than 2^32 reads in one batch");
+    const BdxDevCfg &dev = ctx->dev;
+    BdxFilterSet &f0 = ctx->fs[0], &f1 = ctx->fs[1];
+    const bool tiered = tier_len > 0;
+    p.npass = dev.is_dual ? 2 : 1;
+    p.tier_len = tier_len;
+    p.batch_len = batch_len;
+    for (int k = 0; k < p.npass; ++k) p.split |= !f0.bplan.known_ok[k];
+    // (:exact returns the occurrence's start and end whatever the output policy: a caller that wants them gets the launch in
+    // its split form — known-alignment class first, exact kernel for what that lists)
+    if (dev.algorithm == BDX_ALG_EXACT && (o.pass_start != nullptr || o.pass_end != nullptr)) p.split = true;
+    p.windows = p.split && !ctx->tune.no_windows;
+    // dense window table of the plain-sweep kernel (few barcodes, many genuine candidates per read; columns fit 16 bits)
+    p.dense_w = p.windows && f0.bplan.dense_d && !f0.splan.enabled && batch_len <= 60000 && !ctx->tune.no_dense;
+    // restricted runs of passes that only report score (+ end) through the clean-class DP start m + kb columns before
+    // the first end column (orc_selftest_clean_short_lookback); everything else keeps 2 (m + kb) + 1
+    for (int k = 0; k < p.npass; ++k) {
+        const int ts = dev.pass[k].trim_side;
+        p.short_lb[k] = (ctx->plan.clean || ctx->plan.band_roll) && dev.algorithm == BDX_ALG_SEMIGLOBAL && !dev.need_traceback &&
+                        (ts == 0 || (ts == 5 && o.pass_start == nullptr));
+    }
+    for (BdxFilterSet &f : ctx->fs) {
+        f.bplan.short_lb[0] = p.short_lb[0];
+        f.bplan.short_lb[1] = p.short_lb[1];
+        f.bplan.n_cu = ctx->n_cu;
+    }
+    // Wave-autonomous kernel (bdx_wave.hip) in front of the general one: it answers the reads of the known-score
+    // class and lists the rest — as tier 1 of a tiered config, or (plain configs) ahead of the same filter set
+    // in list mode.  The list-mode plan is made first: if it cannot be made, the general kernel runs alone.
+    // (window mode first: reads much longer than their column window — only the windows are fetched)
+    if (!p.split && !dev.vlen) {
+        BdxWavePlan &wp = tiered ? f1.wplan : f0.wplan;
+        if ((size_wave_win(ctx, wp, batch_len, n_reads) || size_wave(ctx, wp, batch_len, n_reads)) &&
+            (tiered || size_bitpar(ctx, 0, batch_len, n_reads, true))) {
+            p.front = wp.winm ? Front::wave_win : Front::wave;
+            p.wfront = &wp;
+        }
+        if (!tiered && p.front == Front::none) (void)size_bitpar(ctx, 0, batch_len, n_reads);  // (restore the dense plan)
+    }
+    // Known-end class (trim_side = 5, single pass, no start positions or statistics wanted): the same kernel in its
+    // known-end form answers the reads it can settle, trimmed keep range included; the listed rest goes through the
+    // split path (filter in list mode -> exact kernel in list mode).
+    bool trim3 = false;  // (a trim_side = 3 pass of the known-trim class knows its start only)
+    for (int k = 0; k < p.npass; ++k) trim3 |= dev.pass[k].trim_side == 3;
+    const bool kend_ok = p.split && p.windows && !dev.vlen && !p.dense_w && o.pass_start == nullptr && !stats && !(trim3 && o.pass_end != nullptr);
+    // known-alignment class: the caller wants positions the known-trim class does not know, or the statistics tables
+    p.aln = p.split && p.windows && !dev.vlen && !p.dense_w && !kend_ok && ctx->fs[tiered ? 1 : 0].wplan_a.enabled;
+    if (kend_ok || p.aln) {
+        BdxWavePlan &wk = tiered ? (p.aln ? f1.wplan_a : f1.wplan_k) : (p.aln ? f0.wplan_a : f0.wplan_k);
+        if (size_wave(ctx, wk, batch_len, n_reads)) {
+            if (tiered || size_bitpar(ctx, 0, batch_len, n_reads, true)) {
+                p.front = Front::wave_end;
+                p.wfront = &wk;
+            } else {
+                (void)size_bitpar(ctx, 0, batch_len, n_reads);  // (restore the dense plan)
+            }
+        }
+    }
+    // split configs (trimming, summary, weighted costs): the wave kernel as the FILTER of a dense launch — candidate
+    // masks and column windows in the formats of the general kernel's split mode, every verdict from the exact
+    // kernel as before.  Tiered: tier 1 (all reads); plain: the only filter launch.
+    bool wsplit0 = false;
+    if (p.split && p.windows && !dev.vlen && p.front == Front::none) {
+        if (tiered && f1.wplan.split && size_wave(ctx, 1, batch_len, n_reads)) p.front = Front::wave_split;
+        if (!tiered) wsplit0 = f0.wplan.split && !p.dense_w && size_wave(ctx, 0, batch_len, n_reads);
+    }
+    // the pairs tier: tier 1's filter is the same-diagonal pairs mode over every read of the batch
+    if (tiered && p.front != Front::wave_end && ctx->pairs_tier && p.split && p.windows && !p.dense_w && !dev.vlen &&
+        size_pairs(ctx, f1.pplan, batch_len))
+        p.front = Front::pairs;
+    if (tiered && p.front == Front::none) p.front = Front::bitpar;
+    p.t1_exact = tiered && p.split && p.front != Front::wave_end;
+    // Carried passes: tier 1 of a dual known-class config lists a read when ONE of its passes is open; the pass it settled goes
+    // along (two state bits on the list entry + the pass's winning survivor in d_carry[read]) and the pairs mode only looks for
+    // the other pass's barcodes — about half of its sweeps for C4.  Only when the pairs mode in its known form is what reads
+    // tier 1's list (nothing else understands the state bits), reads fit 30 bits and min_delta = 0 (a lone carried winner
+    // then IS the pass's result).
+    // (the known-trim / known-alignment forms and the plain known-score form of a dual config without trimming)
+    if (tiered && (p.front == Front::wave_end || p.front == Front::wave) && dev.is_dual && dev.min_delta == 0.0 && !ctx->tune.no_carry &&
+        n_reads < (1LL << 30) && o.pass_start == nullptr && o.pass_end == nullptr && o.pass_raw == nullptr && o.pass_bc == nullptr &&
+        o.pass_score == nullptr && o.pass_delta == nullptr) {
+        BdxWavePlan &pp = p.front == Front::wave_end ? (p.aln ? f0.pplan_a : f0.pplan_k) : f0.pplan;
+        p.carry = size_pairs(ctx, pp, tier_len) && pp.groups <= 1 && pp.pairs_kb <= 4 && !pp.split;
+    }
+    if (tiered) {
+        // tier 0 walks the list: scattered reads -> slot staging
+        // (tier 0 sees a fraction of the batch — 10..25 % in the bench configs: its tile size is planned for a sixteenth of
+        // the batch, so that the list of a small batch still spreads over the device — C5, 400 k reads: tiles of 16 instead
+        // of 128 reads, 0.42 -> 0.38 ms; batches of millions of reads keep their tiles)
+        long long n_list_est = n_reads / (ctx->tune.tier0_div > 0 ? ctx->tune.tier0_div : 16);
+        if (n_list_est < 1) n_list_est = 1;
+        if (!size_bitpar(ctx, 0, tier_len, n_list_est, true)) return fail(ctx, BDX_E_DEVICE, "internal: tier 0 cannot be planned in list mode");
+    }
+    // Pairs mode of the wave kernel between tier 1 and the general kernel: the listed reads are gathered into slots and
+    // filtered at the full budgets by the two-intact-pieces lemma.  Known-score configs: it answers them (what it cannot
+    // answer goes on to the general kernel in list mode); split configs: it is tier 0's filter (masks + windows of the
+    // listed reads for the exact kernel).  Known-end class: the pairs mode answers the listed reads itself (verdict +
+    // trimmed keep range); what it cannot answer goes on to the split path in list mode.
+    // Same-diagonal pairs mode as the ONLY filter of a split config without tiers (weighted costs whose full budget is beyond
+    // every seeded variant — the reference's demo2 options): every read of the batch is laid out in slots and scanned;
+    // masks + windows of all reads go to the exact kernel's dense launch.
+    BdxWavePlan &pk = p.aln ? f0.pplan_a : f0.pplan_k;
+    p.wmid = &f0.pplan;
+    if (tiered && (kend_ok || p.aln) && size_pairs(ctx, pk, tier_len)) {
+        p.middle = Middle::end;
+        p.wmid = &pk;
+    } else if (tiered && (!p.split || p.windows) && !p.dense_w && size_pairs(ctx, tier_len)) {
+        p.middle = p.split ? Middle::split : Middle::list;
+    } else if (!tiered && p.split && p.windows && !p.dense_w && !wsplit0 && p.front != Front::wave_end && !dev.vlen && f0.pplan.enabled &&
+               f0.pplan.pairs_kb >= 8 && f0.pplan.split && size_pairs(ctx, batch_len)) {
+        p.middle = Middle::all;
+    }
+    p.full = (p.middle == Middle::split || p.middle == Middle::all) ? Full::none : wsplit0 ? Full::wave_split : Full::bitpar;
+    p.exact = !p.split ? Exact::known : p.front != Front::none ? Exact::split_list : Exact::split;
+    return BDX_OK;
+}
+
+// Buffers of the plan's hand-overs, the test switch's fills, this call's half of the scratch block and the per-launch
+// fields of the plans.
+static int reserve(bdx_ctx *ctx, const CallPlan &p, long long n_reads) {
+    const bool tiered = p.tier_len > 0;
+    const size_t list_bytes = (size_t)n_reads * 4 + 64;
+    for (int k = 0; k < p.npass; ++k) {
+        HIP_TRY(ctx, ctx->d_cand[k].ensure((size_t)n_reads * ctx->dev.pass[k].cand_words * 4 + 64));
+        if (p.windows) {
+            size_t per_read = (size_t)BDX_WCAP * 3;
+            if (p.dense_w && (size_t)ctx->dev.pass[k].n_barcodes > per_read) per_read = (size_t)ctx->dev.pass[k].n_barcodes;
+            HIP_TRY(ctx, ctx->d_wins[k].ensure((size_t)n_reads * per_read * 4 + 64));
+            HIP_TRY(ctx, ctx->d_wcnt[k].ensure((size_t)n_reads + 64));
+        }
+    }
+    if (!p.split) HIP_TRY(ctx, ctx->d_exc.ensure(list_bytes));
+    if (tiered) HIP_TRY(ctx, ctx->d_tier.ensure(list_bytes));
+    if ((!tiered && p.front != Front::none) || p.middle == Middle::end || p.middle == Middle::list) HIP_TRY(ctx, ctx->d_wlist.ensure(list_bytes));
+    for (BdxFilterSet &f : ctx->fs)
+        f.wplan.d_carry = f.pplan.d_carry = f.wplan_k.d_carry = f.wplan_a.d_carry = f.pplan_k.d_carry = f.pplan_a.d_carry = nullptr;
+    if (p.carry) {
+        HIP_TRY(ctx, ctx->d_carry.ensure(list_bytes));
+        p.wfront->d_carry = p.wmid->d_carry = (uint32_t *)ctx->d_carry.p;
+    }
+    if (ctx->tune.poison) {
+        // test switch: whatever a consumer reads without a producer having written it is garbage on EVERY run
+        // every hand-over buffer is filled with 0xA5; between each producer and its consumer a checker kernel
+        // (bdx_poison_check_kernel) then looks at exactly the elements the consumer is going to read — an element that
+        // still holds the fill was never written: counted (bdx_rejected_windows) and made harmless
+        DevBuf *bufs[] = {&ctx->d_cand[0], &ctx->d_cand[1], &ctx->d_wins[0], &ctx->d_wins[1], &ctx->d_wcnt[0], &ctx->d_wcnt[1],
+                          &ctx->d_exc, &ctx->d_tier, &ctx->d_wlist, &ctx->d_carry};
+        for (DevBuf *b : bufs)
+            if (b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0xA5, b->cap, ctx->stream));
+    }
+    // scratch words (d_maxlen, 1 KiB): +64 tile queue, +128 hand-over count (+132.. tuning statistics),
+    // +192 tier-0 list length, +256 tile queue of the second launch, +320 the pairs mode's list length; one memset clears them all
+    // (the block's two halves alternate between calls: this call's last launch clears the other half for the next call,
+    // which then needs no memset of its own — 5 us of fill + a launch gap per call, 1 % of a 10 M-read C2 step)
+    const int spar = ctx->scratch_par & 1;
+    char *scratch = (char *)ctx->d_maxlen.p + 512 * spar;
+    if (!ctx->scratch_zeroed && !ctx->scratch_clean[spar]) HIP_TRY(ctx, hipMemsetAsync(scratch + 64, 0, 4 * BDX_SCRATCH_WORDS, ctx->stream));
+    ctx->scratch_zeroed = false;
+    ctx->scratch_clean[spar] = false;  // (a call that fails half-way leaves it that way: the next one clears it itself)
+    for (int set = tiered ? 1 : 0; set >= 0; --set) {
+        BdxBitparPlan &b = ctx->fs[set].bplan;
+        b.d_tile_counter = (int *)(scratch + (set ? 256 : 64));
+        b.dense_w = set ? 0 : p.dense_w;
+        b.grid_override = ctx->tune.grid;
+        b.dbg = ctx->tune.debug;
+    }
+    return BDX_OK;
+}
+
+static int enqueue(bdx_ctx *ctx, const CallPlan &p, const uint8_t *seq, const long long *off, long long n_reads, const BdxDevOut &o,
+                   const BdxDevStats *stp) {
+    const BdxFilterSet &f0 = ctx->fs[0], &f1 = ctx->fs[1];
+    const bool tiered = p.tier_len > 0, two = p.npass > 1;
+    const int spar = ctx->scratch_par & 1;
+    char *scratch = (char *)ctx->d_maxlen.p + 512 * spar;
+    uint32_t *zero_next = (uint32_t *)((char *)ctx->d_maxlen.p + 512 * (1 - spar) + 64);
+    uint32_t *c0 = (uint32_t *)ctx->d_cand[0].p, *c1 = two ? (uint32_t *)ctx->d_cand[1].p : c0;
+    uint32_t *w0 = p.windows ? (uint32_t *)ctx->d_wins[0].p : nullptr, *w1 = p.windows && two ? (uint32_t *)ctx->d_wins[1].p : w0;
+    uint8_t *n0 = p.windows ? (uint8_t *)ctx->d_wcnt[0].p : nullptr, *n1 = p.windows && two ? (uint8_t *)ctx->d_wcnt[1].p : n0;
+    uint32_t *exc_list = p.split ? nullptr : (uint32_t *)ctx->d_exc.p;
+    unsigned int *exc_count = (unsigned int *)(scratch + 128);
+    // what the front stage cannot settle: tier 1 lists into d_tier, a plain front stage into d_wlist; the pairs mode into d_wlist
+    uint32_t *front_list = (uint32_t *)(tiered ? ctx->d_tier.p : ctx->d_wlist.p), *mid_list = (uint32_t *)ctx->d_wlist.p;
+    unsigned int *front_count = (unsigned int *)(scratch + 192), *mid_count = (unsigned int *)(scratch + 320);
+    const double *slo = f1.bplan.tier_slo;
+    BdxWaveSplit wsp{};
+    for (int k = 0; k < 2; ++k) {
+        wsp.cw[k] = k < p.npass ? ctx->dev.pass[k].cand_words : 0;
+        wsp.cand_out[k] = k ? c1 : c0;
+        wsp.wins_out[k] = k ? w1 : w0;
+        wsp.wcnt_out[k] = k ? n1 : n0;
+        wsp.short_lb[k] = p.short_lb[k];
+    }
+    // diagonal-band DP of the exact kernel (sg_core_band): clean class, every barcode of the config with the same
+    // number of rows and of the pass with the same budget, column windows handed over by tracked sweeps
+    const auto band_cfg = [&](const BdxFilterSet &f) {
+        BdxDevCfg dv = ctx->dev;
+        dv.dense_w = (&f == &ctx->fs[0]) && p.dense_w;
+        for (int k = 0; k < p.npass; ++k) {
+            const int kb = f.bplan.kb_uniform[k];
+            // (rolling band, barcodes beyond 32 rows: any uniform budget; the first end column is rebuilt from the hand-over row
+            // when every barcode has the same length — band_lb is made of max_m)
+            const bool on = ctx->plan.band_roll ? (p.windows && ctx->plan.same_len && kb >= 0)
+                                                : (p.windows && ctx->plan.clean && ctx->plan.uniform_len > 0 && !ctx->tune.no_band &&
+                                                   ctx->dev.algorithm == BDX_ALG_SEMIGLOBAL && kb >= 0 && kb <= 4);
+            dv.band_m = ctx->plan.uniform_len;
+            dv.band_kb[k] = on ? kb : -1;
+            if (on && !ctx->plan.band_roll) ctx->band_launches += 1;
+            dv.band_lb[k] = p.short_lb[k] ? ctx->dev.max_m + kb : 2 * (ctx->dev.max_m + kb) + 1;
+        }
+        return dv;
+    };
+    // test switch BDX_POISON: between a producer and its consumer, every element the consumer will read must have
+    // been written (bdx_poison_check_kernel); `with_windows`: also the window hand-over of both passes for these reads
+    const auto poison_check = [&](const uint32_t *list, const unsigned int *count, bool check_list, bool with_windows, bool packed = false) -> hipError_t {
+        if (!ctx->tune.poison) return hipSuccess;
+        unsigned int *dbg = (unsigned int *)ctx->d_dbg.p;
+        uint32_t *l = (uint32_t *)list;
+        if (!with_windows || !p.windows)
+            return l ? bdx_launch_poison_check(l, count, n_reads, nullptr, nullptr, nullptr, 0, 0, (check_list ? 1 : 0) | (packed ? 2 : 0), dbg, ctx->stream) : hipSuccess;
+        for (int k = 0; k < p.npass; ++k) {
+            hipError_t e = bdx_launch_poison_check(l, count, n_reads, k ? w1 : w0, k ? n1 : n0, k ? c1 : c0, ctx->dev.pass[k].cand_words,
+                                                   ctx->dev.pass[k].n_barcodes, (check_list && k == 0) ? 1 : 0, dbg, ctx->stream);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    };
+    // one launcher per kernel family; `filter`: the split form (masks + windows into wsp, no verdicts, no list)
+    const auto counted = [](hipError_t e, int64_t &launches) { if (e == hipSuccess) launches += 1; return e; };
+    const int he = ctx->plan.hist_entries, dbg = ctx->tune.debug;
+    const auto bitpar = [&](const BdxFilterSet &f, const BdxTierArgs *t) {
+        return bdx_launch_bitpar(ctx->dev, ctx->plan, f.bplan, f.splan, seq, off, n_reads, o, ctx->counts, c0, c1, ctx->stream, w0, w1, n0, n1,
+                                 p.split ? 1 : 0, exc_list, exc_count, t);
+    };
+    const auto wave = [&](const BdxWavePlan &wp, int tier1, bool filter) {
+        return counted(bdx_launch_wave(ctx->dev, wp, he, seq, off, n_reads, o, filter ? nullptr : ctx->counts, (int *)(scratch + 256), tier1,
+                                       tier1 ? slo[0] : 0.0, filter ? nullptr : front_list, filter ? nullptr : front_count, ctx->stream, dbg,
+                                       filter ? &wsp : nullptr, tier1 ? slo[1] : 0.0),
+                       ctx->wave_launches);
+    };
+    const auto wave_win = [&](const BdxWavePlan &wp, int tier1) {
+        return counted(bdx_launch_wave_win(ctx->dev, wp, he, seq, off, n_reads, o, ctx->counts, tier1, tier1 ? slo[0] : 0.0, front_list,
+                                           front_count, ctx->stream, dbg),
+                       ctx->wave_launches);
+    };
+    const auto wave_end = [&](const BdxWavePlan &wp, int tier1) {
+        return counted(bdx_launch_wave_end(ctx->dev, wp, he, seq, off, n_reads, o, ctx->counts, tier1, tier1 ? slo[0] : 0.0, front_list,
+                                           front_count, ctx->stream, dbg, tier1 ? slo[1] : 0.0, p.aln ? stp : nullptr),
+                       ctx->wave_launches);
+    };
+    const auto pairs = [&](const BdxWavePlan &wp, const uint32_t *in_list, const unsigned int *in_count, bool filter, const BdxDevStats *st) {
+        return counted(bdx_launch_pairs(ctx->dev, wp, he, seq, off, n_reads, in_list, in_count, o, filter ? nullptr : ctx->counts,
+                                        filter ? nullptr : mid_list, filter ? nullptr : mid_count, ctx->stream, dbg >> 8, filter ? &wsp : nullptr, st),
+                       ctx->pair_launches);
+    };
+    const auto generic = [&](const BdxDevCfg &dv, const uint32_t *list, const unsigned int *count, const BdxTierArgs *t, const double *t_slo,
+                             uint32_t *zero) {
+        return bdx_launch_generic(dv, ctx->plan, seq, off, n_reads, o, ctx->counts, c0, two ? c1 : nullptr, ctx->stream, w0, two ? w1 : nullptr, n0,
+                                  two ? n1 : nullptr, list, count, stp, t, t_slo, zero);
+    };
+
+    BdxTierArgs t1{1, (uint32_t *)ctx->d_tier.p, front_count, nullptr, nullptr};
+    BdxTierArgs t0{0, nullptr, nullptr, nullptr, nullptr};
+    // 1. front stage
+    switch (p.front) {
+        case Front::none: break;
+        case Front::bitpar: HIP_TRY(ctx, bitpar(f1, &t1)); break;
+        case Front::wave: HIP_TRY(ctx, wave(*p.wfront, tiered, false)); break;
+        case Front::wave_win: HIP_TRY(ctx, wave_win(*p.wfront, tiered)); break;
+        case Front::wave_split: HIP_TRY(ctx, wave(f1.wplan, 0, true)); break;  // (the exact kernel settles and lists)
+        case Front::wave_end: HIP_TRY(ctx, wave_end(*p.wfront, tiered)); break;  // verdicts + trimmed keep range of what it settles
+        case Front::pairs: HIP_TRY(ctx, pairs(f1.pplan, nullptr, nullptr, true, nullptr)); break;
+    }
+    // 2. tier 1's exact launch: it answers what tier 1 settles and lists the rest (known-score / known-end configs: the filter kernel did)
+    if (p.t1_exact) {
+        HIP_TRY(ctx, poison_check(nullptr, nullptr, false, true));
+        HIP_TRY(ctx, generic(band_cfg(f1), nullptr, nullptr, &t1, f1.bplan.tier_slo, nullptr));
+    }
+    if (p.front != Front::none) {  // tier 0 / the plain front stage's filter set walks the list
+        t0.in_list = front_list;
+        t0.in_count = front_count;
+        HIP_TRY(ctx, poison_check(t0.in_list, t0.in_count, true, false, p.carry));
+    }
+    // 3. middle stage
+    switch (p.middle) {
+        case Middle::none: break;
+        case Middle::end: HIP_TRY(ctx, pairs(*p.wmid, t0.in_list, t0.in_count, false, p.aln ? stp : nullptr)); break;
+        case Middle::list: HIP_TRY(ctx, pairs(*p.wmid, t0.in_list, t0.in_count, false, nullptr)); break;
+        case Middle::split: HIP_TRY(ctx, pairs(*p.wmid, t0.in_list, t0.in_count, true, nullptr)); break;
+        case Middle::all: HIP_TRY(ctx, pairs(*p.wmid, nullptr, nullptr, true, nullptr)); break;
+    }
+    if (p.middle == Middle::end || p.middle == Middle::list) {  // what the pairs mode cannot answer goes on in list mode
+        t0.in_list = mid_list;
+        t0.in_count = mid_count;
+        HIP_TRY(ctx, poison_check(mid_list, mid_count, true, false));
+    }
+    // 4. full-budget filter
+    switch (p.full) {
+        case Full::none: break;  // (the pairs mode already wrote the masks and windows)
+        case Full::wave_split: HIP_TRY(ctx, wave(f0.wplan, 0, true)); break;
+        case Full::bitpar: HIP_TRY(ctx, bitpar(f0, p.front != Front::none ? &t0 : nullptr)); break;
+    }
+    // 5. exact stage (its last launch clears the other scratch half for the next call)
+    switch (p.exact) {
+        case Exact::known:
+            HIP_TRY(ctx, poison_check(exc_list, exc_count, true, false));
+            HIP_TRY(ctx, generic(ctx->dev, exc_list, exc_count, nullptr, nullptr, zero_next));
+            break;
+        case Exact::split:
+            HIP_TRY(ctx, poison_check(nullptr, nullptr, false, true));
+            HIP_TRY(ctx, generic(band_cfg(f0), nullptr, nullptr, nullptr, nullptr, zero_next));
+            break;
+        case Exact::split_list:  // (tiered: list mode over the reads tier 1 handed on)
+            HIP_TRY(ctx, poison_check(t0.in_list, t0.in_count, false, true));
+            HIP_TRY(ctx, generic(band_cfg(f0), t0.in_list, t0.in_count, nullptr, nullptr, zero_next));
+            break;
+    }
+    // (the call's last launch is enqueued: the other half will hold zeros when the next call's kernels start)
+    ctx->scratch_clean[1 - spar] = true;
+    ctx->scratch_par = 1 - spar;
+#ifdef BDX_TUNING
+    if (ctx->tune.debug & 128) {  // tuning statistics of the fused kernel (see bdx_bitpar.hip)
+            unsigned int st[4] = {0, 0, 0, 0}, tl = 0;
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(st, exc_count, sizeof(st), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(&tl, scratch + 192, sizeof(tl), hipMemcpyDeviceToHost));
+            fprintf(stderr, "[bdx] handed over %u reads; %u windowed sweeps, %u columns, %u tiles with a fallback read; tier 0 list %u (of %lld reads)\n",
+                    st[0], st[1], st[2], st[3], tl, (long long)n_reads);
+    }
+#endif
+    return BDX_OK;
+}
+
+// ctx->path of a filtered call: its stages, front first
+static std::string call_path(const bdx_ctx *ctx, const CallPlan &p) {
+    const BdxSeedPlan &sp = ctx->fs[0].splan;
+    std::string s = sp.enabled ? (sp.diag ? "qgram2+bitpar+verify" : "qgram+bitpar+verify") : "bitpar+verify";
+    if (p.full == Full::wave_split) s = "wave+verify";
+    switch (p.middle) {
+        case Middle::none: break;
+        case Middle::end: s = (p.aln ? "pairs(aln) > " : "pairs(end) > ") + s; break;
+        case Middle::list: s = "pairs > " + s; break;
+        case Middle::split: s = "pairs+verify"; break;
+        case Middle::all: s = "pairs(diag)+verify"; break;
+    }
+    static const char *const front[] = {"", "qgram+bitpar", "wave", "wave(win)", "wave", "wave(end)", "pairs(diag)"};
+    if (p.front == Front::none) return s;
+    return std::string(p.tier_len > 0 ? "tier1:" : "") + (p.front == Front::wave_end && p.aln ? "wave(aln)" : front[(int)p.front]) + " > " + s;
+}
+
 int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int64_t *d_seq_off, int64_t n_reads,
                             const bdx_outputs_t *d_out) {
     if (!ctx) return BDX_E_INVALID;
@@ -2376,17 +2771,8 @@ int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int6
     if (n_reads == 0) return BDX_OK;
     if (!d_seq_bytes || !d_seq_off || !d_out) return fail(ctx, BDX_E_INVALID, "NULL device pointer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BdxDevOut o;
-    o.bc1 = d_out->bc1;
-    o.bc2 = d_out->bc2;
-    o.keep_start = d_out->keep_start;
-    o.keep_end = d_out->keep_end;
-    o.pass_start = d_out->pass_start;
-    o.pass_end = d_out->pass_end;
-    o.pass_raw = d_out->pass_raw;
-    o.pass_score = d_out->pass_score;
-    o.pass_bc = d_out->pass_bc;
-    o.pass_delta = d_out->pass_delta;
+    const BdxDevOut o{d_out->bc1,      d_out->bc2,      d_out->keep_start, d_out->keep_end,   d_out->pass_start,
+                      d_out->pass_end, d_out->pass_raw, d_out->pass_bc,    d_out->pass_score, d_out->pass_delta};
     BdxDevStats st{};
     const BdxDevStats *stp = nullptr;
     int measured_len = -1;
@@ -2421,7 +2807,7 @@ int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int6
     bool filtered = false;
     int tier_len = 0;  // > 0: tiered budgets apply to this batch (the read length both tiers were planned for)
     int batch_len = 0;  // the read length the filtered launches were planned for
-    if (ctx->F().bplan.enabled) {
+    if (ctx->fs[0].bplan.enabled) {
         int len = ctx->virt_maxlen > 0 ? ctx->virt_maxlen : ctx->user_len_hint;
         if (len <= 0 && measured_len >= 0) len = measured_len > 0 ? measured_len : 1;
         if (len <= 0) {  // measure the batch: one tiny kernel + a 4-byte copy
@@ -2432,372 +2818,19 @@ int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int6
             len = host_len;
         }
         batch_len = len;
-        filtered = size_bitpar(ctx, len, n_reads);
-        if (filtered && ctx->tiered) {  // both tiers must be plannable for this batch, else the full budget alone
-            ctx->cur = 1;
-            const bool ok1 = size_bitpar(ctx, len, n_reads);
-            ctx->cur = 0;
-            tier_len = ok1 ? len : 0;
-        }
+        filtered = size_bitpar(ctx, 0, len, n_reads);
+        // both tiers must be plannable for this batch, else the full budget alone
+        if (filtered && ctx->tiered && size_bitpar(ctx, 1, len, n_reads)) tier_len = len;
     }
     if (filtered) {
-        // The fused kernel filters; the exact DP runs at full width in the generic kernel:
-        //  * split (trimming / summary / weighted costs / N-scoring / Hamming / exact): every read's
-        //    candidate mask (+ column windows) goes through HBM, the generic kernel gives every verdict;
-        //  * known-score configs: the fused kernel also gives the verdict of (nearly) every read by
-        //    replaying the reducer; the few it cannot settle are listed and evaluated by the generic
-        //    kernel in list mode;
-        //  * tiered budgets (known-score configs whose full budget is too large for selective single seeds):
-        //    tier 1 — capped budgets, single seeds — runs over the whole batch and settles every read whose
-        //    verdict cannot depend on a barcode beyond the cap; tier 0 — the full budget — then runs in list
-        //    mode over the rest.
-        const int npass = ctx->dev.is_dual ? 2 : 1;
-        bool split = false;
-        for (int k = 0; k < npass; ++k) split |= !ctx->F().bplan.known_ok[k];
-        // (:exact returns the occurrence's start and end whatever the output policy: a caller that wants them gets the launch in
-        // its split form — known-alignment class first, exact kernel for what that lists)
-        if (ctx->dev.algorithm == BDX_ALG_EXACT && (o.pass_start != nullptr || o.pass_end != nullptr)) split = true;
-        const bool tiered = tier_len > 0;
-        if (n_reads > 0xFFFFFFF0LL) return fail(ctx, BDX_E_INVALID, "more than 2^32 reads in one batch");
-        uint32_t *c0 = nullptr, *c1 = nullptr, *w0 = nullptr, *w1 = nullptr;
-        uint8_t *n0 = nullptr, *n1 = nullptr;
-        const bool windows = split && !ctx->tune.no_windows;
-        // dense window table of the plain-sweep kernel (few barcodes, many genuine candidates per read; columns fit 16 bits)
-        const bool dense_w = windows && ctx->fs[0].bplan.dense_d && !ctx->fs[0].splan.enabled && batch_len <= 60000 && !ctx->tune.no_dense;
-        for (int k = 0; k < npass; ++k) {
-            HIP_TRY(ctx, ctx->d_cand[k].ensure((size_t)n_reads * ctx->dev.pass[k].cand_words * 4 + 64));
-            if (windows) {
-                size_t per_read = (size_t)BDX_WCAP * 3;
-                if (dense_w && (size_t)ctx->dev.pass[k].n_barcodes > per_read) per_read = (size_t)ctx->dev.pass[k].n_barcodes;
-                HIP_TRY(ctx, ctx->d_wins[k].ensure((size_t)n_reads * per_read * 4 + 64));
-                HIP_TRY(ctx, ctx->d_wcnt[k].ensure((size_t)n_reads + 64));
-            }
-        }
-        c0 = (uint32_t *)ctx->d_cand[0].p;
-        c1 = npass > 1 ? (uint32_t *)ctx->d_cand[1].p : c0;
-        if (windows) {
-            w0 = (uint32_t *)ctx->d_wins[0].p;
-            n0 = (uint8_t *)ctx->d_wcnt[0].p;
-            w1 = npass > 1 ? (uint32_t *)ctx->d_wins[1].p : w0;
-            n1 = npass > 1 ? (uint8_t *)ctx->d_wcnt[1].p : n0;
-        }
-        // scratch words (d_maxlen, 1 KiB): +64 tile queue, +128 hand-over count (+132.. tuning statistics),
-        // +192 tier-0 list length, +256 tile queue of the second launch; one memset clears them all
-        // (the block's two halves alternate between calls: this call's last launch clears the other half for the next call,
-        // which then needs no memset of its own — 5 us of fill + a launch gap per call, 1 % of a 10 M-read C2 step)
-        const int spar = ctx->scratch_par & 1;
-        char *scratch = (char *)ctx->d_maxlen.p + 512 * spar;
-        uint32_t *zero_next = (uint32_t *)((char *)ctx->d_maxlen.p + 512 * (1 - spar) + 64);
-        uint32_t *exc_list = nullptr;
-        unsigned int *exc_count = (unsigned int *)(scratch + 128);
-        if (!split) {
-            HIP_TRY(ctx, ctx->d_exc.ensure((size_t)n_reads * 4 + 64));
-            exc_list = (uint32_t *)ctx->d_exc.p;
-        }
-        if (ctx->tune.poison) {
-            // test switch: whatever a consumer reads without a producer having written it is garbage on EVERY run
-            if (tiered) HIP_TRY(ctx, ctx->d_tier.ensure((size_t)n_reads * 4 + 64));
-            if (ctx->fs[0].wplan.enabled) HIP_TRY(ctx, ctx->d_wlist.ensure((size_t)n_reads * 4 + 64));
-            // every hand-over buffer is filled with 0xA5; between each producer and its consumer a checker kernel
-            // (bdx_poison_check_kernel) then looks at exactly the elements the consumer is going to read — an element that
-            // still holds the fill was never written: counted (bdx_rejected_windows) and made harmless
-            DevBuf *bufs[] = {&ctx->d_cand[0], &ctx->d_cand[1], &ctx->d_wins[0], &ctx->d_wins[1], &ctx->d_wcnt[0], &ctx->d_wcnt[1],
-                              &ctx->d_exc, &ctx->d_tier, &ctx->d_wlist, &ctx->d_carry};
-            for (DevBuf *b : bufs)
-                if (b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0xA5, b->cap, ctx->stream));
-        }
-        if (!ctx->scratch_zeroed && !ctx->scratch_clean[spar]) HIP_TRY(ctx, hipMemsetAsync(scratch + 64, 0, 4 * BDX_SCRATCH_WORDS, ctx->stream));
-        ctx->scratch_zeroed = false;
-        ctx->scratch_clean[spar] = false;  // (a call that fails half-way leaves it that way: the next one clears it itself)
-        // restricted runs of passes that only report score (+ end) through the clean-class DP start m + kb columns before
-        // the first end column (orc_selftest_clean_short_lookback); everything else keeps 2 (m + kb) + 1
-        int short_lb[2] = {0, 0};
-        for (int k = 0; k < npass; ++k) {
-            const int ts = ctx->dev.pass[k].trim_side;
-            short_lb[k] = (ctx->plan.clean || ctx->plan.band_roll) && ctx->dev.algorithm == BDX_ALG_SEMIGLOBAL && !ctx->dev.need_traceback &&
-                          (ts == 0 || (ts == 5 && o.pass_start == nullptr));
-        }
-        for (BdxFilterSet &f : ctx->fs) {
-            f.bplan.short_lb[0] = short_lb[0];
-            f.bplan.short_lb[1] = short_lb[1];
-            f.bplan.n_cu = ctx->n_cu;
-        }
-        // diagonal-band DP of the exact kernel (sg_core_band): clean class, every barcode of the config with the same
-        // number of rows and of the pass with the same budget, column windows handed over by tracked sweeps
-        const auto band_cfg = [&](const BdxFilterSet &f) {
-            BdxDevCfg dv = ctx->dev;
-            dv.dense_w = (&f == &ctx->fs[0]) && dense_w;
-            for (int k = 0; k < npass; ++k) {
-                const int kb = f.bplan.kb_uniform[k];
-                // (rolling band, barcodes beyond 32 rows: any uniform budget; the first end column is rebuilt from the hand-over row
-                // when every barcode has the same length — band_lb is made of max_m)
-                const bool on = ctx->plan.band_roll ? (windows && ctx->plan.same_len && kb >= 0)
-                                                    : (windows && ctx->plan.clean && ctx->plan.uniform_len > 0 && !ctx->tune.no_band &&
-                                                       ctx->dev.algorithm == BDX_ALG_SEMIGLOBAL && kb >= 0 && kb <= 4);
-                dv.band_m = ctx->plan.uniform_len;
-                dv.band_kb[k] = on ? kb : -1;
-                if (on && !ctx->plan.band_roll) ctx->band_launches += 1;
-                dv.band_lb[k] = short_lb[k] ? ctx->dev.max_m + kb : 2 * (ctx->dev.max_m + kb) + 1;
-            }
-            return dv;
-        };
-        // test switch BDX_POISON: between a producer and its consumer, every element the consumer will read must have
-        // been written (bdx_poison_check_kernel); `with_windows`: also the window hand-over of both passes for these reads
-        const auto poison_check = [&](uint32_t *list, const unsigned int *count, bool check_list, bool with_windows, bool packed = false) -> hipError_t {
-            if (!ctx->tune.poison) return hipSuccess;
-            unsigned int *dbg = (unsigned int *)ctx->d_dbg.p;
-            if (!with_windows || !windows)
-                return list ? bdx_launch_poison_check(list, count, n_reads, nullptr, nullptr, nullptr, 0, 0, (check_list ? 1 : 0) | (packed ? 2 : 0), dbg, ctx->stream) : hipSuccess;
-            for (int k = 0; k < npass; ++k) {
-                hipError_t e = bdx_launch_poison_check(list, count, n_reads, k ? w1 : w0, k ? n1 : n0, k ? c1 : c0, ctx->dev.pass[k].cand_words,
-                                                       ctx->dev.pass[k].n_barcodes, (check_list && k == 0) ? 1 : 0, dbg, ctx->stream);
-                if (e != hipSuccess) return e;
-            }
-            return hipSuccess;
-        };
-        BdxTierArgs t0{0, nullptr, nullptr, nullptr, nullptr};
-        // Wave-autonomous kernel (bdx_wave.hip) in front of the general one: it answers the reads of the known-score
-        // class and lists the rest — as tier 1 of a tiered config, or (plain configs) ahead of the same filter set
-        // in list mode.  The list-mode plan is made first: if it cannot be made, the general kernel runs alone.
-        bool wave1 = false, wave0 = false;
-        if (!split && !ctx->dev.vlen) {
-            // (window mode first: reads much longer than their column window — only the windows are fetched)
-            if (tiered)
-                wave1 = size_wave_win(ctx, ctx->fs[1].wplan, batch_len, n_reads) || size_wave(ctx, 1, batch_len, n_reads);
-            else if (size_wave_win(ctx, ctx->fs[0].wplan, batch_len, n_reads) || size_wave(ctx, 0, batch_len, n_reads))
-                wave0 = size_bitpar(ctx, batch_len, n_reads, true);
-            if (!tiered && !wave0) (void)size_bitpar(ctx, batch_len, n_reads);  // (restore the dense plan)
-        }
-        // Known-end class (trim_side = 5, single pass, no start positions or statistics wanted): the same kernel in its
-        // known-end form answers the reads it can settle, trimmed keep range included; the listed rest goes through the
-        // split path (filter in list mode -> exact kernel in list mode).
-        bool wave1k = false, wave0k = false;
-        bool trim3 = false;  // (a trim_side = 3 pass of the known-trim class knows its start only)
-        for (int k = 0; k < npass; ++k) trim3 |= ctx->dev.pass[k].trim_side == 3;
-        const bool kend_ok = split && windows && !ctx->dev.vlen && !dense_w && o.pass_start == nullptr && stp == nullptr && !(trim3 && o.pass_end != nullptr);
-        // known-alignment class: the caller wants positions the known-trim class does not know, or the statistics tables
-        const bool aln_ok = split && windows && !ctx->dev.vlen && !dense_w && !kend_ok && ctx->fs[tiered ? 1 : 0].wplan_a.enabled;
-        BdxWavePlan &wk1 = aln_ok ? ctx->fs[1].wplan_a : ctx->fs[1].wplan_k, &wk0 = aln_ok ? ctx->fs[0].wplan_a : ctx->fs[0].wplan_k;
-        if (kend_ok || aln_ok) {
-            if (tiered)
-                wave1k = size_wave(ctx, wk1, batch_len, n_reads);
-            else if (size_wave(ctx, wk0, batch_len, n_reads)) {
-                wave0k = size_bitpar(ctx, batch_len, n_reads, true);
-                if (!wave0k) (void)size_bitpar(ctx, batch_len, n_reads);  // (restore the dense plan)
-            }
-        }
-        // split configs (trimming, summary, weighted costs): the wave kernel as the FILTER of a dense launch — candidate
-        // masks and column windows in the formats of the general kernel's split mode, every verdict from the exact
-        // kernel as before.  Tiered: tier 1 (all reads); plain: the only filter launch.
-        bool wsplit1 = false, wsplit0 = false, pairs_t1 = false;
-        BdxWaveSplit wsp{};
-        for (int k = 0; k < 2; ++k) {
-            wsp.cw[k] = k < npass ? ctx->dev.pass[k].cand_words : 0;
-            wsp.cand_out[k] = k ? c1 : c0;
-            wsp.wins_out[k] = k ? w1 : w0;
-            wsp.wcnt_out[k] = k ? n1 : n0;
-            wsp.short_lb[k] = short_lb[k];
-        }
-        const BdxWaveSplit &wsp_all = wsp;
-        if (split && windows && !ctx->dev.vlen && !wave1k && !wave0k) {
-            if (tiered)
-                wsplit1 = ctx->fs[1].wplan.split && size_wave(ctx, 1, batch_len, n_reads);
-            else
-                wsplit0 = ctx->fs[0].wplan.split && !dense_w && size_wave(ctx, 0, batch_len, n_reads);
-        }
-        if (wave0) {
-            HIP_TRY(ctx, ctx->d_wlist.ensure((size_t)n_reads * 4 + 64));
-            if (ctx->fs[0].wplan.winm)
-                HIP_TRY(ctx, bdx_launch_wave_win(ctx->dev, ctx->fs[0].wplan, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
-                                                 ctx->counts, 0, 0.0, (uint32_t *)ctx->d_wlist.p, (unsigned int *)(scratch + 192), ctx->stream, ctx->tune.debug));
-            else
-            HIP_TRY(ctx, bdx_launch_wave(ctx->dev, ctx->fs[0].wplan, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
-                                         ctx->counts, (int *)(scratch + 256), 0, 0.0, (uint32_t *)ctx->d_wlist.p, (unsigned int *)(scratch + 192),
-                                         ctx->stream, ctx->tune.debug));
-            ctx->wave_launches += 1;
-            t0.in_list = (const uint32_t *)ctx->d_wlist.p;
-            t0.in_count = (const unsigned int *)(scratch + 192);
-        }
-        if (wave0k) {
-            HIP_TRY(ctx, ctx->d_wlist.ensure((size_t)n_reads * 4 + 64));
-            HIP_TRY(ctx, bdx_launch_wave_end(ctx->dev, wk0, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
-                                             ctx->counts, 0, 0.0, (uint32_t *)ctx->d_wlist.p, (unsigned int *)(scratch + 192), ctx->stream, ctx->tune.debug, 0.0,
-                                             aln_ok ? stp : nullptr));
-            ctx->wave_launches += 1;
-            t0.in_list = (const uint32_t *)ctx->d_wlist.p;
-            t0.in_count = (const unsigned int *)(scratch + 192);
-        }
-        // Carried passes: tier 1 of a dual known-class config lists a read when ONE of its passes is open; the pass it settled goes
-        // along (two state bits on the list entry + the pass's winning survivor in d_carry[read]) and the pairs mode only looks for
-        // the other pass's barcodes — about half of its sweeps for C4.  Only when the pairs mode in its known form is what reads
-        // tier 1's list (nothing else understands the state bits), reads fit 30 bits and min_delta = 0 (a lone carried winner
-        // then IS the pass's result).
-        bool carry_on = false;
-        for (BdxFilterSet &f : ctx->fs)
-            f.wplan.d_carry = f.pplan.d_carry = f.wplan_k.d_carry = f.wplan_a.d_carry = f.pplan_k.d_carry = f.pplan_a.d_carry = nullptr;
-        // (the known-trim / known-alignment forms — wave1k — and the plain known-score form of a dual config without trimming — wave1)
-        const bool carry_tier = tiered && (wave1k || (wave1 && !split && !ctx->fs[1].wplan.winm));
-        if (carry_tier && ctx->dev.is_dual && ctx->dev.min_delta == 0.0 && !ctx->tune.no_carry && n_reads < (1LL << 30) && o.pass_start == nullptr &&
-            o.pass_end == nullptr && o.pass_raw == nullptr && o.pass_bc == nullptr && o.pass_score == nullptr && o.pass_delta == nullptr) {
-            BdxWavePlan &pp = wave1k ? (aln_ok ? ctx->fs[0].pplan_a : ctx->fs[0].pplan_k) : ctx->fs[0].pplan;
-            BdxWavePlan &t1p = wave1k ? wk1 : ctx->fs[1].wplan;
-            if (size_pairs(ctx, pp, tier_len) && pp.groups <= 1 && pp.pairs_kb <= 4 && !pp.split) {
-                HIP_TRY(ctx, ctx->d_carry.ensure((size_t)n_reads * 4 + 64));
-                carry_on = true;
-                t1p.d_carry = (uint32_t *)ctx->d_carry.p;
-                pp.d_carry = (uint32_t *)ctx->d_carry.p;
-            }
-        }
-        if (tiered) {
-            HIP_TRY(ctx, ctx->d_tier.ensure((size_t)n_reads * 4 + 64));
-            BdxTierArgs t1{1, (uint32_t *)ctx->d_tier.p, (unsigned int *)(scratch + 192), nullptr, nullptr};
-            BdxFilterSet &f1 = ctx->fs[1];
-            f1.bplan.d_tile_counter = (int *)(scratch + 256);
-            f1.bplan.dense_w = 0;
-            f1.bplan.grid_override = ctx->tune.grid;
-            f1.bplan.dbg = ctx->tune.debug;
-            if (wave1k) {  // tier 1 as the known-end form of the wave kernel: verdicts + trimmed keep range of what it settles, the rest listed
-                HIP_TRY(ctx, bdx_launch_wave_end(ctx->dev, wk1, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
-                                                 ctx->counts, 1, f1.bplan.tier_slo[0], t1.out_list, t1.out_count, ctx->stream, ctx->tune.debug, f1.bplan.tier_slo[1],
-                                                 aln_ok ? stp : nullptr));
-                ctx->wave_launches += 1;
-            } else if (ctx->pairs_tier && split && windows && !dense_w && !ctx->dev.vlen && size_pairs(ctx, f1.pplan, batch_len)) {
-                // the pairs tier: tier 1's filter is the same-diagonal pairs mode over every read of the batch
-                HIP_TRY(ctx, bdx_launch_pairs(ctx->dev, f1.pplan, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, nullptr,
-                                              nullptr, o, nullptr, nullptr, nullptr, ctx->stream, ctx->tune.debug >> 8, &wsp));
-                ctx->pair_launches += 1;
-                pairs_t1 = true;
-            } else if (wsplit1) {  // tier 1's filter as the wave-autonomous kernel (split mode: the exact kernel settles and lists)
-                HIP_TRY(ctx, bdx_launch_wave(ctx->dev, f1.wplan, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
-                                             nullptr, (int *)(scratch + 256), 0, 0.0, nullptr, nullptr, ctx->stream, ctx->tune.debug, &wsp));
-                ctx->wave_launches += 1;
-            } else if (wave1 && f1.wplan.winm) {  // ... in window mode
-                HIP_TRY(ctx, bdx_launch_wave_win(ctx->dev, f1.wplan, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
-                                                 ctx->counts, 1, f1.bplan.tier_slo[0], t1.out_list, t1.out_count, ctx->stream, ctx->tune.debug));
-                ctx->wave_launches += 1;
-            } else if (wave1) {  // tier 1 as the wave-autonomous kernel: same budgets, same settle rule, same list
-                HIP_TRY(ctx, bdx_launch_wave(ctx->dev, f1.wplan, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
-                                             ctx->counts, (int *)(scratch + 256), 1, f1.bplan.tier_slo[0], t1.out_list, t1.out_count, ctx->stream, ctx->tune.debug,
-                                             nullptr, f1.bplan.tier_slo[1]));
-                ctx->wave_launches += 1;
-            } else
-            HIP_TRY(ctx, bdx_launch_bitpar(ctx->dev, ctx->plan, f1.bplan, f1.splan, d_seq_bytes, (const long long *)d_seq_off, n_reads,
-                                           o, ctx->counts, c0, c1, ctx->stream, w0, w1, n0, n1, split ? 1 : 0, exc_list, exc_count, &t1));
-            if (split && !wave1k) HIP_TRY(ctx, poison_check(nullptr, nullptr, false, true));
-            if (split && !wave1k)  // the exact kernel answers what tier 1 settles and lists the rest (known-score / known-end configs: the filter kernel did)
-                HIP_TRY(ctx, bdx_launch_generic(band_cfg(f1), ctx->plan, d_seq_bytes, (const long long *)d_seq_off, n_reads, o, ctx->counts,
-                                                c0, npass > 1 ? c1 : nullptr, ctx->stream, w0, npass > 1 ? w1 : nullptr, n0,
-                                                npass > 1 ? n1 : nullptr, nullptr, nullptr, stp, &t1, f1.bplan.tier_slo));
-            // tier 0 walks the list: scattered reads -> slot staging
-            // (tier 0 sees a fraction of the batch — 10..25 % in the bench configs: its tile size is planned for a sixteenth of
-            // the batch, so that the list of a small batch still spreads over the device — C5, 400 k reads: tiles of 16 instead
-            // of 128 reads, 0.42 -> 0.38 ms; batches of millions of reads keep their tiles)
-            long long n_list_est = n_reads / (ctx->tune.tier0_div > 0 ? ctx->tune.tier0_div : 16);
-            if (n_list_est < 1) n_list_est = 1;
-            if (!size_bitpar(ctx, tier_len, n_list_est, true)) return fail(ctx, BDX_E_DEVICE, "internal: tier 0 cannot be planned in list mode");
-            t0.in_list = (const uint32_t *)ctx->d_tier.p;
-            t0.in_count = (const unsigned int *)(scratch + 192);
-        }
-        if (tiered || wave0 || wave0k) HIP_TRY(ctx, poison_check((uint32_t *)t0.in_list, t0.in_count, true, false, carry_on));
-        // Pairs mode of the wave kernel between tier 1 and the general kernel: the listed reads are gathered into slots and
-        // filtered at the full budgets by the two-intact-pieces lemma.  Known-score configs: it answers them (what it cannot
-        // answer goes on to the general kernel in list mode); split configs: it is tier 0's filter (masks + windows of the
-        // listed reads for the exact kernel).
-        bool pairs = false, pairs_k = false;
-        if (tiered && (kend_ok || aln_ok) && size_pairs(ctx, aln_ok ? ctx->fs[0].pplan_a : ctx->fs[0].pplan_k, tier_len)) {
-            // known-end class: the pairs mode answers the listed reads itself (verdict + trimmed keep range); what it cannot
-            // answer goes on to the split path in list mode
-            const BdxWavePlan &pp = aln_ok ? ctx->fs[0].pplan_a : ctx->fs[0].pplan_k;
-            HIP_TRY(ctx, ctx->d_wlist.ensure((size_t)n_reads * 4 + 64));
-            if (ctx->tune.poison) HIP_TRY(ctx, hipMemsetAsync(ctx->d_wlist.p, 0xA5, ctx->d_wlist.cap, ctx->stream));
-            uint32_t *list2 = (uint32_t *)ctx->d_wlist.p;
-            unsigned int *count2 = (unsigned int *)(scratch + 320);
-            HIP_TRY(ctx, bdx_launch_pairs(ctx->dev, pp, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, t0.in_list,
-                                          t0.in_count, o, ctx->counts, list2, count2, ctx->stream, ctx->tune.debug >> 8, nullptr, aln_ok ? stp : nullptr));
-            ctx->pair_launches += 1;
-            pairs = pairs_k = true;
-            t0.in_list = list2;
-            t0.in_count = count2;
-            HIP_TRY(ctx, poison_check(list2, count2, true, false));
-        } else
-        if (tiered && (!split || windows) && !dense_w && size_pairs(ctx, tier_len)) {
-            const BdxWavePlan &pp = ctx->fs[0].pplan;
-            if (!split) HIP_TRY(ctx, ctx->d_wlist.ensure((size_t)n_reads * 4 + 64));
-            if (ctx->tune.poison && !split) HIP_TRY(ctx, hipMemsetAsync(ctx->d_wlist.p, 0xA5, ctx->d_wlist.cap, ctx->stream));
-            uint32_t *list2 = split ? nullptr : (uint32_t *)ctx->d_wlist.p;
-            unsigned int *count2 = split ? nullptr : (unsigned int *)(scratch + 320);
-            HIP_TRY(ctx, bdx_launch_pairs(ctx->dev, pp, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, t0.in_list,
-                                          t0.in_count, o, split ? nullptr : ctx->counts, list2, count2, ctx->stream, ctx->tune.debug >> 8, split ? &wsp_all : nullptr));
-            ctx->pair_launches += 1;
-            pairs = true;
-            if (!split) {  // the general kernel (list mode) evaluates what is left
-                t0.in_list = list2;
-                t0.in_count = count2;
-                HIP_TRY(ctx, poison_check(list2, count2, true, false));
-            }
-        }
-        // Same-diagonal pairs mode as the ONLY filter of a split config without tiers (weighted costs whose full budget is beyond
-        // every seeded variant — the reference's demo2 options): every read of the batch is laid out in slots and scanned;
-        // masks + windows of all reads go to the exact kernel's dense launch.
-        bool pairs_all = false;
-        if (!tiered && split && windows && !dense_w && !wsplit0 && !wave0k && !ctx->dev.vlen && ctx->fs[0].pplan.enabled &&
-            ctx->fs[0].pplan.pairs_kb >= 8 && ctx->fs[0].pplan.split && size_pairs(ctx, batch_len)) {
-            const BdxWavePlan &pp = ctx->fs[0].pplan;
-            HIP_TRY(ctx, bdx_launch_pairs(ctx->dev, pp, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, nullptr,
-                                          nullptr, o, nullptr, nullptr, nullptr, ctx->stream, ctx->tune.debug >> 8, &wsp_all));
-            ctx->pair_launches += 1;
-            pairs_all = true;
-        }
-        ctx->F().bplan.d_tile_counter = (int *)(scratch + 64);
-        ctx->F().bplan.dense_w = dense_w;
-        ctx->F().bplan.grid_override = ctx->tune.grid;
-        ctx->F().bplan.dbg = ctx->tune.debug;
-        if ((pairs && split && !pairs_k) || pairs_all) {
-            // (tier 0's filter already ran: the pairs mode wrote the listed reads' masks and windows)
-        } else if (wsplit0) {
-            HIP_TRY(ctx, bdx_launch_wave(ctx->dev, ctx->fs[0].wplan, ctx->plan.hist_entries, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
-                                         nullptr, (int *)(scratch + 256), 0, 0.0, nullptr, nullptr, ctx->stream, ctx->tune.debug, &wsp));
-            ctx->wave_launches += 1;
-        } else
-        HIP_TRY(ctx, bdx_launch_bitpar(ctx->dev, ctx->plan, ctx->F().bplan, ctx->F().splan, d_seq_bytes,
-                                       (const long long *)d_seq_off, n_reads, o, ctx->counts, c0, c1, ctx->stream, w0, w1, n0,
-                                       n1, split ? 1 : 0, exc_list, exc_count, (tiered || wave0 || wave0k) ? &t0 : nullptr));
-        const bool listed = tiered || wave0k;  // split configs: the exact kernel's last launch walks a list
-        if (split)
-            HIP_TRY(ctx, poison_check(listed ? (uint32_t *)t0.in_list : nullptr, listed ? t0.in_count : nullptr, false, true));
-        else
-            HIP_TRY(ctx, poison_check(exc_list, exc_count, true, false));
-        if (split)  // (tiered: list mode over the reads tier 1 handed on)
-            HIP_TRY(ctx, bdx_launch_generic(band_cfg(ctx->F()), ctx->plan, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
-                                            ctx->counts, c0, npass > 1 ? c1 : nullptr, ctx->stream, w0,
-                                            npass > 1 ? w1 : nullptr, n0, npass > 1 ? n1 : nullptr, listed ? t0.in_list : nullptr,
-                                            listed ? t0.in_count : nullptr, stp, nullptr, nullptr, zero_next));
-        else
-            HIP_TRY(ctx, bdx_launch_generic(ctx->dev, ctx->plan, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
-                                            ctx->counts, c0, npass > 1 ? c1 : nullptr, ctx->stream, nullptr, nullptr, nullptr,
-                                            nullptr, exc_list, exc_count, stp, nullptr, nullptr, zero_next));
-        // (the call's last launch is enqueued: the other half will hold zeros when the next call's kernels start)
-        ctx->scratch_clean[1 - spar] = true;
-        ctx->scratch_par = 1 - spar;
-#ifdef BDX_TUNING
-        if (ctx->tune.debug & 128) {  // tuning statistics of the fused kernel (see bdx_bitpar.hip)
-                unsigned int st[4] = {0, 0, 0, 0}, tl = 0;
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                HIP_TRY(ctx, hipMemcpy(st, exc_count, sizeof(st), hipMemcpyDeviceToHost));
-                HIP_TRY(ctx, hipMemcpy(&tl, scratch + 192, sizeof(tl), hipMemcpyDeviceToHost));
-                fprintf(stderr, "[bdx] handed over %u reads; %u windowed sweeps, %u columns, %u tiles with a fallback read; tier 0 list %u (of %lld reads)\n",
-                        st[0], st[1], st[2], st[3], tl, (long long)n_reads);
-        }
-#endif
-        ctx->last_blocks = (n_reads + ctx->F().bplan.reads_per_block - 1) / ctx->F().bplan.reads_per_block;
-        ctx->path = ctx->F().splan.enabled ? (ctx->F().splan.diag ? "qgram2+bitpar+verify" : "qgram+bitpar+verify") : "bitpar+verify";
-        if (wsplit0) ctx->path = "wave+verify";
-        if (pairs) ctx->path = pairs_k ? (aln_ok ? "pairs(aln) > " : "pairs(end) > ") + ctx->path : split ? "pairs+verify" : "pairs > " + ctx->path;
-        if (pairs_all) ctx->path = "pairs(diag)+verify";
-        if (tiered) ctx->path = (pairs_t1 ? "tier1:pairs(diag) > " : (wave1k && aln_ok) ? "tier1:wave(aln) > " : wave1k ? "tier1:wave(end) > " : (wave1 && ctx->fs[1].wplan.winm) ? "tier1:wave(win) > " : (wave1 || wsplit1) ? "tier1:wave > " : "tier1:qgram+bitpar > ") + ctx->path;
-        if (wave0) ctx->path = (ctx->fs[0].wplan.winm ? "wave(win) > " : "wave > ") + ctx->path;
-        if (wave0k) ctx->path = (aln_ok ? "wave(aln) > " : "wave(end) > ") + ctx->path;
-        ctx->filter_used = ctx->F().splan.enabled ? BDX_FILTER_QGRAM : BDX_FILTER_BITPAR;
+        CallPlan p;
+        int rc = plan_call(ctx, o, stp != nullptr, n_reads, batch_len, tier_len, p);
+        if (rc == BDX_OK) rc = reserve(ctx, p, n_reads);
+        if (rc == BDX_OK) rc = enqueue(ctx, p, d_seq_bytes, (const long long *)d_seq_off, n_reads, o, stp);
+        if (rc != BDX_OK) return rc;
+        ctx->last_blocks = (n_reads + ctx->fs[0].bplan.reads_per_block - 1) / ctx->fs[0].bplan.reads_per_block;
+        ctx->path = call_path(ctx, p);
+        ctx->filter_used = ctx->fs[0].splan.enabled ? BDX_FILTER_QGRAM : BDX_FILTER_BITPAR;
     } else {
         HIP_TRY(ctx, bdx_launch_generic(ctx->dev, ctx->plan, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
                                         ctx->counts, nullptr, nullptr, ctx->stream, nullptr, nullptr, nullptr, nullptr, nullptr,

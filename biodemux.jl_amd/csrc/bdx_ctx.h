@@ -92,7 +92,7 @@ struct bdx_ctx {
     BdxDevCfg dev{};
     BdxGenericPlan plan{};
     BdxFilterSet fs[2];
-    int cur = 0;        // the set the table builders / planners below work on
+    int cur = 0;        // the set the table builders of bdx_create work on
     int tiered = 0;     // fs[1] is usable: classify runs tier 1 first, tier 0 on the reads it cannot settle
     BdxFilterSet &F() { return fs[cur]; }
     const BdxFilterSet &F() const { return fs[cur]; }
