@@ -14,11 +14,16 @@ timed region starts; the step classifies every read of the rank's shard through 
 (bdx_classify_device) and all-reduces the per-barcode counters (RCCL when N > 1: through the C-ABI's own
 communicator, bdx_allreduce_counts).  Weak scaling: every rank owns its own shard of the global stream.
 
-Run:  python bench.py [--gpus N --steps K --warmup W --config C2]
+Run:  python bench.py [--gpus N --steps K --warmup W --config C2] [--full]
 With N > 1 and no torchrun environment the script starts its own N ranks (python -m torch.distributed.run)
 before anything touches the GPU, and exits with their code.  Prints ONE JSON line on rank 0.
 ``--dump-outputs DIR`` also writes what the last timed step computed as DIR/<name>.npy (at most 64 MB; inputs are
 seeded, so two builds run with the same arguments can be compared output for output).
+
+A plain run does only what the headline needs: set up, warm up, time the steps, dump, print.  ``--full`` (one rank)
+adds the measurements beyond it, after the timed steps: the host-buffer path, the CPU baseline, and with the default
+C2 run the short legs of the other configs and the end-to-end FASTQ figure (see full_legs).  Without it their fields
+of the result line are null.
 """
 from __future__ import annotations
 
@@ -47,6 +52,9 @@ def _parse():
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU (default: the config's size)")
     ap.add_argument("--filter", default="auto", help="auto|off|qgram|bitpar (all give identical results)")
     ap.add_argument("--max-error-rate", type=float, default=None, help="override the config's rate")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline (host-buffer path, CPU baseline, other configs, "
+                         "end-to-end figure); the --no-* options below skip single ones of them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short legs for the other BASELINE configs and the end-to-end figure")
     ap.add_argument("--e2e-reads", type=int, default=10_000_000, help="reads of the end-to-end FASTQ leg (0: skip)")
@@ -74,6 +82,21 @@ def _self_launch(args) -> int:
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     return subprocess.call(cmd, env=env)
+
+
+def full_legs(args, world: int) -> set:
+    """The measurements beyond the headline this run makes: none without --full, and none in a multi-rank run.
+    "other_configs" (the short legs and the end-to-end figure) needs the default C2 workload as it is."""
+    if not args.full or world != 1:
+        return set()
+    legs = set()
+    if not args.no_host_path:
+        legs.add("host_path")
+    if not args.no_cpu_baseline:
+        legs.add("cpu_baseline")
+    if args.config == "C2" and not args.no_other_configs and not args.reads and args.max_error_rate is None:
+        legs.add("other_configs")
+    return legs
 
 
 def _host_cores() -> int:
@@ -517,10 +540,12 @@ def main():
     info = hc.launch_info()
     path = hc.kernel_path
 
+    legs = full_legs(args, world)
+
     # ---- host-buffer path (SURVEY §8d "two throughputs"): numpy buffers -> H2D -> kernels -> D2H through
     # bdx_classify_host.  PCIe-inclusive; reported beside the headline, never as `value`. ----
     host_path = None
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if "host_path" in legs:
         hc.set_counts_buffer(0)
         hc.set_stream(0)
         hc.classify(seq, off)  # sizes the staging buffers
@@ -563,7 +588,7 @@ def main():
                                 "host buffers / time)" if windowed else "")}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if "cpu_baseline" in legs:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import bdx_oracle as orc  # the checker / reported CPU baseline — never the product path
 
@@ -602,11 +627,11 @@ def main():
     if args.max_error_rate is None and args.filter == "auto":
         traffic, traffic_src, valu = _profile_counters(args.config, n)
 
-    # the other BASELINE configs (short legs) and the end-to-end figure ride on the default single-GPU run, so that one
-    # driver invocation carries every config; the headline above is unaffected (it has been timed already)
+    # the other BASELINE configs (short legs) and the end-to-end figure ride on the default single-GPU --full run, so
+    # that one invocation carries every config; the headline above is unaffected (it has been timed already)
     other, e2e, extra = None, None, None
     matched_headline = int(counts[1]) if world == 1 else None  # (the counter vector is zeroed at the top of every step)
-    if rank == 0 and world == 1 and args.config == "C2" and not args.no_other_configs and not args.reads and args.max_error_rate is None:
+    if "other_configs" in legs:
         del d_seq, d_off
         torch.cuda.empty_cache()
         other, extra = [], []

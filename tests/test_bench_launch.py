@@ -1,5 +1,5 @@
 """bench.py --gpus N outside torchrun must start its own N ranks as a child job (never re-exec, never touch
-the GPU in the parent) and pass the child's exit code on."""
+the GPU in the parent) and pass the child's exit code on; a plain run makes only the headline, --full the rest."""
 import os
 import sys
 
@@ -52,6 +52,30 @@ def test_steps_must_be_positive(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--dump-outputs", "d"])
     args = bench._parse()
     assert args.steps == 3 and args.dump_outputs == "d"
+
+
+def test_plain_run_makes_only_the_headline(monkeypatch):
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench._parse()
+    assert not args.full and bench.full_legs(args, 1) == set()
+
+
+def test_full_run_keeps_every_leg(monkeypatch):
+    import bench
+
+    def legs(*argv, world=1):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--full", *argv])
+        return bench.full_legs(bench._parse(), world)
+
+    assert legs() == {"host_path", "cpu_baseline", "other_configs"}
+    assert legs("--no-cpu-baseline", "--no-host-path") == {"other_configs"}
+    assert legs("--no-other-configs") == {"host_path", "cpu_baseline"}
+    # the short legs and the end-to-end figure belong to the default C2 workload only
+    assert legs("--config", "C4") == legs("--reads", "1000") == legs("--max-error-rate", "0.2") == {"host_path", "cpu_baseline"}
+    # and every leg to a single rank
+    assert legs(world=2) == set()
 
 
 def test_dump_outputs_whole_vectors_when_they_fit(tmp_path):

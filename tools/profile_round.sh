@@ -1,17 +1,18 @@
 #!/bin/bash
-# usage (on the GPU box, via gpurun): tools/profile_round.sh <tag> [bench.py args, e.g. --config C4]
-# The official bench line, the rocprofv3 kernel-trace summary of the same command and the HBM
-# traffic counters (separate --pmc passes), all under gpurun_out/<tag>_*; afterwards, here:
-#   python tools/summarize_prof.py <tag> <reads per launch> gpurun_out/<tag>_stats gpurun_out/<tag>_fetch gpurun_out/<tag>_write gpurun_out/<tag>_sq
+# usage (on the GPU box): tools/profile_round.sh <tag> [bench.py args, e.g. --config C4]
+# The full bench line (bench.py --full), the rocprofv3 kernel-trace summary of the same command and the HBM
+# traffic counters (separate --pmc passes), all under $PROFILE_OUT/<tag>_* (default build/profile); afterwards:
+#   python tools/summarize_prof.py <tag> <reads per launch> $PROFILE_OUT/<tag>_stats $PROFILE_OUT/<tag>_fetch $PROFILE_OUT/<tag>_write $PROFILE_OUT/<tag>_sq
 tag=${1:?tag}
 shift
 cd "$(dirname "$0")/.." && export TMPDIR=/tmp || exit 1
-# (the profiled runs carry ONE config: the short legs of the default run launch the same kernel instantiations on other batches)
-P="--no-cpu-baseline --no-host-path --no-other-configs --e2e-reads 0"
-python bench.py "$@" > gpurun_out/${tag}_bench.json.log 2> gpurun_out/${tag}_bench.err || exit 1
-rocprofv3 --kernel-trace --stats -d gpurun_out/${tag}_stats -o p --output-format csv -- python bench.py $P "$@" > gpurun_out/${tag}_stats.log 2>&1 || exit 1
-rocprofv3 --pmc FETCH_SIZE -d gpurun_out/${tag}_fetch -o p --output-format csv -- python bench.py $P --steps 2 --warmup 1 "$@" > gpurun_out/${tag}_fetch.log 2>&1 || exit 1
-rocprofv3 --pmc WRITE_SIZE -d gpurun_out/${tag}_write -o p --output-format csv -- python bench.py $P --steps 2 --warmup 1 "$@" > gpurun_out/${tag}_write.log 2>&1 || exit 1
-rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS -d gpurun_out/${tag}_sq -o p --output-format csv -- python bench.py $P --steps 2 --warmup 1 "$@" > gpurun_out/${tag}_sq.log 2>&1 || exit 1
-cat gpurun_out/${tag}_bench.json.log
-rocprofv3 --pmc SQ_BUSY_CYCLES SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAIT_INST_ANY SQ_INSTS_VMEM -d gpurun_out/${tag}_sq2 -o p --output-format csv -- python bench.py $P --steps 2 --warmup 1 "$@" > gpurun_out/${tag}_sq2.log 2>&1 || exit 1
+out=${PROFILE_OUT:-build/profile}
+mkdir -p "$out" || exit 1
+# (the profiled runs are plain runs, ONE config: the short legs of the full run launch the same kernel instantiations on other batches)
+python bench.py --full "$@" > "$out/${tag}_bench.json.log" 2> "$out/${tag}_bench.err" || exit 1
+rocprofv3 --kernel-trace --stats -d "$out/${tag}_stats" -o p --output-format csv -- python bench.py "$@" > "$out/${tag}_stats.log" 2>&1 || exit 1
+rocprofv3 --pmc FETCH_SIZE -d "$out/${tag}_fetch" -o p --output-format csv -- python bench.py --steps 2 --warmup 1 "$@" > "$out/${tag}_fetch.log" 2>&1 || exit 1
+rocprofv3 --pmc WRITE_SIZE -d "$out/${tag}_write" -o p --output-format csv -- python bench.py --steps 2 --warmup 1 "$@" > "$out/${tag}_write.log" 2>&1 || exit 1
+rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS -d "$out/${tag}_sq" -o p --output-format csv -- python bench.py --steps 2 --warmup 1 "$@" > "$out/${tag}_sq.log" 2>&1 || exit 1
+cat "$out/${tag}_bench.json.log"
+rocprofv3 --pmc SQ_BUSY_CYCLES SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAIT_INST_ANY SQ_INSTS_VMEM -d "$out/${tag}_sq2" -o p --output-format csv -- python bench.py --steps 2 --warmup 1 "$@" > "$out/${tag}_sq2.log" 2>&1 || exit 1

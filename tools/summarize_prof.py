@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Collect rocprofv3 outputs from gpurun_out/ into profiles/<tag>_*.{csv,json} (tracked).
+"""Collect rocprofv3 outputs (tools/profile_round.sh) into profiles/<tag>_*.{csv,json} (tracked).
 usage: summarize_prof.py <tag> <reads per launch> <stats_dir> [<pmc_dir> ...]
 <tag> should carry the bench config between underscores (r02_C2_final, r02_C4_...): bench.py looks for
 profiles/*_<config>_*_pmc.json."""
