@@ -99,8 +99,28 @@ struct WaveArgs {
     BdxDevPass dpass[2];     // the passes' ranges (ranged only)
     const uint32_t *idmap;   // [count] batch read numbers (= the list an earlier tier wrote; NULL: every read of the batch)
     const unsigned int *n_dev;  // the number of listed reads lives on the device (NULL: n_reads)
+    uint32_t req;            // REQ_* bits below: the outputs asked for, tier, min_delta != 0 (set by launch_wave from the fields above)
     int dbg;  // timing experiments (env BDX_DEBUG), compiled in ONLY with -DBDX_TUNING — results are wrong when a skip bit
               // is set: 1 skip verdicts, 2 skip sweeps, 4 skip resolve + emit, 8 skip seed scan, 32 skip transcode, 64 skip loads
+};
+
+// The kernel's arguments where they are stored (the kernel-argument segment: WaveArgs is the kernel's only argument), for
+// fields that are cold inside the tile loop.  The segment's address passes through an empty asm statement at every use, so
+// the compiler reads such a field with a scalar load where it is used instead of holding it in scalar registers across the
+// loop (where it spilled into vector-register lanes).
+typedef const __attribute__((address_space(4))) WaveArgs *KArgs;
+__device__ __forceinline__ KArgs kargs() {
+    uint64_t p = (uint64_t)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return (KArgs)(uintptr_t)p;
+}
+
+// outputs a launch asks for (a.out's non-null pointers and a.counts), one bit each: WaveArgs::req
+enum : uint32_t {
+    REQ_BC1 = 1u, REQ_BC2 = 2u, REQ_KS = 4u, REQ_KE = 8u, REQ_PSTART = 16u, REQ_PEND = 32u, REQ_PRAW = 64u, REQ_PBC = 128u,
+    REQ_PSCORE = 256u, REQ_PDELTA = 512u, REQ_COUNTS = 1024u,
+    REQ_TIER = 2048u, REQ_DELTA = 4096u,  // (two switches of the verdicts beside them: a.tier != 0, a.min_delta != 0)
+    REQ_PASS = REQ_PSTART | REQ_PEND | REQ_PRAW | REQ_PBC | REQ_PSCORE | REQ_PDELTA  // the per-pass outputs
 };
 
 // The product library has no phase-skip switches: BDX_DBG folds to 0 and the branches disappear.
@@ -337,6 +357,7 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
     constexpr int q = Q;  // seed length
     // (pairs mode: the number of gathered reads is only known on the device)
     const bool ranged = GEN && a.ranged != 0, dual = GEN && a.dual != 0;
+    const uint32_t req = a.req;
     static_assert(!WINM || (!PAIRS && !SPLIT && KEND == 0 && GEN), "window mode: the non-split single-seed kernel");
     constexpr bool SCAT = PAIRS || WINM;  // scattered tiles: every read of a tile is fetched on its own (by list index) into a slot of the images
     // Carried passes (dual tiered known-class configs with min_delta = 0): tier 1 lists a read when ONE of its passes is open; the pass
@@ -689,10 +710,13 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
             // just leaves the read without candidates
             const int n = lane < nr ? rlen(lane) : 0;
             bool known = true;
+            const KArgs ka = kargs();  // (the ranges: read here, see kargs)
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
                 PassWindow w{1, 0, 0, 0};
-                const bool ok = (p == 0 || a.B0 < B) && lane < nr && pass_window(a.dpass[p], n, w);
+                BdxDevPass dp;
+                __builtin_memcpy(&dp, (const void *)&ka->dpass[p], sizeof dp);  // (scalar loads: the source stays in the constant space)
+                const bool ok = (p == 0 || a.B0 < B) && lane < nr && pass_window(dp, n, w);
                 wwin[(2 * p) * RW + lane] = ok ? w.first - 1 : 0;
                 wwin[(2 * p + 1) * RW + lane] = ok ? w.last : 0;
                 if (p == 0 || a.B0 < B) known = known && ok && n > 0 && w.max_start >= n && w.min_end <= 1;
@@ -1085,8 +1109,8 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
         } else {
             constexpr uint32_t AMASK = ((1u << (2 * Q - 5)) - 1u) << 2;
             constexpr uint32_t KMASK = (1u << (2 * Q)) - 1u;
-            uint32_t amask = AMASK;
-            asm volatile("" : "+v"(amask));  // (in a vector register: a literal or scalar operand slows the AND down)
+            uint32_t amask = AMASK, kmask = KMASK, emask = 0x55555555u;
+            asm volatile("" : "+v"(amask), "+v"(kmask), "+v"(emask));  // (in vector registers: a literal or scalar operand slows the AND down)
             // ranged single-pass configs whose window is much shorter than the read (ref_search_range = "1:60"): only the groups
             // of sixteen positions that overlap each read's window are scanned — lane = (read, group of its window) instead of
             // lane = group of the flat image.  A tile with a window longer than planned (a read beyond the length hint) takes
@@ -1111,7 +1135,7 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
             for (int g0i = 0; g0i < nscan; g0i += 64) {
                 int g = g0i + lane;
                 bool ong = g < nscan;
-                uint32_t keep = 0xFFFFu;  // positions of the group that are this lane's to report
+                uint32_t keep = emask;  // positions of the group that are this lane's to report (position i: bit 2 i, as the hits below)
                 if (gpr > 0) {
                     const int i = g0i + lane;
                     const int tw = ong ? (int)(((uint32_t)i * (uint32_t)a.scan_gpr_inv) >> 16) : 0;  // (read, window) number
@@ -1126,7 +1150,8 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                     }
                     const int below = s0 - 16 * g, above = f1 - 16 * g;  // bits < below lie in front of the window, bits >= above in the next read
                     ong = ong && above > 0 && g < nvec;
-                    keep = (below > 0 ? (0xFFFFu << (below > 16 ? 16 : below)) : 0xFFFFu) & (above < 16 ? ((1u << (above < 0 ? 0 : above)) - 1u) : 0xFFFFu) & 0xFFFFu;
+                    const int b2 = below > 0 ? 2 * (below > 16 ? 16 : below) : 0, a2 = above < 16 ? 2 * (above < 0 ? 0 : above) : 32;
+                    keep = (b2 >= 32 ? 0u : 0xFFFFFFFFu << b2) & (a2 >= 32 ? 0xFFFFFFFFu : (1u << a2) - 1u) & 0x55555555u;
                 }
                 uint32_t hits = 0;
                 uint32_t w0 = 0, w1 = 0;
@@ -1145,22 +1170,42 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                         lds_read8(word, addr);
                         lds_wait8(word);
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) hits = __builtin_amdgcn_alignbit(word[i] >> (Wk[8 * h + i] & 31u), hits, 1);
+                        for (int i = 0; i < 8; ++i) hits = __builtin_amdgcn_alignbit(word[i] >> (Wk[8 * h + i] & 31u), hits, 2);
                     }
-                    hits >>= 16;
+                    // (two bits per position: its hit at bit 2 i, the next bit of its probed word at 2 i + 1 — masked off; the even
+                    // bits give the append the key's shift 2 i directly)
                     hits &= keep;
                 }
-                // append: one trip per "layer" of hits (the lowest remaining hit of every lane that has one)
+                // append by count and prefix: every lane's hits go to a run of their own, the lanes' runs in lane order.  The
+                // lane's first entry is nhq + the hits of the lanes below it, summed as one ballot per level j of the fullest
+                // lane (lanes with more than j hits; mbcnt accumulates), then each lane writes its run in a loop of its own.
+                // The resolve below does not depend on the order of the entries in hq: every hit is looked up on its own, a
+                // record is keyed by (barcode, first diagonal) whichever hit opens it, its diagonal bits are OR-ed in, and each
+                // record's window is lossless on its own (phase 3).
                 unsigned long long mk = __builtin_amdgcn_ballot_w64(hits != 0u);
-                while (mk) {
-                    const int k = nhq + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-                    if (hits) {
-                        const int i = __builtin_ctz(hits);
-                        hits &= hits - 1u;
-                        if (k < HQ) hq[k] = ((uint32_t)(16 * g + i) << 16) | (__builtin_amdgcn_alignbit(w1, w0, 2 * i) & KMASK);
+                if (mk) {
+                    const uint32_t nl = (uint32_t)__builtin_popcount(hits);
+                    uint32_t k = (uint32_t)nhq;
+                    for (uint32_t j = 1; mk; ++j) {
+                        k = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, k));
+                        nhq += (int)__builtin_popcountll(mk);
+                        mk = __builtin_amdgcn_ballot_w64(nl > j);
                     }
-                    nhq += (int)__builtin_popcountll(mk);
-                    mk = __builtin_amdgcn_ballot_w64(hits != 0u);
+                    // overflow: nhq > HQ sends the whole tile to the list (hq_ok below), so a trip that runs over writes
+                    // nothing, and every entry written has k < HQ
+                    if (nhq <= HQ && hits) {
+                        const uint32_t gp = (uint32_t)g << 20;  // (flat position 16 g) << 16
+                        LDS uint32_t *dst = hq + k;
+                        do {
+                            const uint32_t i2 = (uint32_t)__builtin_ctz(hits);  // 2 i for position i of the group
+                            hits &= hits - 1u;
+                            const uint32_t ph = gp + (i2 << 15), kw = __builtin_amdgcn_alignbit(w1, w0, i2);
+                            // (16-bit keys: the two low bytes of the key word under the position, one v_perm)
+                            *dst = Q == 8 ? __builtin_amdgcn_perm(ph, kw, 0x07060100u) : ph | (kw & kmask);
+                            __builtin_amdgcn_sched_barrier(0);  // (the address steps after the write: in place, no copy)
+                            ++dst;
+                        } while (hits);
+                    }
                 }
             }
         }
@@ -1382,6 +1427,10 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
         }
 
         // ---- verdicts: lane = read; reducer replay on the survivors' unit distances ----
+        // (the requested outputs, as a value of this tile: tests of its bits stay scalar tests here and are not hoisted out of
+        // the tile loop as one 64-bit lane mask each)
+        uint32_t rq = req;
+        asm volatile("" : "+s"(rq));
         const bool active = lane < nr;
         const long long ridx = SCAT ? (long long)gid[lane < RW ? lane : 0] : r0 + lane;
         Verdict vd{0, 0, -1, -1};
@@ -1393,8 +1442,8 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
             const int cnt = scnt[lane], cnt1 = dual ? wcl1[lane] : 0;
             // known-score class per read: this kernel only runs for configs whose ranges resolve to
             // 1:n, so n >= 1 is all that is left to check (n = 0: the :805 sanity check sends the read to :unknown)
-            const bool simple = a.out.pass_start == nullptr && a.out.pass_end == nullptr && a.out.pass_raw == nullptr && a.out.pass_bc == nullptr &&
-                                a.out.pass_score == nullptr && a.out.pass_delta == nullptr;  // (kernel-uniform: only the verdict vectors are wanted)
+            const bool simple = (rq & REQ_PASS) == 0u;  // (kernel-uniform: only the verdict vectors are wanted)
+            const bool tiered = (rq & REQ_TIER) != 0u;  // (the settle rule is looked up for tier 1 only)
             if (simple && !KALN && !flag[lane] && cnt <= 1 && cnt1 <= 1 && n >= 1) {
                 // No or one survivor per pass and nobody asked for scores: the reducers' answer for a lone survivor with distance d
                 // is a per-barcode constant — accepted iff d <= floor(rate * m) and fl(d / m) <= rate (classification.jl:254, :658 /
@@ -1403,7 +1452,12 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                 // only behind a matched pass 1, and a pass 2 without a match makes the read unknown (:887-895).
                 done = true;
                 int pos1 = 0, pos2 = 0;  // known-trim class: position keys of the two passes' survivors (end column / 0xFFFF - start)
-                const int sbit = a.min_delta == 0.0 ? 0 : 16;
+                const int sbit = (rq & REQ_DELTA) ? 16 : 0;
+                // (the settle words follow the meta words in the carve-up above; their address is formed here from meta's, not
+                // held across the tile loop)
+                uint32_t soff = (uint32_t)((B + 7) & ~7);
+                asm volatile("" : "+s"(soff));
+                const LDS uint32_t *const settle_w = meta + soff;
                 bool settled_all = true;
                 if (cnt == 1) {
                     const uint32_t e = slots[lane * 4];
@@ -1411,7 +1465,7 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                     pos1 = (int)(e & 0xFFFFu);
                     const int dmax = (int)((meta[bb] >> 16) & 255u);
                     vd.bc1 = (dmax != 255 && d <= dmax) ? bb + 1 : 0;
-                    settled_all = vd.bc1 > 0 && ((settle[bb] >> (d + sbit)) & 1u) != 0u;
+                    settled_all = tiered && vd.bc1 > 0 && ((settle_w[bb] >> (d + sbit)) & 1u) != 0u;
                 } else {
                     vd.bc1 = 0;
                     settled_all = false;  // (nothing within the capped budgets: tier 0 decides)
@@ -1427,15 +1481,15 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                         pos2 = (int)(e & 0xFFFFu);
                         const int dmax = (int)((meta[g] >> 16) & 255u);
                         bc2v = (dmax != 255 && d <= dmax) ? bb + 1 : 0;
-                        s2 = bc2v > 0 && ((settle[g] >> (d + sbit)) & 1u) != 0u;
+                        s2 = tiered && bc2v > 0 && ((settle_w[g] >> (d + sbit)) & 1u) != 0u;
                     }
                     settled_all = settled_all && s2;
                     vd.bc2 = bc2v;
                     if (bc2v == 0) vd.bc1 = 0;  // (:891-894: the verdict is pass 2's status)
                     if (bc2v == 0) vd.bc2 = 0;
                 }
-                if (a.tier) done = settled_all;
-                if (!PAIRS && a.tier && dual && a.carry_ent != nullptr && !settled_all) {
+                if (tiered) done = settled_all;
+                if (!PAIRS && tiered && dual && a.carry_ent != nullptr && !settled_all) {
                     // one pass settled, the other open: the settled one travels with the read (see CARRY above)
                     if (s1_settled) {
                         cst = 1u;
@@ -1444,7 +1498,7 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                         const uint32_t e = cand[lane * 4];
                         const int bb = KEND ? (int)(e >> 22) : (int)(e >> 8), d = KEND ? (int)((e >> 16) & 63u) : (int)(e & 255u), g = a.B0 + bb;
                         const int dmax = (int)((meta[g] >> 16) & 255u);
-                        if (dmax != 255 && d <= dmax && ((settle[g] >> (d + sbit)) & 1u) != 0u) {
+                        if (dmax != 255 && d <= dmax && ((settle_w[g] >> (d + sbit)) & 1u) != 0u) {
                             cst = 2u;
                             centry = e;
                         }
@@ -1490,14 +1544,14 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                 cfg.need_traceback = KALN ? a.need_tb : 0;
                 classify_known<(KALN ? 2 : (KEND != 0 ? 1 : 0))>(cfg, m0, m1, n, kn0, kn1, vd, p1, p2);
                 done = true;
-                if (a.tier) {
+                if (tiered) {
                     // tier settle rule (same code as bdx_bitpar.hip)
-                    const bool nd = a.min_delta == 0.0;
+                    const bool nd = (rq & REQ_DELTA) == 0u;
                     const auto settled = [&](const PassOut &po, const int c, const double slo) {
                         if (c < 1 || !(po.score < slo)) return false;
                         if (nd) return true;
                         if (c >= 2 && po.sub <= slo) return true;
-                        return a.out.pass_delta == nullptr && (slo - po.score) >= a.min_delta && po.status == 1;
+                        return (rq & REQ_PDELTA) == 0u && (slo - po.score) >= a.min_delta && po.status == 1;
                     };
                     bool ok = settled(p1, cnt, a.tier_slo);
                     if (ok && dual && p1.status == 1) ok = settled(p2, cnt1, a.tier_slo1);
@@ -1518,7 +1572,7 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
             //    column, whose first column is prepared as "row 1 entered here" (D[i] = delta(q1, r[start]) + i - 1).
             // Models + enumeration: oracle orc_known_other_position / orc_selftest_known_alignment.
             // A start <= 0 (the alignment comes out of the initial column, :278-283) is not representable here: such a read is handed on.
-            const bool want_pos = a.out.pass_start != nullptr || a.out.pass_end != nullptr || a.stats.rows > 0;
+            const bool want_pos = (rq & (REQ_PSTART | REQ_PEND)) != 0u || a.stats.rows > 0;
             const int tl = lane < RW ? lane : 0;
             const int n_t = rlen(tl);
             bool lost = false;
@@ -1651,44 +1705,48 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
             }
         }
         if (done) {
-            if (a.out.bc1) a.out.bc1[ridx] = vd.bc1;
-            if (a.out.bc2) a.out.bc2[ridx] = vd.bc2;
-            if (a.out.keep_start) a.out.keep_start[ridx] = vd.keep_start;
-            if (a.out.keep_end) a.out.keep_end[ridx] = vd.keep_end;
-            if (a.out.pass_start) {
-                a.out.pass_start[2 * ridx] = p1.start;
-                a.out.pass_start[2 * ridx + 1] = p2.start;
+            // The output pointers are read here, from the kernel arguments (scalar loads once per tile), and whether each one
+            // is wanted from one bit of `req`: held across the tile loop they took 40 scalar registers, which the compiler
+            // spilled into vector-register lanes and read back every tile.
+            const KArgs ka = kargs();
+            if (rq & REQ_BC1) ka->out.bc1[ridx] = vd.bc1;
+            if (rq & REQ_BC2) ka->out.bc2[ridx] = vd.bc2;
+            if (rq & REQ_KS) ka->out.keep_start[ridx] = vd.keep_start;
+            if (rq & REQ_KE) ka->out.keep_end[ridx] = vd.keep_end;
+            if (rq & REQ_PSTART) {
+                ka->out.pass_start[2 * ridx] = p1.start;
+                ka->out.pass_start[2 * ridx + 1] = p2.start;
             }
-            if (a.out.pass_end) {
-                a.out.pass_end[2 * ridx] = p1.end;
-                a.out.pass_end[2 * ridx + 1] = p2.end;
+            if (rq & REQ_PEND) {
+                ka->out.pass_end[2 * ridx] = p1.end;
+                ka->out.pass_end[2 * ridx + 1] = p2.end;
             }
-            if (a.out.pass_raw) {
-                a.out.pass_raw[2 * ridx] = p1.raw;
-                a.out.pass_raw[2 * ridx + 1] = p2.raw;
+            if (rq & REQ_PRAW) {
+                ka->out.pass_raw[2 * ridx] = p1.raw;
+                ka->out.pass_raw[2 * ridx + 1] = p2.raw;
             }
-            if (a.out.pass_bc) {
-                a.out.pass_bc[2 * ridx] = p1.bc;
-                a.out.pass_bc[2 * ridx + 1] = p2.bc;
+            if (rq & REQ_PBC) {
+                ka->out.pass_bc[2 * ridx] = p1.bc;
+                ka->out.pass_bc[2 * ridx + 1] = p2.bc;
             }
-            if (a.out.pass_score) {
-                a.out.pass_score[2 * ridx] = p1.score;
-                a.out.pass_score[2 * ridx + 1] = p2.score;
+            if (rq & REQ_PSCORE) {
+                ka->out.pass_score[2 * ridx] = p1.score;
+                ka->out.pass_score[2 * ridx + 1] = p2.score;
             }
-            if (a.out.pass_delta) {
-                a.out.pass_delta[2 * ridx] = p1.delta;
-                a.out.pass_delta[2 * ridx + 1] = p2.delta;
+            if (rq & REQ_PDELTA) {
+                ka->out.pass_delta[2 * ridx] = p1.delta;
+                ka->out.pass_delta[2 * ridx + 1] = p2.delta;
             }
             // DemuxStats scalar counters (classification.jl:942-978), accumulated in LDS across the workgroup's tiles
-            if (a.counts) {
-                const int slot = vd.bc1 > 0 ? 4 + (vd.bc1 - 1) * a.counts_stride2 + (vd.bc2 > 0 ? vd.bc2 - 1 : 0) : -1;
+            if (rq & REQ_COUNTS) {
+                const int slot = vd.bc1 > 0 ? 4 + (vd.bc1 - 1) * ka->counts_stride2 + (vd.bc2 > 0 ? vd.bc2 - 1 : 0) : -1;
                 const int cls = vd.bc1 > 0 ? 1 : (vd.bc1 == 0 ? 2 : 3);
                 __hip_atomic_fetch_add(&hist[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 __hip_atomic_fetch_add(&hist[cls], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 if (slot >= 0 && slot < a.hist_entries)
                     __hip_atomic_fetch_add(&hist[slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 else if (slot >= 0)
-                    atomicAdd(&a.counts[slot], 1ULL);
+                    atomicAdd(&ka->counts[slot], 1ULL);
             }
         }
         WAVE_SYNC();  // the next tile reuses the per-read tables
@@ -1713,7 +1771,12 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
 }
 
 template <int RW, int TF, int NV, int Q, bool SPLIT, int KB, int NW, bool MG = false, int KEND = 0, bool GEN = true, bool WINM = false>
-hipError_t launch_wave(const WaveArgs &a, size_t lds, int waves, long long blocks, hipStream_t stream) {
+hipError_t launch_wave(const WaveArgs &a0, size_t lds, int waves, long long blocks, hipStream_t stream) {
+    WaveArgs a = a0;
+    a.req = (a.out.bc1 ? REQ_BC1 : 0u) | (a.out.bc2 ? REQ_BC2 : 0u) | (a.out.keep_start ? REQ_KS : 0u) | (a.out.keep_end ? REQ_KE : 0u) |
+            (a.out.pass_start ? REQ_PSTART : 0u) | (a.out.pass_end ? REQ_PEND : 0u) | (a.out.pass_raw ? REQ_PRAW : 0u) | (a.out.pass_bc ? REQ_PBC : 0u) |
+            (a.out.pass_score ? REQ_PSCORE : 0u) | (a.out.pass_delta ? REQ_PDELTA : 0u) | (a.counts ? REQ_COUNTS : 0u) | (a.tier ? REQ_TIER : 0u) |
+            (a.min_delta != 0.0 ? REQ_DELTA : 0u);
     static std::atomic<bool> attr_set[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
