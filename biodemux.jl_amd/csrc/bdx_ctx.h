@@ -1,4 +1,4 @@
-// bdx_ctx.h — the context object behind the C-ABI (private; shared by bdx_abi.cpp and bdx_comm.cpp).
+// bdx_ctx.h — the context object behind the C-ABI (private; shared by bdx_abi.cpp, bdx_host.cpp and bdx_comm.cpp).
 #pragma once
 #include <cstdarg>
 #include <cstdio>
@@ -24,6 +24,27 @@ struct DevBuf {
     }
     void release() {
         if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// Page-locked host twin of DevBuf: grows to `bytes` + `slack` (room for somewhat larger calls to come)
+struct PinnedBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t bytes, size_t slack) {
+        if (bytes <= cap && p) return hipSuccess;
+        release();
+        hipError_t e = hipHostMalloc(&p, bytes + slack, hipHostMallocDefault);
+        if (e == hipSuccess)
+            cap = bytes + slack;
+        else
+            p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
         p = nullptr;
         cap = 0;
     }
@@ -133,14 +154,11 @@ struct bdx_ctx {
     bool scratch_clean[2] = {false, false};  // that half is known to hold zeros (cleared by the previous call's last launch)
     bool scratch_zeroed = false;  // the small-batch copy kernel has already cleared the filter kernels' scratch words
     int host_maxlen = 0;     // > 0 while bdx_classify_host runs an ordinary batch: its longest read (seen on the host)
-    void *h_stage = nullptr;  // page-locked staging for the verdict vectors of small batches
-    size_t h_stage_bytes = 0;
-    void *h_in = nullptr;     // page-locked staging for the bytes + offsets of small batches
-    void *h_back = nullptr;   // page-locked staging for the result vectors of large batches handed over in pageable memory (download_items)
-    size_t h_back_bytes = 0;
+    PinnedBuf h_stage;  // page-locked staging for the verdict vectors of small batches
+    PinnedBuf h_in;     // page-locked staging for the bytes + offsets of small batches
+    PinnedBuf h_back;   // page-locked staging for the result vectors of large batches handed over in pageable memory (download_items)
     hipEvent_t back_events[10] = {};
     bool back_events_made = false;
-    size_t h_in_bytes = 0;
     int64_t window_uploads = 0;
     int64_t band_launches = 0;  // (pass, exact-kernel launch) pairs that ran with the diagonal-band DP enabled
     std::vector<uint8_t> h_win;    // host staging of the compacted windows

@@ -29,110 +29,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 
-// ---- persistent worker pool --------------------------------------------------------------------------------------
-// The parallel sections of the reader (line index, packer) and of the writer (sizes, gather / iovecs, files) run on a
-// pool that belongs to the CALLING thread (the pipeline's reader and writer threads each keep their own for the whole
-// run) instead of starting and joining a set of std::threads per section: a 10 M-read run has ~140 sections per stage,
-// i.e. ~2 200 thread starts at a few tens of microseconds each on the coordinating thread.  Tasks are claimed with an
-// atomic counter; the caller works too.
-class WorkPool {
-  public:
-    ~WorkPool() {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            stop_ = true;
-        }
-        cv_start_.notify_all();
-        for (auto &t : th_) t.join();
-    }
-    template <class F>
-    void run(int n, F &&f) {
-        if (n <= 1) {
-            if (n == 1) f(0);
-            return;
-        }
-        while ((int)th_.size() < n - 1) th_.emplace_back([this]() { worker(); });
-        std::function<void(int)> job = std::ref(f);
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            job_ = &job;
-            njobs_ = n;
-            next_.store(0, std::memory_order_relaxed);
-            pending_ = n;
-            ++gen_;
-        }
-        cv_start_.notify_all();
-        work(job, n);
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_done_.wait(lk, [this]() { return pending_ == 0; });
-        job_ = nullptr;
-    }
-
-  private:
-    void work(const std::function<void(int)> &job, int n) {
-        int finished = 0;
-        for (;;) {
-            const int i = next_.fetch_add(1, std::memory_order_relaxed);
-            if (i >= n) break;
-            job(i);
-            ++finished;
-        }
-        if (finished) {
-            std::lock_guard<std::mutex> lk(mu_);
-            pending_ -= finished;
-            if (pending_ == 0) cv_done_.notify_all();
-        }
-    }
-    void worker() {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::function<void(int)> *job = nullptr;
-            int n = 0;
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_start_.wait(lk, [&]() { return stop_ || (gen_ != seen && job_ != nullptr); });
-                if (stop_) return;
-                seen = gen_;
-                job = job_;
-                n = njobs_;
-            }
-            // (the job object lives until pending_ reaches 0: a worker that arrives after the last task was claimed only
-            // reads the counter)
-            int finished = 0;
-            for (;;) {
-                const int i = next_.fetch_add(1, std::memory_order_relaxed);
-                if (i >= n) break;
-                (*job)(i);
-                ++finished;
-            }
-            if (finished) {
-                std::lock_guard<std::mutex> lk(mu_);
-                pending_ -= finished;
-                if (pending_ == 0) cv_done_.notify_all();
-            }
-        }
-    }
-    std::vector<std::thread> th_;
-    std::mutex mu_;
-    std::condition_variable cv_start_, cv_done_;
-    const std::function<void(int)> *job_ = nullptr;
-    std::atomic<int> next_{0};
-    int njobs_ = 0, pending_ = 0;
-    uint64_t gen_ = 0;
-    bool stop_ = false;
-};
-
-template <class F>
-static void parallel_for(int n, F &&f) {
-    static thread_local WorkPool pool;
-    pool.run(n, std::forward<F>(f));
-}
+#include "bdx_pool.h"
 
 extern "C" {
 

@@ -19,12 +19,13 @@ from .classification import filename_for
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "csrc", "bdx_io.cpp")
+_DEPS = (_SRC, os.path.join(_HERE, "csrc", "bdx_pool.h"))
 LIB_PATH = os.path.join(_HERE, "csrc", "libbdx_io.so")
 _lib = None
 
 
 def build(force: bool = False) -> str:
-    if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < os.path.getmtime(_SRC):
+    if force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(LIB_PATH) < os.path.getmtime(d) for d in _DEPS):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-o", LIB_PATH, _SRC, "-lz"])
     return LIB_PATH
 
