@@ -18,6 +18,16 @@
 
 thread_local std::string g_create_error;
 static std::atomic<long long> g_rejected_windows{0};  // summed over the contexts destroyed so far (see bdx_debug_rejected_windows_total)
+static thread_local std::string *t_launch_log = nullptr;  // the log of the classify call in progress on this thread
+
+bool bdx_launch_logging() { return t_launch_log != nullptr; }
+
+void bdx_note_launch(const char *family, const char *kernel, long long blocks, int threads, int tile, long long units, long long reads, int list) {
+    if (!t_launch_log) return;
+    char line[256];
+    snprintf(line, sizeof line, "%s\t%s\t%lld\t%d\t%d\t%lld\t%lld\t%d\n", family, kernel, blocks, threads, tile, units, reads, list);
+    *t_launch_log += line;
+}
 
 int bdx_fail(bdx_ctx *ctx, int code, const char *fmt, ...) {
     char buf[512];
@@ -2335,10 +2345,17 @@ static std::string call_path(const bdx_ctx *ctx, const CallPlan &p) {
 int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int64_t *d_seq_off, int64_t n_reads,
                             const bdx_outputs_t *d_out) {
     if (!ctx) return BDX_E_INVALID;
+    if (!ctx->log_host_call) ctx->launch_log.clear();
     if (n_reads < 0) return fail(ctx, BDX_E_INVALID, "n_reads is negative");
     if (n_reads == 0) return BDX_OK;
     if (!d_seq_bytes || !d_seq_off || !d_out) return fail(ctx, BDX_E_INVALID, "NULL device pointer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the launchers note what they enqueue into this call's log (test visibility: bdx_last_launches)
+    struct LogScope {
+        std::string *prev;
+        explicit LogScope(std::string *log) : prev(t_launch_log) { t_launch_log = log; }
+        ~LogScope() { t_launch_log = prev; }
+    } log_scope(&ctx->launch_log);
     const BdxDevOut o{d_out->bc1,      d_out->bc2,      d_out->keep_start, d_out->keep_end,   d_out->pass_start,
                       d_out->pass_end, d_out->pass_raw, d_out->pass_bc,    d_out->pass_score, d_out->pass_delta};
     BdxDevStats st{};
@@ -2520,6 +2537,17 @@ int64_t bdx_rejected_windows(bdx_ctx *ctx) {
 }
 
 int64_t bdx_debug_rejected_windows_total(void) { return (int64_t)g_rejected_windows.load(); }
+
+int64_t bdx_last_launches(const bdx_ctx *ctx, char *buf, int64_t cap) {
+    const std::string empty;
+    const std::string &log = ctx ? ctx->launch_log : empty;
+    if (buf && cap > 0) {
+        const size_t n = std::min((size_t)(cap - 1), log.size());
+        memcpy(buf, log.data(), n);
+        buf[n] = '\0';
+    }
+    return (int64_t)log.size();
+}
 
 int32_t bdx_launch_info(const bdx_ctx *ctx, bdx_launch_info_t *out) {
     if (!ctx || !out) return BDX_E_INVALID;

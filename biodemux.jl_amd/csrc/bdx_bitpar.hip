@@ -25,6 +25,7 @@
 // for any code, and lanes of the same read fetch the same symbol byte (LDS broadcast).  Pairs
 // are flattened (pair = read * B + barcode) so lanes stay busy for any B (96 = 1.5 waves).
 #include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -1229,6 +1230,11 @@ hipError_t launch_one(const BitparArgs &a, size_t lds, long long n_reads, hipStr
     if (blocks > tiles) blocks = tiles;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL((bdx_bitpar_kernel<BS, R, SEED, DIAG, NW, WL>), dim3((unsigned)blocks), dim3(BS), lds, stream, a);
+    if (bdx_launch_logging()) {
+        char name[96];
+        snprintf(name, sizeof name, "bdx_bitpar_kernel<%d, %d, %s, %s, %d, %d>", BS, R, SEED ? "true" : "false", DIAG ? "true" : "false", NW, WL);
+        bdx_note_launch("bitpar", name, blocks, BS, R, blocks, n_reads, a.in_list != nullptr ? 1 : 0);
+    }
     return hipGetLastError();
 }
 

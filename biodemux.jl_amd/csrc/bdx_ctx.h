@@ -181,6 +181,8 @@ struct bdx_ctx {
     DevBuf fq[BDX_FQ_SCRATCH];  // scratch of the device FASTQ pipeline (bdx_fastq.hip)
     std::string err;
     std::string path;
+    std::string launch_log;      // the classify kernels the last classify call enqueued (bdx_last_launches)
+    bool log_host_call = false;  // a bdx_classify_host call is in progress: its device calls add to one log
     int64_t launches = 0;
     int64_t last_blocks = 0;
 };

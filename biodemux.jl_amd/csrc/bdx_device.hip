@@ -21,6 +21,8 @@
 // (lane mod 32): conflict-free by construction even when lanes sit on different rows.
 // All DP arithmetic is int32 (see bdx_internal.h for the bound that makes that exact); the
 // accept/tighten/ambiguity decisions are IEEE doubles exactly as written in the reference.
+#include <cstdio>
+
 #include "bdx_core.h"
 
 #ifndef BDX_CLEAN_WAVES
@@ -425,6 +427,17 @@ hipError_t bdx_generic_set_lds_limit(size_t bytes) {
     return hipSuccess;
 }
 
+template <int BS, int REGM, bool CLEAN = false, bool UM = false>
+static void launch_generic_one(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const GenericArgs &a) {
+    hipLaunchKernelGGL((bdx_generic_kernel<BS, REGM, CLEAN, UM>), grid, block, lds, stream, a);
+    if (bdx_launch_logging()) {
+        char name[64];
+        snprintf(name, sizeof name, "bdx_generic_kernel<%d, %d, %s, %s>", BS, REGM, CLEAN ? "true" : "false", UM ? "true" : "false");
+        // (list mode: the grid strides over the list; else one read per thread)
+        bdx_note_launch("generic", name, grid.x, BS, BS, a.list ? (long long)grid.x : 0, a.n_reads, a.list ? 1 : 0);
+    }
+}
+
 hipError_t bdx_launch_generic(const BdxDevCfg &cfg, const BdxGenericPlan &plan, const uint8_t *d_seq,
                               const long long *d_off, long long n_reads, const BdxDevOut &out,
                               unsigned long long *d_counts, const uint32_t *d_cand0, const uint32_t *d_cand1,
@@ -470,28 +483,28 @@ hipError_t bdx_launch_generic(const BdxDevCfg &cfg, const BdxGenericPlan &plan, 
     const dim3 grid((unsigned)blocks), block((unsigned)plan.threads);
     if (plan.reg_rows == 24 && plan.threads == 256 && plan.clean) {
         if (plan.uniform_m)
-            hipLaunchKernelGGL((bdx_generic_kernel<256, 24, true, true>), grid, block, plan.lds_bytes, stream, a);
+            launch_generic_one<256, 24, true, true>(grid, block, plan.lds_bytes, stream, a);
         else
-            hipLaunchKernelGGL((bdx_generic_kernel<256, 24, true, false>), grid, block, plan.lds_bytes, stream, a);
+            launch_generic_one<256, 24, true, false>(grid, block, plan.lds_bytes, stream, a);
     } else if (plan.reg_rows == 32 && plan.threads == 256 && plan.clean) {
         if (plan.uniform_m)
-            hipLaunchKernelGGL((bdx_generic_kernel<256, 32, true, true>), grid, block, plan.lds_bytes, stream, a);
+            launch_generic_one<256, 32, true, true>(grid, block, plan.lds_bytes, stream, a);
         else
-            hipLaunchKernelGGL((bdx_generic_kernel<256, 32, true, false>), grid, block, plan.lds_bytes, stream, a);
+            launch_generic_one<256, 32, true, false>(grid, block, plan.lds_bytes, stream, a);
     } else if (plan.reg_rows == 24 && plan.threads == 256) {
-        hipLaunchKernelGGL((bdx_generic_kernel<256, 24>), grid, block, plan.lds_bytes, stream, a);
+        launch_generic_one<256, 24>(grid, block, plan.lds_bytes, stream, a);
     } else if (plan.reg_rows == 32 && plan.threads == 256) {
-        hipLaunchKernelGGL((bdx_generic_kernel<256, 32>), grid, block, plan.lds_bytes, stream, a);
+        launch_generic_one<256, 32>(grid, block, plan.lds_bytes, stream, a);
     } else if (plan.band_roll) {  // barcodes beyond 32 rows in the clean class: the rolling diagonal band (sg_band_roll)
         switch (plan.threads) {
             case 256:
-                hipLaunchKernelGGL((bdx_generic_kernel<256, 0, true>), grid, block, plan.lds_bytes, stream, a);
+                launch_generic_one<256, 0, true>(grid, block, plan.lds_bytes, stream, a);
                 break;
             case 128:
-                hipLaunchKernelGGL((bdx_generic_kernel<128, 0, true>), grid, block, plan.lds_bytes, stream, a);
+                launch_generic_one<128, 0, true>(grid, block, plan.lds_bytes, stream, a);
                 break;
             case 64:
-                hipLaunchKernelGGL((bdx_generic_kernel<64, 0, true>), grid, block, plan.lds_bytes, stream, a);
+                launch_generic_one<64, 0, true>(grid, block, plan.lds_bytes, stream, a);
                 break;
             default:
                 return hipErrorInvalidValue;
@@ -499,13 +512,13 @@ hipError_t bdx_launch_generic(const BdxDevCfg &cfg, const BdxGenericPlan &plan, 
     } else {
         switch (plan.threads) {
             case 256:
-                hipLaunchKernelGGL((bdx_generic_kernel<256, 0>), grid, block, plan.lds_bytes, stream, a);
+                launch_generic_one<256, 0>(grid, block, plan.lds_bytes, stream, a);
                 break;
             case 128:
-                hipLaunchKernelGGL((bdx_generic_kernel<128, 0>), grid, block, plan.lds_bytes, stream, a);
+                launch_generic_one<128, 0>(grid, block, plan.lds_bytes, stream, a);
                 break;
             case 64:
-                hipLaunchKernelGGL((bdx_generic_kernel<64, 0>), grid, block, plan.lds_bytes, stream, a);
+                launch_generic_one<64, 0>(grid, block, plan.lds_bytes, stream, a);
                 break;
             default:
                 return hipErrorInvalidValue;

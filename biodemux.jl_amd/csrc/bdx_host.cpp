@@ -368,12 +368,15 @@ int32_t bdx_classify_host(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t 
     const int64_t total = seq_off[n_reads] - base;
     if (total < 0) return bdx_fail(ctx, BDX_E_INVALID, "seq_off is not non-decreasing");
     // what the host has seen of this batch (the longest read; the window upload's per-read windows) is lent to the launch
-    // plan for this call only, whichever way it ends
+    // plan for this call only, whichever way it ends; the launch log (bdx_last_launches) spans all of its device calls
+    ctx->launch_log.clear();
+    ctx->log_host_call = true;
     struct HostFactsReset {
         bdx_ctx *c;
         ~HostFactsReset() {
             c->host_maxlen = c->virt_maxlen = 0;
             c->dev.vlen = c->dev.vlo = nullptr;
+            c->log_host_call = false;
         }
     } reset{ctx};
     {

@@ -279,6 +279,11 @@ hipError_t bdx_launch_generic(const BdxDevCfg &cfg, const BdxGenericPlan &plan, 
                               const uint8_t *d_wcnt1 = nullptr, const uint32_t *d_list = nullptr,
                               const unsigned int *d_list_count = nullptr, const BdxDevStats *stats = nullptr,
                               const BdxTierArgs *tier = nullptr, const double *tier_slo = nullptr, uint32_t *zero_words = nullptr);
+// Launch log of the classify call in progress on this thread (bdx_last_launches; bdx_abi.cpp): the launchers note every
+// classify kernel they enqueue while bdx_launch_logging() holds.  tile: reads per tile; units: what the tiles are dealt
+// over (0: no tile loop); list: `reads` is the capacity of a device-side list.
+bool bdx_launch_logging();
+void bdx_note_launch(const char *family, const char *kernel, long long blocks, int threads, int tile, long long units, long long reads, int list);
 // scratch words of a classify call (tile queues, hand-over / tier list lengths): bytes [64, 512) of one half of the context's
 // 1 KiB scratch block; the halves alternate between calls and a call's last launch clears the other one (bdx_abi.cpp)
 #define BDX_SCRATCH_WORDS 112

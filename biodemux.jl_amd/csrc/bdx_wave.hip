@@ -1786,6 +1786,13 @@ hipError_t launch_wave(const WaveArgs &a0, size_t lds, int waves, long long bloc
         if (dev >= 0) attr_set[dev].store(true, std::memory_order_release);
     }
     hipLaunchKernelGGL((bdx_wave_kernel<RW, TF, NV, Q, SPLIT, KB, NW, MG, KEND, GEN, WINM>), dim3((unsigned)blocks), dim3(64 * waves), lds, stream, a);
+    if (bdx_launch_logging()) {
+        const auto tf = [](bool b) { return b ? "true" : "false"; };
+        char name[128];
+        snprintf(name, sizeof name, "bdx_wave_kernel<%d, %d, %d, %d, %s, %d, %d, %s, %d, %s, %s>", RW, TF, NV, Q, tf(SPLIT), KB, NW, tf(MG), KEND,
+                 tf(GEN), tf(WINM));
+        bdx_note_launch(KB > 0 ? "pairs" : "wave", name, blocks, 64 * waves, RW, blocks * waves, a.n_reads, a.n_dev != nullptr ? 1 : 0);
+    }
     return hipGetLastError();
 }
 

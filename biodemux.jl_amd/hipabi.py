@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     # DemuxStats histograms (summary = true), collected on the device
     "bdx_stats_shape", "bdx_get_stats",
     "bdx_window_uploads", "bdx_band_launches", "bdx_wave_launches", "bdx_pair_launches", "bdx_pipelined_calls", "bdx_staged_downloads", "bdx_last_list_reads", "bdx_rejected_windows",
-    "bdx_debug_rejected_windows_total",
+    "bdx_debug_rejected_windows_total", "bdx_last_launches",
     # device FASTQ pipeline (bdx_fastq.hip)
     "bdx_fq_index_device", "bdx_fq_pack_device", "bdx_fq_gather_device",
 ]
@@ -231,6 +231,8 @@ def load_library(path: Optional[str] = None):
     L.bdx_rejected_windows.argtypes = [vp]
     L.bdx_debug_rejected_windows_total.restype = C.c_int64
     L.bdx_debug_rejected_windows_total.argtypes = []
+    L.bdx_last_launches.restype = C.c_int64
+    L.bdx_last_launches.argtypes = [vp, C.c_char_p, C.c_int64]
     L.bdx_fq_index_device.restype = C.c_int32
     L.bdx_fq_index_device.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, vp, vp, C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int64)]
@@ -519,6 +521,13 @@ class HipClassifier:
         return int(self.lib.bdx_pair_launches(self.h))
 
     @property
+    def last_launches(self) -> list:
+        """The classify kernels the last classify call enqueued, one dict per launch (bdx_last_launches): family, kernel (the
+        instantiation as the code object names it), blocks, threads, tile (reads per tile), units (waves or workgroups the
+        tiles are dealt over; 0: no tile loop), reads (list: the capacity of the device-side list it walks), list."""
+        return parse_launch_log(self.lib, self.h)
+
+    @property
     def window_uploads(self) -> int:
         """classify() calls that uploaded only each read's column window (long reads, short windows)."""
         return int(self.lib.bdx_window_uploads(self.h))
@@ -533,6 +542,23 @@ class HipClassifier:
         d = {k: getattr(li, k) for k, _ in li._fields_}
         d["filter_used"] = FILTER_NAMES.get(d["filter_used"], str(d["filter_used"]))
         return d
+
+
+LAUNCH_FIELDS = ("family", "kernel", "blocks", "threads", "tile", "units", "reads", "list")
+
+
+def parse_launch_log(lib, h) -> list:
+    """bdx_last_launches of context `h` as a list of dicts (LAUNCH_FIELDS; integers but for family and kernel)."""
+    n = int(lib.bdx_last_launches(h, None, 0))
+    buf = C.create_string_buffer(n + 1)
+    lib.bdx_last_launches(h, buf, n + 1)
+    out = []
+    for line in buf.value.decode().splitlines():
+        f = line.split("\t")
+        if len(f) != len(LAUNCH_FIELDS):
+            raise BdxError(f"malformed launch log line: {line!r}")
+        out.append({k: (v if i < 2 else int(v)) for i, (k, v) in enumerate(zip(LAUNCH_FIELDS, f))})
+    return out
 
 
 def pack_reads(seqs) -> tuple:

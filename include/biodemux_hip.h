@@ -341,6 +341,15 @@ int64_t bdx_last_list_reads(bdx_ctx *ctx);
 int64_t bdx_rejected_windows(bdx_ctx *ctx);
 int64_t bdx_debug_rejected_windows_total(void);
 
+/* The classify kernels the LAST classify call enqueued (a bdx_classify_host call: all of its chunks), as the launchers
+ * saw them — a test-visibility log like the counters above; it adds no synchronisation.  One line per launch, fields
+ * separated by tabs: family (wave | pairs | bitpar | generic), the instantiation as the code object names it (e.g.
+ * "bdx_wave_kernel<32, 20, 5, 8, false, 0, 0, false, 0, false, false>"), workgroups, threads per workgroup, reads per
+ * tile, the units the tiles are dealt over (waves of the grid for wave / pairs, workgroups for bitpar; 0: no tile loop),
+ * the reads it was given and a list flag (1: it walks a device-side list of at most that many reads).
+ * Copies at most cap - 1 bytes and a NUL into buf (buf may be NULL when cap is 0); returns the length of the whole log. */
+int64_t bdx_last_launches(const bdx_ctx *ctx, char *buf, int64_t cap);
+
 typedef struct {
     int32_t threads_per_block;
     int32_t lds_bytes_per_block;

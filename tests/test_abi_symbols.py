@@ -53,3 +53,36 @@ def test_config_validation_errors_before_device():
     h = ctypes.c_void_p()
     assert lib.bdx_create(ctypes.byref(c), ctypes.byref(h)) == -1
     assert b"trim_side must be 3 or 5" in lib.bdx_last_error(None)
+
+
+def test_last_launches_binding_parses_an_empty_log():
+    """bdx_last_launches is declared, bound and exported; without a context (or before any call) the log is empty and
+    HipClassifier.last_launches parses it to an empty list — a malformed line is refused, not skipped."""
+    assert "bdx_last_launches" in _declared_symbols() and "bdx_last_launches" in hipabi.ABI_SYMBOLS
+    lib = hipabi.load_library()
+    assert lib.bdx_last_launches(None, None, 0) == 0
+    buf = ctypes.create_string_buffer(8)
+    assert lib.bdx_last_launches(None, buf, len(buf)) == 0 and buf.value == b""
+
+    class _NoContext:
+        pass
+
+    probe = _NoContext()
+    probe.lib, probe.h = lib, None
+    assert hipabi.HipClassifier.last_launches.fget(probe) == []
+
+    class _OneLine:
+        def __init__(self, text):
+            self.text = text.encode()
+
+        def bdx_last_launches(self, h, buf, cap):
+            if buf is not None and cap > 0:
+                ctypes.memmove(buf, self.text, min(cap - 1, len(self.text)))
+            return len(self.text)
+
+    line = "wave\tbdx_wave_kernel<32, 20, 5, 8, false, 0, 0, false, 0, false, false>\t16\t512\t32\t128\t3000\t0\n"
+    got = hipabi.parse_launch_log(_OneLine(line), None)
+    assert got == [dict(family="wave", kernel="bdx_wave_kernel<32, 20, 5, 8, false, 0, 0, false, 0, false, false>", blocks=16,
+                        threads=512, tile=32, units=128, reads=3000, list=0)]
+    with pytest.raises(hipabi.BdxError, match="malformed"):
+        hipabi.parse_launch_log(_OneLine("wave\tbdx_wave_kernel<8>\t1\n"), None)
