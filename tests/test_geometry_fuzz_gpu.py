@@ -15,15 +15,13 @@ each call enqueued: every case asserts that the persistent stages it steers walk
 workgroup, every family asserts the union of the shapes it reached, and every name must exist in the code object."""
 import functools
 import os
-import re
-import struct
 
 import numpy as np
 import pytest
 
 import fuzz
 import helpers as H
-from biodemux_jl_amd import hipabi
+from kernel_lattice import code_object_kernels
 from biodemux_jl_amd.classification import DemuxStats
 
 pytestmark = pytest.mark.gpu
@@ -48,73 +46,7 @@ def _need_gpu():
     assert os.path.exists(H.bdx.LIB_PATH), "HIP extension missing: run __graft_entry__.build()"
 
 
-# ---- the kernels the code object holds ----
-def _demangle(sym: str) -> str:
-    """Itanium names of this library's kernels -> "name<a, b, ...>" (integer and bool template arguments, the spelling of
-    bdx_last_launches); anything else comes back as it is."""
-    m = re.match(r"_ZN12_GLOBAL__N_1(\d+)|_Z(\d+)", sym)
-    if not m:
-        return sym
-    n = int(m.group(1) or m.group(2))
-    name = sym[m.end():m.end() + n]
-    rest = sym[m.end() + n:]
-    if not rest.startswith("I"):
-        return name
-    args = []
-    for t, neg, v in re.findall(r"L([ibj])(n?)(\d+)E", rest[1:rest.index("EE") + 1] if "EE" in rest else rest[1:]):
-        args.append(("true" if v == "1" else "false") if t == "b" else ("-" if neg else "") + v)
-    return f"{name}<{', '.join(args)}>"
-
-
-@functools.lru_cache(maxsize=1)
-def code_object_kernels() -> frozenset:
-    """Every kernel of the gfx950 code objects in the built library: its .hip_fatbin section holds one offload bundle per
-    translation unit (what tools/kernel_regs.sh unbundles object by object); the kernels are the ELF symbols with a
-    kernel descriptor (NAME.kd)."""
-    data = open(hipabi.LIB_PATH, "rb").read()
-    shoff, = struct.unpack_from("<Q", data, 0x28)
-    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", data, 0x3A)
-    secs = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + k * shentsize) for k in range(shnum)]
-    names_off = secs[shstrndx][4]
-
-    def sec_name(s):
-        return data[names_off + s[0]: data.index(b"\0", names_off + s[0])].decode()
-
-    fat = [s for s in secs if sec_name(s) == ".hip_fatbin"]
-    assert len(fat) == 1, "no .hip_fatbin section in the library"
-    fat = data[fat[0][4]: fat[0][4] + fat[0][5]]
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    kernels = set()
-    pos = fat.find(magic)
-    n_objects = 0
-    while pos >= 0:
-        n_entries, = struct.unpack_from("<Q", fat, pos + 24)
-        p = pos + 32
-        for _ in range(n_entries):
-            off, size, tlen = struct.unpack_from("<QQQ", fat, p)
-            triple = fat[p + 24: p + 24 + tlen].decode()
-            p += 24 + tlen
-            if "gfx950" not in triple:
-                continue
-            co = fat[pos + off: pos + off + size]
-            assert co[:4] == b"\x7fELF", f"code object for {triple} is not an ELF (compressed bundle?)"
-            n_objects += 1
-            c_shoff, = struct.unpack_from("<Q", co, 0x28)
-            c_entsize, c_num = struct.unpack_from("<HH", co, 0x3A)
-            csecs = [struct.unpack_from("<IIQQQQIIQQ", co, c_shoff + k * c_entsize) for k in range(c_num)]
-            for s in csecs:
-                if s[1] not in (2, 11):  # SHT_SYMTAB, SHT_DYNSYM
-                    continue
-                so = csecs[s[6]][4]
-                for j in range(s[5] // 24):
-                    st_name, = struct.unpack_from("<I", co, s[4] + j * 24)
-                    nm = co[so + st_name: co.index(b"\0", so + st_name)].decode()
-                    if nm.endswith(".kd"):
-                        kernels.add(_demangle(nm[:-3]))
-        pos = fat.find(magic, pos + len(magic))
-    assert n_objects >= 6 and kernels, (n_objects, len(kernels))
-    return frozenset(kernels)
-
+# ---- the kernels the code object holds (kernel_lattice.py) ----
 
 def test_code_object_reader_sees_the_instantiation_lattice():
     ks = code_object_kernels()
