@@ -420,7 +420,7 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
     LDS int *stn = (LDS int *)(wbase + O_STN);
     LDS uint32_t *img2 = (LDS uint32_t *)(wbase + O_IMG2);
     LDS uint32_t *img4 = img2 + ((nvec_cap + 2 + 3) & ~3);  // u32[2 nvec_cap + 6]: 4-bit image (16-byte aligned)
-    LDS uint32_t *hq = img4 + ((2 * nvec_cap + 6 + 3) & ~3);  // u32[HQ]: seed hits: flat position << 16 | key (pairs mode: sweep entries)
+    LDS uint32_t *hq = img4 + ((2 * nvec_cap + 6 + 3) & ~3);  // u32[HQ]: seed hits: group << 5 | bit of the lane's hit word; general forms: flat position << 16 | key (pairs mode: sweep entries)
     LDS uint32_t *recq = hq + HQ;                             // u32[SQ]: the tile's records in use (slot numbers) = its sweeps
     const int cwt = a.cw[0] + a.cw[1];                        // split mode: candidate mask words per read (pass 0 then pass 1)
     LDS uint32_t *cand = recq + SQ;                           // u32[RW][cwt] (split mode)
@@ -1108,9 +1108,8 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
             }
         } else {
             constexpr uint32_t AMASK = ((1u << (2 * Q - 5)) - 1u) << 2;
-            constexpr uint32_t KMASK = (1u << (2 * Q)) - 1u;
-            uint32_t amask = AMASK, kmask = KMASK, emask = 0x55555555u;
-            asm volatile("" : "+v"(amask), "+v"(kmask), "+v"(emask));  // (in vector registers: a literal or scalar operand slows the AND down)
+            uint32_t amask = AMASK, emask = 0x55555555u;
+            asm volatile("" : "+v"(amask), "+v"(emask));  // (in vector registers: a literal or scalar operand slows the AND down)
             // ranged single-pass configs whose window is much shorter than the read (ref_search_range = "1:60"): only the groups
             // of sixteen positions that overlap each read's window are scanned — lane = (read, group of its window) instead of
             // lane = group of the flat image.  A tile with a window longer than planned (a read beyond the length hint) takes
@@ -1132,79 +1131,126 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                 if (__builtin_amdgcn_ballot_w64(over)) gpr = 0;
             }
             const int nscan = BDX_DBG(8) ? 0 : (gpr > 0 ? nr * npw * gpr : nvec);
-            for (int g0i = 0; g0i < nscan; g0i += 64) {
-                int g = g0i + lane;
-                bool ong = g < nscan;
-                uint32_t keep = emask;  // positions of the group that are this lane's to report (position i: bit 2 i, as the hits below)
-                if (gpr > 0) {
-                    const int i = g0i + lane;
-                    const int tw = ong ? (int)(((uint32_t)i * (uint32_t)a.scan_gpr_inv) >> 16) : 0;  // (read, window) number
-                    const int t = npw == 2 ? tw >> 1 : tw, which = npw == 2 ? tw & 1 : 0;
-                    int s0 = fb[t] + wwin[(2 * which) * RW + t];
-                    const int f1 = fb[t + 1];
-                    g = (s0 >> 4) + (i - tw * gpr);
-                    if (which) {  // positions the lanes of the read's first window report already
-                        const int c0 = (((fb[t] + wwin[t]) >> 4) + gpr) << 4;
-                        const int a0 = fb[t] + wwin[t];
-                        if (s0 >= a0 && s0 < c0) s0 = c0;
+            // The scan runs in rounds of KT trips (a trip: 64 groups, one per lane); a lane keeps the hit word of each of its
+            // trips in a register and the round appends once (one round per tile in the NV = 5 forms): the levels of the
+            // count-and-prefix and the iterations of the write loop follow the fullest lane's hits over the ROUND, not the sum of
+            // every trip's fullest lane.
+            // (the general forms — dual, ranged, known-trim — have no registers to spare, neither for the hit words nor for the
+            // resolve's fetch of the key: a trip per round, and the write loop puts position and key into the entry)
+            constexpr int KT = GEN ? 1 : 5;
+            constexpr uint32_t KMASK = (1u << (2 * Q)) - 1u;
+            for (int r0i = 0; r0i < nscan; r0i += 64 * KT) {
+                uint32_t hm[KT];
+                uint32_t w0 = 0, w1 = 0, gp = 0;  // (KT = 1: the trip's window words and (flat position 16 g) << 16)
+#pragma unroll
+                for (int u = 0; u < KT; ++u) {
+                    hm[u] = 0u;
+                    const int g0i = r0i + 64 * u;
+                    if (g0i >= nscan) continue;  // (wave-uniform)
+                    int g = g0i + lane;
+                    bool ong = g < nscan;
+                    uint32_t keep = emask;  // positions of the group that are this lane's to report (position i: bit 2 i, as the hits below)
+                    if (gpr > 0) {
+                        const int i = g0i + lane;
+                        const int tw = ong ? (int)(((uint32_t)i * (uint32_t)a.scan_gpr_inv) >> 16) : 0;  // (read, window) number
+                        const int t = npw == 2 ? tw >> 1 : tw, which = npw == 2 ? tw & 1 : 0;
+                        int s0 = fb[t] + wwin[(2 * which) * RW + t];
+                        const int f1 = fb[t + 1];
+                        g = (s0 >> 4) + (i - tw * gpr);
+                        if (which) {  // positions the lanes of the read's first window report already
+                            const int c0 = (((fb[t] + wwin[t]) >> 4) + gpr) << 4;
+                            const int a0 = fb[t] + wwin[t];
+                            if (s0 >= a0 && s0 < c0) s0 = c0;
+                        }
+                        const int below = s0 - 16 * g, above = f1 - 16 * g;  // bits < below lie in front of the window, bits >= above in the next read
+                        ong = ong && above > 0 && g < nvec;
+                        const int b2 = below > 0 ? 2 * (below > 16 ? 16 : below) : 0, a2 = above < 16 ? 2 * (above < 0 ? 0 : above) : 32;
+                        keep = (b2 >= 32 ? 0u : 0xFFFFFFFFu << b2) & (a2 >= 32 ? 0xFFFFFFFFu : (1u << a2) - 1u) & 0x55555555u;
                     }
-                    const int below = s0 - 16 * g, above = f1 - 16 * g;  // bits < below lie in front of the window, bits >= above in the next read
-                    ong = ong && above > 0 && g < nvec;
-                    const int b2 = below > 0 ? 2 * (below > 16 ? 16 : below) : 0, a2 = above < 16 ? 2 * (above < 0 ? 0 : above) : 32;
-                    keep = (b2 >= 32 ? 0u : 0xFFFFFFFFu << b2) & (a2 >= 32 ? 0xFFFFFFFFu : (1u << a2) - 1u) & 0x55555555u;
-                }
-                uint32_t hits = 0;
-                uint32_t w0 = 0, w1 = 0;
-                if (ong) {
-                    w0 = img2[g];
-                    w1 = img2[g + 1];
-                    const uint32_t wm = __builtin_amdgcn_alignbit(w1, w0, 16);  // bases 8 .. 23 of the group's window
-                    uint32_t Wk[16];
+                    if (ong) {
+                        uint32_t hits = 0;
+                        w0 = img2[g];
+                        w1 = img2[g + 1];
+                        gp = (uint32_t)g << 20;
+                        const uint32_t wm = __builtin_amdgcn_alignbit(w1, w0, 16);  // bases 8 .. 23 of the group's window
+                        uint32_t Wk[16];
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) Wk[i] = i == 0 ? w0 : (i <= 8 ? w0 >> (2 * i) : wm >> (2 * (i - 8)));
+                        for (int i2 = 0; i2 < 16; ++i2) Wk[i2] = i2 == 0 ? w0 : (i2 <= 8 ? w0 >> (2 * i2) : wm >> (2 * (i2 - 8)));
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        uint32_t word[8], addr[8];
+                        for (int h = 0; h < 2; ++h) {
+                            uint32_t word[8], addr[8];
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) addr[i] = (Wk[8 * h + i] >> 3) & amask;
-                        lds_read8(word, addr);
-                        lds_wait8(word);
+                            for (int i2 = 0; i2 < 8; ++i2) addr[i2] = (Wk[8 * h + i2] >> 3) & amask;
+                            lds_read8(word, addr);
+                            lds_wait8(word);
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) hits = __builtin_amdgcn_alignbit(word[i] >> (Wk[8 * h + i] & 31u), hits, 2);
+                            for (int i2 = 0; i2 < 8; ++i2) hits = __builtin_amdgcn_alignbit(word[i2] >> (Wk[8 * h + i2] & 31u), hits, 2);
+                        }
+                        // (two bits per position: its hit at bit 2 i, the next bit of its probed word at 2 i + 1 — masked off)
+                        hm[u] = hits & keep;
                     }
-                    // (two bits per position: its hit at bit 2 i, the next bit of its probed word at 2 i + 1 — masked off; the even
-                    // bits give the append the key's shift 2 i directly)
-                    hits &= keep;
                 }
+                // the round's hits of a lane as words of two trips each: trip 2 j on the even bits of word j, trip 2 j + 1 on
+                // the odd ones — bit b of word j is position b >> 1 of group r0i + 128 j + 64 (b & 1) + lane
+                constexpr int KW = (KT + 1) / 2;
+                uint32_t cw[KW];
+#pragma unroll
+                for (int j = 0; j < KW; ++j) cw[j] = hm[2 * j] | (2 * j + 1 < KT ? hm[2 * j + 1] << 1 : 0u);
+                uint32_t nl = 0;
+#pragma unroll
+                for (int j = 0; j < KW; ++j) nl += (uint32_t)__builtin_popcount(cw[j]);
                 // append by count and prefix: every lane's hits go to a run of their own, the lanes' runs in lane order.  The
                 // lane's first entry is nhq + the hits of the lanes below it, summed as one ballot per level j of the fullest
                 // lane (lanes with more than j hits; mbcnt accumulates), then each lane writes its run in a loop of its own.
+                // An entry is (group r0i + 128 j + lane) << 5 | b: the resolve, one lane per hit, turns it into the flat
+                // position and fetches the key from the image — the serial loop here only walks the bits.
                 // The resolve below does not depend on the order of the entries in hq: every hit is looked up on its own, a
                 // record is keyed by (barcode, first diagonal) whichever hit opens it, its diagonal bits are OR-ed in, and each
                 // record's window is lossless on its own (phase 3).
-                unsigned long long mk = __builtin_amdgcn_ballot_w64(hits != 0u);
+                unsigned long long mk = __builtin_amdgcn_ballot_w64(nl != 0u);
                 if (mk) {
-                    const uint32_t nl = (uint32_t)__builtin_popcount(hits);
                     uint32_t k = (uint32_t)nhq;
                     for (uint32_t j = 1; mk; ++j) {
                         k = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, k));
                         nhq += (int)__builtin_popcountll(mk);
                         mk = __builtin_amdgcn_ballot_w64(nl > j);
                     }
-                    // overflow: nhq > HQ sends the whole tile to the list (hq_ok below), so a trip that runs over writes
+                    // overflow: nhq > HQ sends the whole tile to the list (hq_ok below), so a round that runs over writes
                     // nothing, and every entry written has k < HQ
-                    if (nhq <= HQ && hits) {
-                        const uint32_t gp = (uint32_t)g << 20;  // (flat position 16 g) << 16
+                    if (nhq <= HQ && nl) {
+                        // the words in the order the loop takes them, with the entry code of each: an empty middle word
+                        // gives way to the last one here, an emptied first word to the next one at the top of the loop (the
+                        // words left behind are stale: the count ends the loop)
+                        uint32_t cd[KW];
+#pragma unroll
+                        for (int j = 0; j < KW; ++j) cd[j] = (uint32_t)(r0i + 128 * j + lane) << 5;
+                        static_assert(KW == 1 || KW == 3, "the hand-over is written for three words");
+                        if constexpr (KW == 3) {
+                            if (cw[1] == 0u) {
+                                cw[1] = cw[2];
+                                cd[1] = cd[2];
+                            }
+                        }
                         LDS uint32_t *dst = hq + k;
                         do {
-                            const uint32_t i2 = (uint32_t)__builtin_ctz(hits);  // 2 i for position i of the group
-                            hits &= hits - 1u;
-                            const uint32_t ph = gp + (i2 << 15), kw = __builtin_amdgcn_alignbit(w1, w0, i2);
-                            // (16-bit keys: the two low bytes of the key word under the position, one v_perm)
-                            *dst = Q == 8 ? __builtin_amdgcn_perm(ph, kw, 0x07060100u) : ph | (kw & kmask);
+                            const bool z = cw[0] == 0u;
+#pragma unroll
+                            for (int j = 0; j < KW - 1; ++j) {
+                                cw[j] = z ? cw[j + 1] : cw[j];
+                                cd[j] = z ? cd[j + 1] : cd[j];
+                            }
+                            const uint32_t b = (uint32_t)__builtin_ctz(cw[0]);  // (KT = 1: 2 i for position i of the group)
+                            cw[0] &= cw[0] - 1u;
+                            if constexpr (KT == 1) {
+                                const uint32_t ph = gp + (b << 15), kw = __builtin_amdgcn_alignbit(w1, w0, b);
+                                // (16-bit keys: the two low bytes of the key word under the position, one v_perm)
+                                *dst = Q == 8 ? __builtin_amdgcn_perm(ph, kw, 0x07060100u) : ph | (kw & KMASK);
+                            } else {
+                                *dst = cd[0] + b;
+                            }
                             __builtin_amdgcn_sched_barrier(0);  // (the address steps after the write: in place, no copy)
                             ++dst;
-                        } while (hits);
+                        } while (KT == 1 ? cw[0] != 0u : --nl != 0u);
                     }
                 }
             }
@@ -1231,8 +1277,15 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                 int new0 = -1, new1 = -1;  // record slots this lane opened
                 if (k < nh) {
                     const uint32_t h = hq[k];
-                    const int pos = (int)(h >> 16);
-                    const uint32_t key = h & 0xFFFFu;
+                    int pos = (int)(h >> 16);  // (the general forms: flat position << 16 | key)
+                    uint32_t key = h & 0xFFFFu;
+                    if constexpr (!GEN) {
+                        // the entry: (group of the even trip) << 5 | b, b = 2 x position in the group + (odd trip: 64 groups on)
+                        const int hg = (int)(h >> 5) + (int)((h & 1u) << 6);
+                        const uint32_t i2 = h & 30u;  // 2 x position in the group: the key's shift in the group's window
+                        pos = 16 * hg + (int)(i2 >> 1);
+                        key = __builtin_amdgcn_alignbit(img2[hg + 1], img2[hg], i2) & ((1u << (2 * Q)) - 1u);
+                    }
                     int t;
                     bool ok = true;
                     if (SCAT) {  // (slots of equal size)

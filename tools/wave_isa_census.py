@@ -7,9 +7,10 @@
 
 Prints the resource lines (VGPRs, SGPRs, scratch), the loops of the function (found from the backward branches), the
 static v_readlane / v_writelane inside the per-tile loop (all of them, and those on the registers the compiler spills
-SGPRs into: the VGPRs some v_writelane writes), and the VALU counts of the seed scan's trip loop, of the loops nested in
-it (the hit append) and of the first sweep loop.  Static counts: what one pass through a loop's body issues; how often
-each body runs depends on the data (the per-trip lines show it for L layers / hits of the fullest lane).
+SGPRs into: the VGPRs some v_writelane writes), and the VALU counts of the seed scan's round loop (the trips of a round
+are unrolled in it: five in the headline form, one round per tile), of the loops nested in it (the hit append, once per
+round) and of the first sweep loop.  Static counts: what one pass through a loop's body issues; how often each body runs
+depends on the data (the per-round lines show it for L layers / hits of the fullest lane over the round).
 """
 from __future__ import annotations
 
@@ -119,9 +120,10 @@ def main() -> None:
     total_rw = sum(1 for l in body if re.match(r"\s+v_(readlane|writelane)_b32", l))
     print("readlane/writelane  function %d, tile loop %d (on spill VGPRs %s: %d)" % (total_rw, len(rw_all), ",".join(sorted(spill_v)) or "none", len(rw_spill)))
 
-    # the seed scan's trip loop and its hit append: the append's write loop is the first innermost loop with a v_ffbl_b32 and
-    # an LDS write; the trip is the smallest loop around it that also holds the bitmap probes; the loops in the trip with a
-    # v_mbcnt or that write loop are the append's per-layer loops (they run once per layer: L = hits of the fullest lane)
+    # the seed scan's round loop and its hit append: the append's write loop is the first innermost loop with a v_ffbl_b32 and
+    # an LDS write; the round is the smallest loop around it that also holds the bitmap probes (sixteen per unrolled trip); the
+    # loops in the round with a v_mbcnt or that write loop are the append's per-layer loops (they run once per layer: L = hits
+    # of the fullest lane over the round)
     inner = [x for x in lp if tile[0] <= x[0] and x[1] <= tile[1] and x != tile]
     def nested(o):
         return [x for x in inner if o[0] <= x[0] and x[1] <= o[1] and x != o]
@@ -137,19 +139,20 @@ def main() -> None:
     for x in inner:
         depth = sum(1 for y in inner if y[0] <= x[0] and x[1] <= y[1] and y != x)
         v, s_, d = count(body, x[0], x[1], [(y[0], y[1]) for y in nested(x)])
-        tag = "scan trip" if x == trip else ("append, per layer" if x in layer else "")
+        tag = "scan round" if x == trip else ("append, per layer" if x in layer else "")
         print("%-12s %6d-%-6d  %5d %5d %4d  %s%s" % (x[2], x[0], x[1], v, s_, d, "  " * depth, tag))
     if trip:
         tv, ts, _ = count(body, trip[0], trip[1], [(y[0], y[1]) for y in layer])
         per = [count(body, y[0], y[1]) for y in layer]
         lv, ls = sum(v for v, _, _ in per), sum(s_ for _, s_, _ in per)
         print()
-        print("scan trip %s without the per-layer append loops: VALU %d, SALU %d" % (trip[2], tv, ts))
+        ntrips = has(trip, r"ds_read_b32") // 16
+        print("scan round %s (%d trips unrolled: %d probes) without the per-layer append loops: VALU %d, SALU %d" % (trip[2], ntrips, 16 * ntrips, tv, ts))
         for y, (v, s_, _) in zip(layer, per):
             print("append loop %s: VALU %d, SALU %d per layer" % (y[2], v, s_))
-        for L in (1, 2, 3):
-            print("trip with hits, L = %d layers: %d + %d = %d VALU, %d + %d SALU" % (L, tv, L * lv, tv + L * lv, ts, L * ls))
-    sweeps = [x for x in inner if count(body, x[0], x[1])[0] > 300]
+        for L in (1, 3, 5, 7):
+            print("round with hits, L = %d layers: %d + %d = %d VALU, %d + %d SALU" % (L, tv, L * lv, tv + L * lv, ts, L * ls))
+    sweeps = [x for x in inner if count(body, x[0], x[1])[0] > 300 and (not trip or x[0] > trip[1])]
     if sweeps:
         sw = min(sweeps, key=lambda x: (x[0], x[1] - x[0]))
         sw = min((x for x in sweeps if x[0] == sweeps[0][0]), key=lambda x: x[1] - x[0])
