@@ -144,7 +144,10 @@ typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
 // differences between the bytes and the bytes their 3-bit index stands for (0 <=> every byte is A, C, G, T or N).
 // idx = (byte >> 1) & 7:  A 0, C 1, T 2, G 3, N 7;  code = idx for ACGT, 4 ("other") for everything else.
 // EXACT: bytes that alias an index (any byte that is not the index's own letter) get code 4 as well.
-template <bool EXACT>
+// DOT: the four 2-bit codes of a word are gathered by one dot product (code_k * 4^k summed: v_dot4_u32_u8 with the weights
+// 1, 4, 16, 64) instead of three shift-or steps; the weights live in a register, which only the forms with registers to
+// spare take (the kernel's LEAN forms).  Same p2 either way.
+template <bool EXACT, bool DOT>
 __device__ __forceinline__ void pack16(const u32x4 v, uint32_t &p2, uint32_t &nlo, uint32_t &nhi, uint32_t &sad) {
     constexpr uint32_t CODE_LO = 0x03020100u, CODE_HI = 0x04040404u;  // idx 0..3 -> 0..3, 4..7 -> 4
     constexpr uint32_t EXP_LO = 0x47544341u /* G T C A */, EXP_HI = 0x4E000000u /* idx 7: N */;
@@ -164,15 +167,19 @@ __device__ __forceinline__ void pack16(const u32x4 v, uint32_t &p2, uint32_t &nl
             sad = __builtin_amdgcn_sad_u8(x, e, sad);
         }
         u[w] = n4 | (n4 >> 4);  // bytes 0 and 2: two 4-bit codes each
-        // 2-bit codes (x >> 1) & 3 of the four bytes gathered into the top byte
-        const uint32_t t6 = (x & 0x06060606u) << 5;
-        const uint32_t a = t6 | (t6 << 6);
-        t2[w] = a | (a << 12);
+        // 2-bit codes (x >> 1) & 3 of the four bytes gathered into one byte: the low one (DOT) or the top one
+        if (DOT) {
+            t2[w] = __builtin_amdgcn_udot4(sel & 0x03030303u, 0x40100401u, 0u, false);
+        } else {
+            const uint32_t t6 = (x & 0x06060606u) << 5;
+            const uint32_t a = t6 | (t6 << 6);
+            t2[w] = a | (a << 12);
+        }
     }
     nlo = __builtin_amdgcn_perm(u[1], u[0], 0x06040200u);
     nhi = __builtin_amdgcn_perm(u[3], u[2], 0x06040200u);
-    const uint32_t lo = __builtin_amdgcn_perm(t2[1], t2[0], 0x0C0C0703u);
-    const uint32_t hi = __builtin_amdgcn_perm(t2[3], t2[2], 0x07030C0Cu);
+    const uint32_t lo = __builtin_amdgcn_perm(t2[1], t2[0], DOT ? 0x0C0C0400u : 0x0C0C0703u);
+    const uint32_t hi = __builtin_amdgcn_perm(t2[3], t2[2], DOT ? 0x04000C0Cu : 0x07030C0Cu);
     p2 = lo | hi;
 }
 
@@ -219,6 +226,16 @@ __device__ __forceinline__ void lds_wait8(uint32_t (&d)[8]) {
                  : "memory");
 }
 
+// Columns of a 32-column block that some lane of the wave still needs: the largest min(rem, 32) of the wave, at least 1
+// (wave-uniform: five ballots, a binary search on the scalar side).
+__device__ __forceinline__ int wave_cols(const int rem) {
+    int x = 0;
+#pragma unroll
+    for (int bit = 16; bit > 0; bit >>= 1)
+        if (__builtin_amdgcn_ballot_w64(rem > x + bit)) x += bit;
+    return x + 1;
+}
+
 // TRACKW: also note which columns have a score within the budget (split mode): bit 31 - j of `inm` for column j of the
 // block (kk1 = budget + 1: the sign bit of score - kk1 is shifted in).
 // TRACKW >= 2 (known-trim class): bit 31 - j instead says "column j lowered the running minimum" — the last such column of a
@@ -227,10 +244,14 @@ __device__ __forceinline__ void lds_wait8(uint32_t (&d)[8]) {
 // bit of Eq & Pv BEFORE the step: "the barcode's last row matches this column and its vertical delta was +1", i.e. the
 // diagonal move into the last row attains the column's value (needed by the reversed sweeps of trim_side = 3 passes, see
 // sweep_lane: there the last row is the barcode's FIRST base).
-template <int TF, int TRACKW>
+// COLS: `nc` (wave-uniform, 1..32) is the number of columns some lane still needs and the block stops there, after any
+// column, with a scalar branch (the loads of a group of eight stay whole); else `nc` counts the groups of eight columns
+// some lane still needs (1..4) and the block stops between groups.
+template <int TF, int TRACKW, bool COLS>
 __device__ __forceinline__ void sweep_block(const uint32_t A0, const uint32_t A1, const uint32_t A2, const uint32_t A3,
                                             const uint32_t pbase, uint32_t &Pv, uint32_t &Mv, int &score, int &best, const int kk1,
-                                            uint32_t &inm, uint32_t &inm2, const int ngr) {
+                                            uint32_t &inm, uint32_t &inm2, const int nc) {
+    const int ngr = COLS ? (nc + 7) >> 3 : nc;
     const uint32_t A[4] = {A0, A1, A2, A3};
     uint32_t Eq[2][8];
     const auto issue = [&](const int h) __attribute__((always_inline)) {
@@ -250,6 +271,7 @@ __device__ __forceinline__ void sweep_block(const uint32_t A0, const uint32_t A1
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
             const int j = 8 * h + jj;
+            if (COLS && jj > 0 && j >= nc) break;  // (wave-uniform: the group's remaining columns are junk in every lane)
             if (j < TF) {
                 sweep_step<false>(Eq[h & 1][jj], Pv, Mv, score, best);
             } else {
@@ -262,8 +284,9 @@ __device__ __forceinline__ void sweep_block(const uint32_t A0, const uint32_t A1
             }
         }
     }
-    if (TRACKW && ngr < 4) inm <<= 32 - 8 * ngr;  // (bit 31 - j stands for column j also when the block stopped early)
-    if (TRACKW >= 3 && ngr < 4) inm2 <<= 32 - 8 * ngr;
+    const int ran = COLS ? nc : 8 * ngr;             // columns the block ran
+    if (TRACKW && ran < 32) inm <<= 32 - ran;        // (bit 31 - j stands for column j also when the block stopped early)
+    if (TRACKW >= 3 && ran < 32) inm2 <<= 32 - ran;
 }
 
 // 32 columns of an ANCHORED sweep (known-alignment class, KEND = 3): one end of the alignment is fixed, the sweep looks for the
@@ -341,6 +364,10 @@ __device__ __forceinline__ void anchored_block(const uint32_t A0, const uint32_t
 template <int RW, int TF, int NV, int Q, bool SPLIT, int KB, int NW, bool MG = false, int KEND = 0, bool GEN = true, bool WINM = false>
 __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
     constexpr bool PAIRS = KB > 0;
+    // LEAN: the seeded forms over contiguous tiles of up to 5 KiB that neither hand columns over nor anchor sweeps — they run
+    // without scratch and have registers to spare for the dot-product pack and the column-granular stop of the sweeps; every
+    // other form is at the 128-register limit and keeps the code it had
+    constexpr bool LEAN = !SPLIT && !PAIRS && !WINM && KEND <= 2 && NV == 5;
     constexpr bool KREV = KEND >= 2;  // known-trim class with a trim_side = 3 pass: reversed sweeps (1: trim sides 5 / none only — the sweeps of round 3's known-end class)
     constexpr bool KALN = KEND == 3;  // known-alignment class: start AND end of every pass's winner (anchored sweeps), for per-pass outputs and the statistics tables
     constexpr int RCAP = 8;       // sweep records (seeded barcode x diagonal cluster) per read
@@ -676,9 +703,9 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
             const int k = 64 * u + lane;
             if (64 * u < nvec) {  // wave-uniform
                 uint32_t p2 = 0, nlo = 0, nhi = 0, sad = 0;
-                if (k < nvec && !BDX_DBG(32)) pack16<false>(v[u], p2, nlo, nhi, sad);
+                if (k < nvec && !BDX_DBG(32)) pack16<false, LEAN>(v[u], p2, nlo, nhi, sad);
                 if (__builtin_amdgcn_ballot_w64(sad != 0)) {  // some byte is neither A, C, G, T nor N (rare)
-                    if (sad != 0) pack16<true>(v[u], p2, nlo, nhi, sad);
+                    if (sad != 0) pack16<true, LEAN>(v[u], p2, nlo, nhi, sad);
                 }
                 if (k < nvec) {
                     img2_lane[64 * u] = p2;
@@ -793,12 +820,13 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                     A[u] |= junk;
                 }
                 uint32_t inm = 0u, inm2 = 0u;
-                // groups of eight columns some lane still needs (the tail block of a 33..48-column window is mostly junk)
-                const int ngr = __builtin_amdgcn_ballot_w64(rem > 24) ? 4 : (__builtin_amdgcn_ballot_w64(rem > 16) ? 3 : (__builtin_amdgcn_ballot_w64(rem > 8) ? 2 : 1));
+                // the columns some lane still needs, LEAN forms: to the column, else in groups of eight (the tail block of a 33..48-column window is mostly junk)
+                const int ncw = LEAN ? wave_cols(rem)
+                                     : (__builtin_amdgcn_ballot_w64(rem > 24) ? 4 : (__builtin_amdgcn_ballot_w64(rem > 16) ? 3 : (__builtin_amdgcn_ballot_w64(rem > 8) ? 2 : 1)));
                 if (blk == 0)
-                    sweep_block<TF, (SPLIT ? 1 : KEND ? 1 + KEND : 0)>(A[0], A[1], A[2], A[3], pbase, Pv, Mv, score, best, kk + 1, inm, inm2, ngr);
+                    sweep_block<TF, (SPLIT ? 1 : KEND ? 1 + KEND : 0), LEAN>(A[0], A[1], A[2], A[3], pbase, Pv, Mv, score, best, kk + 1, inm, inm2, ncw);
                 else
-                    sweep_block<0, (SPLIT ? 1 : KEND ? 1 + KEND : 0)>(A[0], A[1], A[2], A[3], pbase, Pv, Mv, score, best, kk + 1, inm, inm2, ngr);
+                    sweep_block<0, (SPLIT ? 1 : KEND ? 1 + KEND : 0), LEAN>(A[0], A[1], A[2], A[3], pbase, Pv, Mv, score, best, kk + 1, inm, inm2, ncw);
                 if (KEND && !SPLIT) {
                     // (junk columns never lower the minimum, §3.0; masked all the same)
                     inm &= rem >= 32 ? 0xFFFFFFFFu : (rem <= 0 ? 0u : ~((1u << (32 - rem)) - 1u));
@@ -1405,8 +1433,11 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                 const int d0 = (int)(id >> 16) - 64;
                 const int dmin = d0 + __builtin_ctz(dmk) - kk, dmax = d0 + (31 - __builtin_clz(dmk)) - kk;
                 const int n = rlen(t);
-                lo = dmin - kk - 1;
-                hi = dmax + mm + kk + 1;
+                // known-score forms: [dmin - kb, dmax + m + kb) holds every alignment within the budget that a hit of the record can
+                // belong to (DESIGN.md §3.0 phase 4); the forms that hand over or report columns keep one slack column on either side
+                constexpr int SLACK = (!SPLIT && KEND == 0) ? 0 : 1;
+                lo = dmin - kk - SLACK;
+                hi = dmax + mm + kk + SLACK;
                 int wlo = 0, whi = n;
                 if (ranged) {
                     wlo = wwin[(b >= a.B0 ? 2 : 0) * RW + t];

@@ -49,7 +49,11 @@
     F(36, "v_bfm_b32 x,x,b", "v_bfm_b32 %0, %0, %1", 1)                                                   \
     F(37, "v_xor_b32 x,x,b", "v_xor_b32 %0, %0, %1", 1)                                                   \
     F(38, "v_lshrrev_b64 x2,3,x2", "v_lshrrev_b64 %3, 3, %3", 1)                                          \
-    F(39, "v_and_b32 x,x,s (sgpr)", "v_and_b32 %0, %4, %0", 1)
+    F(39, "v_and_b32 x,x,s (sgpr)", "v_and_b32 %0, %4, %0", 1)                                            \
+    F(40, "v_dot4_u32_u8 x,x,b,c (vgpr weights)", "v_dot4_u32_u8 %0, %0, %1, %2", 1)                      \
+    F(41, "v_dot4_u32_u8 x,x,s,c (sgpr weights)", "v_dot4_u32_u8 %0, %0, %4, %2", 1)
+// (no row with literal weights: gfx950's VOP3P encoding takes no literal operand, the assembler refuses it; the compiler
+// moves such a constant into an SGPR, which is row 41)
 
 template <int OP>
 __global__ __launch_bounds__(256) void k(uint32_t *out, int iters, uint32_t sarg) {
