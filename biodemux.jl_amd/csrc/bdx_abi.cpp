@@ -2227,7 +2227,7 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const uint8_t *seq, const lo
                                  p.split ? 1 : 0, exc_list, exc_count, t);
     };
     const auto wave = [&](const BdxWavePlan &wp, int tier1, bool filter) {
-        return counted(bdx_launch_wave(ctx->dev, wp, he, seq, off, n_reads, o, filter ? nullptr : ctx->counts, (int *)(scratch + 256), tier1,
+        return counted(bdx_launch_wave(ctx->dev, wp, he, seq, off, n_reads, o, filter ? nullptr : ctx->counts, tier1,
                                        tier1 ? slo[0] : 0.0, filter ? nullptr : front_list, filter ? nullptr : front_count, ctx->stream, dbg,
                                        filter ? &wsp : nullptr, tier1 ? slo[1] : 0.0),
                        ctx->wave_launches);

@@ -246,10 +246,15 @@ struct BdxWaveSplit {
     int short_lb[2];
 };
 
-// Implemented in bdx_wave.hip.
+// The wave-autonomous kernel (bdx_wave_kernel.h) is compiled in six translation units, one set of instantiations each.
+// Implemented in bdx_wave.hip (LDS sizing; the known-score and plain split-mode instantiations: whole ranges, one pass).
 size_t bdx_wave_table_bytes(const BdxWavePlan &wp, int hist_entries);
 size_t bdx_wave_area_bytes(int rw, int span_cap, bool pairs, int hq_cap, int sq_cap, int cand_words, bool winm = false);
-// Implemented in bdx_wave_end.hip (the known-end instantiations of the same kernel).
+hipError_t bdx_launch_wave(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
+                           long long n_reads, const BdxDevOut &out, unsigned long long *d_counts, int tier1, double tier_slo, uint32_t *list,
+                           unsigned int *list_count, hipStream_t stream, int dbg = 0, const BdxWaveSplit *sp = nullptr, double tier_slo1 = 0.0);
+// Implemented in bdx_wave_end.hip (the known-end class: its forward-sweep instantiations are there, the reversed ones in
+// bdx_wave_rev.hip, the known-alignment ones in bdx_wave_aln.hip).
 hipError_t bdx_launch_wave_end(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
                                long long n_reads, const BdxDevOut &out, unsigned long long *d_counts, int tier1, double tier_slo, uint32_t *list,
                                unsigned int *list_count, hipStream_t stream, int dbg = 0, double tier_slo1 = 0.0,
@@ -259,16 +264,13 @@ hipError_t bdx_launch_wave_end(const BdxDevCfg &cfg, const BdxWavePlan &wp, int 
 hipError_t bdx_launch_wave_win(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
                                long long n_reads, const BdxDevOut &out, unsigned long long *d_counts, int tier1, double tier_slo, uint32_t *list,
                                unsigned int *list_count, hipStream_t stream, int dbg = 0);
-// Implemented in bdx_pairs.hip (the pairs-mode instantiations of the same kernel).
+// Implemented in bdx_pairs.hip (the pairs-mode instantiations; those of the known-end class with reversed sweeps are in
+// bdx_wave_rev.hip, the known-alignment ones in bdx_wave_aln.hip).
 // (the listed reads d_idmap[0 .. *d_count) are fetched straight from the batch; d_idmap == NULL: every read of the batch)
 hipError_t bdx_launch_pairs(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
                             long long n_reads, const uint32_t *d_idmap, const unsigned int *d_count, const BdxDevOut &out,
                             unsigned long long *d_counts, uint32_t *list, unsigned int *list_count, hipStream_t stream, int dbg = 0,
                             const BdxWaveSplit *sp = nullptr, const BdxDevStats *stats = nullptr);
-hipError_t bdx_launch_wave(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
-                           long long n_reads, const BdxDevOut &out, unsigned long long *d_counts, int *d_tile_counter, int tier1,
-                           double tier_slo, uint32_t *list, unsigned int *list_count, hipStream_t stream, int dbg = 0, const BdxWaveSplit *sp = nullptr,
-                           double tier_slo1 = 0.0);
 
 // Implemented in bdx_device.hip.
 hipError_t bdx_launch_generic(const BdxDevCfg &cfg, const BdxGenericPlan &plan, const uint8_t *d_seq,

@@ -80,7 +80,7 @@ def code_object_kernels() -> frozenset:
 
 
 # ---- instantiation names ----
-# the template parameters of the three classify families, in order (bdx_wave.hip, bdx_bitpar.hip, bdx_device.hip)
+# the template parameters of the three classify families, in order (bdx_wave_kernel.h, bdx_bitpar.hip, bdx_device.hip)
 PARAMS = {
     "bdx_wave_kernel": ("RW", "TF", "NV", "Q", "SPLIT", "KB", "NW", "MG", "KEND", "GEN", "WINM"),
     "bdx_bitpar_kernel": ("BS", "R", "SEED", "DIAG", "NW", "WL"),
@@ -110,8 +110,8 @@ def classify_kernels() -> list:
     return sorted(k for k in code_object_kernels() if parse(k) is not None)
 
 
-# ---- the wave planner, restated (bdx_abi.cpp: build_seed_tables, build_wave_tables, size_wave; bdx_wave.hip: the
-# dispatch macros of bdx_launch_wave and its siblings, bdx_wave_table_bytes, bdx_wave_area_bytes) ----
+# ---- the wave planner, restated (bdx_abi.cpp: build_seed_tables, build_wave_tables, size_wave; bdx_wave_kernel.h: the
+# dispatch ladder seeded_ladder; bdx_wave.hip: bdx_wave_table_bytes, bdx_wave_area_bytes) ----
 LDS_MAX = 160 * 1024  # bdx_abi.cpp LDS_MAX
 
 
@@ -119,9 +119,9 @@ def wave_seed_plan(ms, rate: float) -> dict:
     """Seed and sweep parameters of a single-set, unit-cost or weighted (cost >= 1) config of barcodes `ms` (lengths) at
     `rate`, outside any tier: kb = floor(rate * m) (build_seed_tables / build_wave_tables, cmin = 1); Q = the shortest
     piece floor(m / (kb + 1)), capped at 8 (build_seed_tables); track = min (m - kb - 1), clamped to 0..28
-    (build_wave_tables: wp.track_from); TF = 20 / 12 / 0 as the dispatch macros pick it from Q and track; chance = 150 x
-    pieces / 4^Q (build_wave_tables: at most 6 outside a tier); expected = chance + 1 (build_seed_tables' selectivity,
-    no barcode without seeds)."""
+    (build_wave_tables: wp.track_from); TF = 20 / 12 / 0 as the dispatch ladder (seeded_tfq) picks it from Q and track;
+    chance = 150 x pieces / 4^Q (build_wave_tables: at most 6 outside a tier); expected = chance + 1 (build_seed_tables'
+    selectivity, no barcode without seeds)."""
     kbs = [int(rate * m) for m in ms]
     q = min(8, min(m // (kb + 1) for m, kb in zip(ms, kbs)))
     pieces = sum(kb + 1 for kb in kbs)
@@ -159,7 +159,7 @@ def wave_span(rw: int, read_len: int) -> int:
 
 
 def wave_nv(span: int) -> int:
-    """The dispatch macros (BDX_WAVE_NV): span_cap <= 5 KiB -> 5 vectors per lane, else 10."""
+    """The dispatch ladder (seeded_nv): span_cap <= 5 KiB -> 5 vectors per lane, else 10."""
     return 5 if span <= 5 * 1024 else 10
 
 

@@ -23,6 +23,18 @@ def test_parse_round_trips_every_classify_instantiation():
         RW=32, TF=20, NV=5, Q=8, SPLIT=False, KB=0, NW=0, MG=False, KEND=0, GEN=False, WINM=False)
 
 
+def test_the_instantiation_list_is_the_pinned_one():
+    """The built library holds exactly the classify instantiations of tests/kernel_names.txt (one name per line, sorted):
+    a kernel that drops out of the build, or one that joins it, shows here instead of as one parametrised case fewer."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "kernel_names.txt")) as f:
+        pinned = f.read().split("\n")[:-1]
+    built = KL.classify_kernels()
+    missing = sorted(set(pinned) - set(built))
+    extra = sorted(set(built) - set(pinned))
+    assert not missing and not extra, "missing from the build:\n  " + "\n  ".join(missing) + "\nnot in kernel_names.txt:\n  " + "\n  ".join(extra)
+    assert built == pinned
+
+
 def test_every_instantiation_is_accounted_for():
     for n in KL.classify_kernels():
         has = [KL.recipe(n) is not None, n in KL.UNREACHABLE, KL.pending_reason(n) is not None]

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static instruction census of one instantiation of the wave kernel (csrc/bdx_wave.hip), read from its gfx950 assembly.
+"""Static instruction census of one instantiation of the wave kernel (csrc/bdx_wave_kernel.h, as csrc/bdx_wave.hip
+or another of its translation units instantiates it: --src), read from its gfx950 assembly.
 
     python tools/wave_isa_census.py                      # the headline form, compiled from the tree (~2 min, CPU only)
     python tools/wave_isa_census.py --asm wave.s         # an assembly file kept from an earlier run (--keep wave.s)
