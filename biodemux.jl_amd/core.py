@@ -196,7 +196,7 @@ def _close_all(classifiers) -> None:
 
 def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxConfig], object]] = None,
                            _batch_reads: int = DEFAULT_BATCH_READS, _io: str = "auto", device: int = 0,
-                           devices=None, _timings: Optional[dict] = None, **kw):
+                           devices=None, _timings: Optional[dict] = None, _gzip: str = "host", **kw):
     """execute_demultiplexing(FASTQ_file, barcode_file, output_directory; kwargs...)      core.jl:500
     execute_demultiplexing(FASTQ_file1, FASTQ_file2, barcode_file, output_directory; ...)  core.jl:360
 
@@ -212,6 +212,9 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
     ``_timings`` (a dict) receives the busy seconds of the native pipeline's stages (bench.py's end-to-end figure; with
     _io="device": upload_s, device_s, download_s, write_s and batches; with several devices also devices,
     classify_s_per_device and batches_per_device, classify_s being their sum).
+    ``_gzip`` selects who compresses gzip output: "host" (zlib on the writer's threads) or "device" (csrc/bdx_deflate.hip:
+    the device pipeline deflates each batch's blocks and downloads finished gzip members; needs ``_io="device"``, inert
+    when the output is not gzip; _timings then also holds deflate_s, plain_bytes and compressed_bytes).
     Returns the DemuxStats scalar counters (the reference returns nothing)."""
     if len(args) == 3:
         fastq1, barcode_file, output_directory = args
@@ -222,6 +225,10 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         paired = True
     else:
         raise TypeError("execute_demultiplexing takes 3 (single-end) or 4 (paired-end) positional arguments")
+    if _gzip not in ("host", "device"):
+        raise ValueError("_gzip must be 'host' or 'device'")
+    if _gzip == "device" and _io != "device":  # (no silent fallback to the host deflate)
+        raise ValueError("_gzip='device' compresses inside the device FASTQ pipeline: it needs _io='device'")
 
     defaults = dict(
         barcode_file2=None, gzip_output=None, max_error_rate=0.2, min_delta=0.0, match=0, mismatch=1, indel=1,
@@ -297,7 +304,7 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
             _timings["pre_s"] = (_dt.datetime.now() - start_time).total_seconds()  # everything before the first batch can be read
         if _io == "device":
             deviceio.demux_device(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifier, _batch_reads,
-                                  _timings)
+                                  _timings, gzip_device=_gzip == "device")
         elif use_native:
             t_call = _dt.datetime.now()
             nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2,

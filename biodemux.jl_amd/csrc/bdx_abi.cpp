@@ -1928,6 +1928,7 @@ void bdx_destroy(bdx_ctx *ctx) {
         }
     ctx->st_flag.release();
     for (DevBuf &b : ctx->fq) b.release();
+    for (DevBuf &b : ctx->dfl) b.release();
     delete ctx;
 }
 

@@ -8,6 +8,7 @@
 #include "bdx_internal.h"
 
 #define BDX_FQ_SCRATCH 12  // scratch buffers of the device FASTQ pipeline (bdx_fastq.hip)
+#define BDX_DFL_SCRATCH 4  // scratch buffers of the device DEFLATE encoder (bdx_deflate.hip)
 
 struct DevBuf {
     void *p = nullptr;
@@ -179,6 +180,7 @@ struct bdx_ctx {
     bdx_comm_state *comm = nullptr;
     DevBuf counts_sum;
     DevBuf fq[BDX_FQ_SCRATCH];  // scratch of the device FASTQ pipeline (bdx_fastq.hip)
+    DevBuf dfl[BDX_DFL_SCRATCH];  // scratch of the device DEFLATE encoder (bdx_deflate.hip): chunk table, member sizes / offsets, tokens, slots
     std::string err;
     std::string path;
     std::string launch_log;      // the classify kernels the last classify call enqueued (bdx_last_launches)

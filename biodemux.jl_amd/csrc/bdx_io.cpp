@@ -922,8 +922,8 @@ static int32_t demux_write_impl(const bdx_fq_file *src, const int64_t *line_off,
 // follows the blocks of classes 0 .. c-1 in `buf` and is appended to class_paths[c] — one write per plain file, the
 // 4 MiB 'D','X'-tagged members of demux_write_impl for gzip output.  Classes without bytes create no file (their path
 // may be NULL).  Threads work across files and members; each file is appended by one thread.
-int32_t bdx_fq_write_blocks(const uint8_t *buf, const int64_t *class_bytes, int32_t n_classes, const char *const *class_paths,
-                            int32_t force_gzip, int32_t nthreads) {
+static int32_t write_blocks_impl(const uint8_t *buf, const int64_t *class_bytes, int32_t n_classes, const char *const *class_paths,
+                                 int32_t force_gzip, int32_t nthreads, bool raw) {
     std::vector<int64_t> start((size_t)std::max(n_classes, 0) + 1, 0);
     std::vector<int> todo;
     for (int c = 0; c < n_classes; ++c) {
@@ -943,7 +943,7 @@ int32_t bdx_fq_write_blocks(const uint8_t *buf, const int64_t *class_bytes, int3
     std::vector<GzMember> members;
     std::vector<char> gz((size_t)std::max(n_classes, 0), 0);
     for (int c : todo)
-        if ((gz[(size_t)c] = gz_path(class_paths[c], force_gzip))) add_gz_members(members, c, buf + start[(size_t)c], (size_t)class_bytes[c]);
+        if ((gz[(size_t)c] = !raw && gz_path(class_paths[c], force_gzip))) add_gz_members(members, c, buf + start[(size_t)c], (size_t)class_bytes[c]);
     deflate_gz_members(members, nthreads);
     std::sort(todo.begin(), todo.end(), [&](int x, int y) { return class_bytes[x] > class_bytes[y]; });
     std::vector<char> fail((size_t)std::max(n_classes, 0), 0);
@@ -964,6 +964,18 @@ int32_t bdx_fq_write_blocks(const uint8_t *buf, const int64_t *class_bytes, int3
             return -1;
         }
     return 0;
+}
+
+int32_t bdx_fq_write_blocks(const uint8_t *buf, const int64_t *class_bytes, int32_t n_classes, const char *const *class_paths,
+                            int32_t force_gzip, int32_t nthreads) {
+    return write_blocks_impl(buf, class_bytes, n_classes, class_paths, force_gzip, nthreads, false);
+}
+
+// The same, but every block is appended verbatim whatever its path's suffix: the blocks are finished gzip member
+// chains already (bdx_fq_deflate_device).
+int32_t bdx_fq_write_blocks_raw(const uint8_t *buf, const int64_t *class_bytes, int32_t n_classes, const char *const *class_paths,
+                                int32_t nthreads) {
+    return write_blocks_impl(buf, class_bytes, n_classes, class_paths, 0, nthreads, true);
 }
 
 }  // extern "C"

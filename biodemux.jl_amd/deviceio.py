@@ -9,6 +9,10 @@ Batches of ``batch_reads`` records flow through three overlapped stages:
   writer thread   waits for batch k-1's download and appends its blocks (one write per file, in batch order: per-file
                   order is input order)
 Same files, bytes, counters and reports as nativeio.demux_native.
+
+With ``gzip_device`` (``execute_demultiplexing(..., _gzip="device")``) and gzip output the calling thread also deflates
+the batch's blocks on the device (csrc/bdx_deflate.hip, bdx_fq_deflate_device): only finished gzip members come back
+and the writer appends them verbatim (bdx_fq_write_blocks_raw); the files then gunzip to the same bytes.
 """
 from __future__ import annotations
 
@@ -108,6 +112,8 @@ def _io():
         L.bdx_fq_wait.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.bdx_fq_write_blocks.restype = C.c_int32
         L.bdx_fq_write_blocks.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.c_int32]
+        L.bdx_fq_write_blocks_raw.restype = C.c_int32
+        L.bdx_fq_write_blocks_raw.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_char_p), C.c_int32]
         _io_lib = L
     return _io_lib
 
@@ -134,9 +140,11 @@ class _Input:
 
 
 def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
-                 classifier, batch_reads: int, timings: Optional[dict] = None) -> None:
+                 classifier, batch_reads: int, timings: Optional[dict] = None, gzip_device: bool = False) -> None:
     """Device counterpart of nativeio.demux_native (same arguments but ``on_batch``: the HIP classifier keeps the
-    summary tables itself).  ``classifier`` must be the HIP classifier."""
+    summary tables itself).  ``classifier`` must be the HIP classifier.  ``gzip_device``: gzip output is compressed by
+    bdx_fq_deflate_device after the gathers, only finished gzip members are downloaded and the writer appends them as
+    they are (inert when the output is not gzip)."""
     if not hasattr(classifier, "classify_device"):
         raise ValueError("the device FASTQ pipeline (_io='device') needs the HIP classifier")
     t_wall = time.perf_counter()
@@ -151,6 +159,9 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
     n_classes = 2 + len(config.bc_seqs) * stride
     do_trim = config.trim_side is not None or config.trim_side2 is not None
     gz = int(bool(config.gzip_output))
+    dev_gz = bool(gzip_device) and bool(gz)
+    if dev_gz:
+        busy.update(deflate_s=0.0, plain_bytes=0, compressed_bytes=0)
     paired = fastq2 is not None
     # output streams of a batch: (input, prefix, trim) — core.jl:175-196
     if paired and config.classify_both:
@@ -176,9 +187,9 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
             ins.append(_Input(fastq2, rt, batch_reads))
         s_main, s_copy = rt.stream(), rt.stream()
         classifier.set_stream(s_main)
-        d_seq, d_seq_off, d_out = _DevBuf(rt), _DevBuf(rt), _DevBuf(rt)
+        d_seq, d_seq_off, d_out, d_gz = _DevBuf(rt), _DevBuf(rt), _DevBuf(rt), _DevBuf(rt)
         d_v = {k: _DevBuf(rt) for k in ("bc1", "bc2", "keep_start", "keep_end")}
-        dbufs = [d_seq, d_seq_off, d_out, *d_v.values()]
+        dbufs = [d_seq, d_seq_off, d_out, d_gz, *d_v.values()]
         d_seq_off.ensure((batch_reads + 1) * 8)
         for b in d_v.values():
             b.ensure(batch_reads * 4)
@@ -227,7 +238,11 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
                     t1 = time.perf_counter()
                     base = hbuf[slot].ctypes.data
                     for off, cb, prefix in blocks:
-                        if L.bdx_fq_write_blocks(base + off, cb.ctypes.data, n_classes, _paths(prefix, cb), gz, T) != 0:
+                        if dev_gz:  # finished gzip members: appended as they are
+                            rc = L.bdx_fq_write_blocks_raw(base + off, cb.ctypes.data, n_classes, _paths(prefix, cb), T)
+                        else:
+                            rc = L.bdx_fq_write_blocks(base + off, cb.ctypes.data, n_classes, _paths(prefix, cb), gz, T)
+                        if rc != 0:
                             raise OSError(L.bdx_io_last_error().decode())
                     busy["download_s"] += t1 - t0
                     busy["write_s"] += time.perf_counter() - t1
@@ -313,6 +328,25 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
                                                int(bool(trim)), d_out.p + pos, d_out.cap - pos, cb.ctypes.data))
                 blocks.append((pos, cb, prefix))
                 pos += int(cb.sum())
+            d_src = d_out
+            if dev_gz:  # the streams' blocks are one run of n_classes * len(outs) blocks: one deflate call
+                t_z = time.perf_counter()
+                cb_all = np.concatenate([cb for _, cb, _ in blocks])
+                bound = int(lib.bdx_fq_deflate_bound(cb_all.ctypes.data, len(cb_all)))
+                d_gz.ensure(bound)
+                zb = np.zeros(len(cb_all), dtype=np.int64)
+                check(lib.bdx_fq_deflate_device(h, d_out.p, cb_all.ctypes.data, len(cb_all), d_gz.p, d_gz.cap,
+                                                zb.ctypes.data))
+                busy["plain_bytes"] += pos
+                prefixes = [prefix for _, _, prefix in blocks]
+                blocks, pos = [], 0
+                for k, prefix in enumerate(prefixes):
+                    cz = zb[k * n_classes:(k + 1) * n_classes].copy()
+                    blocks.append((pos, cz, prefix))
+                    pos += int(cz.sum())
+                busy["compressed_bytes"] += pos
+                busy["deflate_s"] += time.perf_counter() - t_z
+                d_src = d_gz
             busy["device_s"] += time.perf_counter() - t0
             busy["batches"] += 1
             # download into a free host slot (the writer hands them back); the writer waits for the copy
@@ -328,7 +362,7 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
             if hbuf[hs] is None or len(hbuf[hs]) < pos:
                 hbuf[hs] = pinned_empty(max(pos, 1) + (max(pos, 1) >> 3), np.uint8)
             if pos:
-                rt.check(rt.hipMemcpyAsync(hbuf[hs].ctypes.data, d_out.p, pos, _D2H, s_main), "hipMemcpyAsync (download)")
+                rt.check(rt.hipMemcpyAsync(hbuf[hs].ctypes.data, d_src.p, pos, _D2H, s_main), "hipMemcpyAsync (download)")
             rt.check(rt.hipEventRecord(events[hs], s_main), "hipEventRecord")
             q_w.put((hs, blocks))
             if last:

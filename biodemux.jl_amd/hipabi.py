@@ -38,6 +38,8 @@ ABI_SYMBOLS = [
     "bdx_debug_rejected_windows_total", "bdx_last_launches",
     # device FASTQ pipeline (bdx_fastq.hip)
     "bdx_fq_index_device", "bdx_fq_pack_device", "bdx_fq_gather_device",
+    # device DEFLATE of the pipeline's gzip output (bdx_deflate.hip)
+    "bdx_fq_deflate_chunk", "bdx_fq_deflate_bound", "bdx_fq_deflate_device",
 ]
 STATS_WHICH = {"pos": 0, "len": 1, "raw": 2}
 BDX_COMM_ID_BYTES = 128
@@ -241,6 +243,12 @@ def load_library(path: Optional[str] = None):
     L.bdx_fq_gather_device.restype = C.c_int32
     L.bdx_fq_gather_device.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32,
                                        vp, C.c_int64, vp]
+    L.bdx_fq_deflate_chunk.restype = C.c_int32
+    L.bdx_fq_deflate_chunk.argtypes = []
+    L.bdx_fq_deflate_bound.restype = C.c_int64
+    L.bdx_fq_deflate_bound.argtypes = [vp, C.c_int32]
+    L.bdx_fq_deflate_device.restype = C.c_int32
+    L.bdx_fq_deflate_device.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int64, vp]
     if path is None:
         _lib = L
     return L

@@ -283,6 +283,26 @@ int32_t bdx_fq_gather_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_l
                              int32_t stride, int32_t n_classes, const int32_t *d_keep_start, const int32_t *d_keep_end,
                              int32_t trim, uint8_t *d_out, int64_t out_cap, int64_t *class_bytes);
 
+/* Device DEFLATE for the pipeline's gzip output (csrc/bdx_deflate.hip).  The input is what bdx_fq_gather_device
+ * leaves: per-class blocks back to back in device memory (any byte offsets), their sizes in the host array class_bytes.
+ * Every non-empty block is cut into chunks of at most bdx_fq_deflate_chunk() bytes and every chunk becomes one
+ * complete gzip member written by the device: FEXTRA header with OS = 255 and the 'D','X' subfield (4 bytes LE: the
+ * member's total size, the tag the project's reader walks and inflates in parallel), one dynamic-Huffman block (or one
+ * stored block when that is not smaller), CRC-32, ISIZE.  A block's members concatenated are a valid .gz for any
+ * reader.  The same input bytes give the same output bytes on every run and in every context.
+ *
+ * bdx_fq_deflate_bound: the most bytes the members of these blocks can take (len + 33 per chunk); needs no context
+ * and no device.  0 when every class is empty, negative for a negative entry.
+ *
+ * bdx_fq_deflate_device: runs on the context's stream and device and synchronises before it returns.  class_cbytes
+ * (HOST memory, n_classes entries) receives the bytes of class c's members, which follow one another in class order
+ * from d_out[0]; an empty class has no member and 0 bytes.  Fails with BDX_E_INVALID, writing nothing, when
+ * out_cap < bdx_fq_deflate_bound(class_bytes, n_classes). */
+int32_t bdx_fq_deflate_chunk(void);
+int64_t bdx_fq_deflate_bound(const int64_t *class_bytes, int32_t n_classes);
+int32_t bdx_fq_deflate_device(bdx_ctx *ctx, const uint8_t *d_in, const int64_t *class_bytes, int32_t n_classes,
+                              uint8_t *d_out, int64_t out_cap, int64_t *class_cbytes);
+
 /* Introspection for bench/tests: name of the kernel path a classify call will take, and numbers of the
  * last launch.  "generic": exact kernel only; "bitpar+verify": bit-vector sweep of every pair, then the exact
  * stage; "qgram+bitpar+verify": single-piece q-gram seeds in front of the sweep; "qgram2+bitpar+verify":

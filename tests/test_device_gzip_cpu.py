@@ -1,0 +1,183 @@
+"""Device gzip, the parts that need no GPU: the _gzip keyword's validation, the pure size functions of
+csrc/bdx_deflate.hip, the raw block writer of csrc/bdx_io.cpp, and the chunk encoder itself (csrc/bdx_deflate_core.h)
+compiled as plain C++ and held to the checks the GPU tests hold the device to."""
+import ctypes as C
+import gzip
+import os
+import subprocess
+import zlib
+
+import numpy as np
+import pytest
+
+import helpers as H
+from biodemux_jl_amd import hipabi, nativeio
+
+
+# ---- keyword validation: before any file or device is touched ----
+@pytest.mark.parametrize("kw, needle", [
+    (dict(_gzip="zstd"), "_gzip must be"),
+    (dict(_gzip="device", _io="native"), "_io='device'"),
+    (dict(_gzip="device", _io="auto"), "_io='device'"),
+    (dict(_gzip="device"), "_io='device'"),
+])
+def test_gzip_keyword_is_validated_first(tmp_path, kw, needle):
+    out = tmp_path / "never_made"
+    with pytest.raises(ValueError, match=needle):
+        H.bdx.execute_demultiplexing(str(tmp_path / "no.fastq"), str(tmp_path / "no.csv"), str(out), gzip_output=True, **kw)
+    assert not out.exists()
+
+
+# ---- the pure entries of the library ----
+def test_new_entries_are_part_of_the_abi():
+    lib = H.bdx.load_library()
+    for name in ("bdx_fq_deflate_chunk", "bdx_fq_deflate_bound", "bdx_fq_deflate_device"):
+        assert name in hipabi.ABI_SYMBOLS and hasattr(lib, name)
+    assert lib.bdx_abi_version() == 1
+
+
+def test_deflate_chunk_range():
+    assert 4096 <= H.bdx.load_library().bdx_fq_deflate_chunk() <= 65535
+
+
+def _bound(sizes):
+    a = np.asarray(sizes, dtype=np.int64)
+    return int(H.bdx.load_library().bdx_fq_deflate_bound(a.ctypes.data if len(a) else None, len(a)))
+
+
+def test_deflate_bound_without_a_device():
+    ch = H.bdx.load_library().bdx_fq_deflate_chunk()
+    rng = np.random.default_rng(4)
+    cases = [[1], [ch - 1, ch, ch + 1], [0, 3, 0, 2 * ch + 1, 0], [10 * ch], [2 ** 33 + 5]]
+    cases += [list(rng.integers(0, 5 * ch, 40)) for _ in range(5)]
+    for sizes in cases:
+        need = sum(int(n) + 33 * -(-int(n) // ch) for n in sizes if n > 0)
+        got = _bound(sizes)
+        assert need <= got <= need + 64 * len(sizes), sizes
+    assert _bound([]) == 0 and _bound([0]) == 0 and _bound([0] * 9) == 0
+    assert _bound([5, -1, 5]) < 0
+
+
+# ---- bdx_fq_write_blocks_raw ----
+def _members(data: bytes, piece: int) -> bytes:
+    """`data` as a chain of 'D','X'-tagged gzip members of `piece` bytes each, the way deflate_gz_members makes them"""
+    out = []
+    for o in range(0, len(data), piece):
+        part = data[o:o + piece]
+        z = zlib.compressobj(6, zlib.DEFLATED, -15)
+        body = z.compress(part) + z.flush()
+        total = 20 + len(body) + 8
+        out.append(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x08\0DX\x04\0" + total.to_bytes(4, "little") + body
+                   + zlib.crc32(part).to_bytes(4, "little") + (len(part) & 0xFFFFFFFF).to_bytes(4, "little"))
+    return b"".join(out)
+
+
+def _raw(buf: bytes, sizes, paths, threads=4):
+    L = nativeio._load()
+    L.bdx_fq_write_blocks_raw.restype = C.c_int32
+    L.bdx_fq_write_blocks_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32]
+    L.bdx_io_last_error.restype = C.c_char_p
+    cb = np.asarray(sizes, dtype=np.int64)
+    arr = (C.c_char_p * len(paths))(*[p.encode() if p else None for p in paths])
+    data = np.frombuffer(buf + b"\0", dtype=np.uint8)
+    return L.bdx_fq_write_blocks_raw(data.ctypes.data, cb.ctypes.data, len(cb), arr, threads), L
+
+
+def test_write_blocks_raw_appends_verbatim(tmp_path):
+    nativeio.build()
+    rec = b"".join(b"@r%d\nACGTACGTAC\n+\nIIIIIIIIII\n" % i for i in range(4000))
+    blocks = [_members(rec, 30000), b"", _members(rec[:290], 100), b"", b"not gzip at all"]
+    paths = [str(tmp_path / "a.fastq.gz"), None, str(tmp_path / "b.fastq.gz"), str(tmp_path / "empty.fastq.gz"),
+             str(tmp_path / "c.fastq.gz")]
+    for times in (1, 2):  # the second call appends
+        rc, L = _raw(b"".join(blocks), [len(b) for b in blocks], paths)
+        assert rc == 0, L.bdx_io_last_error()
+        for b, p in zip(blocks, paths):
+            if b:
+                assert open(p, "rb").read() == b * times
+        assert sorted(os.listdir(tmp_path)) == ["a.fastq.gz", "b.fastq.gz", "c.fastq.gz"]
+    assert gzip.open(paths[0]).read() == rec * 2
+    f = nativeio.FastqFile(paths[0], 4)  # the tagged chain reads back through the parallel inflate
+    try:
+        assert C.c_int32(nativeio._load().bdx_fq_parallel_inflate(f.h)).value == 1
+    finally:
+        f.close()
+
+
+def test_write_blocks_raw_refuses_a_block_without_a_path(tmp_path):
+    nativeio.build()
+    rc, L = _raw(b"abcdef", [3, 3], [str(tmp_path / "x.gz"), None])
+    assert rc != 0 and b"no path" in L.bdx_io_last_error()
+    rc, L = _raw(b"abc", [3, -1], [str(tmp_path / "y.gz"), None])
+    assert rc != 0
+
+
+# ---- the chunk encoder as plain C++ (tests/deflate_core_host.cpp) ----
+@pytest.fixture(scope="module")
+def host_encode(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("dfl") / "libdfl_host.so")
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "deflate_core_host.cpp")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, src])
+    L = C.CDLL(so)
+    L.dfl_host_encode.restype = C.c_int64
+    L.dfl_host_encode.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+    ch = L.dfl_host_chunk()
+    assert ch == H.bdx.load_library().bdx_fq_deflate_chunk()
+
+    def encode(data: bytes) -> bytes:
+        src = np.frombuffer(data + b"\0", dtype=np.uint8)
+        cap = len(data) + 33 * -(-len(data) // ch) + 64
+        out = np.zeros(cap, dtype=np.uint8)
+        n = L.dfl_host_encode(src.ctypes.data, len(data), out.ctypes.data, cap)
+        assert 0 <= n <= cap - 64
+        comp = out[:n].tobytes()
+        assert gzip.decompress(comp) == data if data else comp == b""
+        members, p = 0, 0
+        while p < len(comp):  # the 'D','X' sizes land on the end
+            assert comp[p:p + 4] == b"\x1f\x8b\x08\x04" and comp[p + 9] == 255 and comp[p + 12:p + 16] == b"DX\x04\0"
+            p += int.from_bytes(comp[p + 16:p + 20], "little")
+            members += 1
+        assert p == len(comp) and members == -(-len(data) // ch)
+        return comp
+
+    encode.chunk = ch
+    return encode
+
+
+def test_host_encoder_sizes_and_edge_inputs(host_encode):
+    ch = host_encode.chunk
+    rng = np.random.default_rng(8)
+    alphabet = np.frombuffer(b"ACGTN\n@+FFFF:,I#0123 ", dtype=np.uint8)
+    for n in (1, 2, 3, 4, 5, 258, 259, ch - 1, ch, ch + 1, 2 * ch + 1):
+        host_encode(rng.choice(alphabet, n).tobytes())
+    assert len(host_encode(b"G" * ch)) < 1024
+    assert len(host_encode(rng.integers(0, 256, ch, dtype=np.uint8).tobytes())) <= ch + 33  # one stored block
+    host_encode(b"aaababbbaa")  # no 3-gram twice: no distance code at all
+    host_encode(b"ab" * 40)     # one distance code
+
+
+@pytest.mark.parametrize("k", [22, 21])
+def test_host_encoder_limits_code_lengths(host_encode, k):
+    f = [1, 1]
+    while len(f) < k:
+        f.append(f[-1] + f[-2])
+    data = np.repeat(np.arange(65, 65 + k, dtype=np.uint8), f)  # an unrestricted Huffman tree is k - 1 > 15 deep
+    assert len(host_encode(data.tobytes())) < 2048
+    mixed = np.random.default_rng(11).permutation(data).tobytes()
+    assert len(host_encode(mixed)) < len(mixed) // 2
+
+
+def test_host_encoder_beats_huffman_only_on_fastq(host_encode):
+    rng = np.random.default_rng(20)
+    qsym = np.frombuffer(b"F:,#FFFF::0123456789-", dtype=np.uint8)[:16]
+    p = np.array([40, 15, 8, 2, 6, 6, 5, 4, 3, 3, 2, 2, 1, 1, 1, 1], dtype=np.float64)
+    out = []
+    for _ in range(600):
+        x, y = rng.integers(1000, 32000, 2)
+        out.append(b"@A00123:45:HXXXXXXX:1:1101:%d:%d 1:N:0:ACGT\n" % (x, y))
+        out.append(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), 150).tobytes() + b"\n+\n")
+        out.append(rng.choice(qsym, 150, p=p / p.sum()).tobytes() + b"\n")
+    text = b"".join(out)
+    z = zlib.compressobj(6, zlib.DEFLATED, 31, 8, zlib.Z_HUFFMAN_ONLY)
+    assert len(host_encode(text)) < len(z.compress(text) + z.flush())
+    assert host_encode(text) == host_encode(text)

@@ -2,11 +2,15 @@
 """End-to-end reads/s of execute_demultiplexing on the C2 shape: the native host pipeline (_io="native") against the device
 FASTQ pipeline (_io="device"), each run in a fresh child process (GPU box).
 
-  N=10000000 REPS=3 python tools/e2e_device_probe.py [out.json]
+  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device}] [out.json]
 
 One synthetic FASTQ of N 150 bp reads x 96 barcodes (24 bp), max_error_rate=0.1, on tmpfs (/dev/shm unless E2E_ROOT is
 set); the outputs are checked (total bytes = input bytes).  Prints every run with its stage seconds, then the medians; the
-optional argument receives the same as JSON."""
+optional argument receives the same as JSON.
+
+--gzip host: both legs write gzip (gzip_output=True, zlib on the host threads): "native+gz" and "device+gz".  --gzip device
+adds the leg "device+dgz" (_gzip="device": DEFLATE on the GPU) to the same alternating series.  The check then sums the
+ISIZE fields along the members' size tags.  Every leg reports min, median and max wall seconds."""
 import json
 import os
 import shutil
@@ -44,18 +48,42 @@ def make_input(root: str, n: int) -> None:
         f.write("ID,Full_seq,Full_annotation\n" + "".join(f"bc{i + 1:03d},{b},{'B' * 24}\n" for i, b in enumerate(bcs)))
 
 
+def gz_sizes(path: str):
+    """(compressed, uncompressed) bytes of a file made of size-tagged gzip members"""
+    import numpy as np
+
+    d = np.memmap(path, dtype=np.uint8, mode="r")
+    p, plain = 0, 0
+    while p < len(d):
+        assert bytes(d[p:p + 4]) == b"\x1f\x8b\x08\x04" and bytes(d[p + 12:p + 14]) == b"DX", (path, p)
+        p += int.from_bytes(bytes(d[p + 16:p + 20]), "little")
+        plain += int.from_bytes(bytes(d[p - 4:p]), "little")
+    assert p == len(d), (path, p, len(d))
+    return len(d), plain
+
+
 def child(mode: str) -> None:
     import biodemux_jl_amd as bdx
 
     root = os.environ["E2E_ROOT"]
     n = int(os.environ["N"])
-    fq, bc, out = (os.path.join(root, x) for x in ("synthetic.fastq", "barcodes.csv", f"out_{mode}"))
+    io, _, gz = mode.partition("+")
+    fq, bc, out = (os.path.join(root, x) for x in ("synthetic.fastq", "barcodes.csv", f"out_{io}_{gz}"))
     shutil.rmtree(out, ignore_errors=True)
     tm = {}
+    kw = dict(gzip_output=True) if gz else {}
+    if gz == "dgz":
+        kw["_gzip"] = "device"
     t = time.perf_counter()
-    bdx.execute_demultiplexing(fq, bc, out, max_error_rate=0.1, _io=mode, _timings=tm)
+    bdx.execute_demultiplexing(fq, bc, out, max_error_rate=0.1, _io=io, _timings=tm, **kw)
     dt = time.perf_counter() - t
-    nb = sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out))
+    files = [os.path.join(out, f) for f in os.listdir(out)]
+    if gz:
+        sizes = [gz_sizes(f) for f in files]
+        nb = sum(s[1] for s in sizes)
+        tm["file_bytes"] = sum(s[0] for s in sizes)
+    else:
+        nb = sum(os.path.getsize(f) for f in files)
     assert nb == n * 319, (nb, n * 319)
     shutil.rmtree(out, ignore_errors=True)
     tm = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in tm.items()}
@@ -63,6 +91,13 @@ def child(mode: str) -> None:
 
 
 def main() -> None:
+    argv = sys.argv[1:]
+    modes = ["native", "device"]
+    if argv and argv[0] == "--gzip":
+        if len(argv) < 2 or argv[1] not in ("host", "device"):
+            raise SystemExit("--gzip takes host or device")
+        modes = ["native+gz", "device+gz"] + (["device+dgz"] if argv[1] == "device" else [])
+        argv = argv[2:]
     n = int(os.environ.get("N", "10000000"))
     reps = int(os.environ.get("REPS", "3"))
     root = os.environ.get("E2E_ROOT") or "/dev/shm/bdx_e2e_device_probe"
@@ -74,7 +109,7 @@ def main() -> None:
     runs = []
     try:
         for rep in range(reps):
-            for mode in ("native", "device"):
+            for mode in modes:
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode], env=env, capture_output=True,
                                    text=True, timeout=600)
                 line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
@@ -85,20 +120,23 @@ def main() -> None:
                 r["rep"] = rep
                 runs.append(r)
                 st = r["stages"]
-                keys = ("index_s", "pack_s", "classify_s", "write_s") if mode == "native" else ("upload_s", "device_s", "download_s", "write_s")
-                print(f"RUN {rep} {mode:6s} {r['seconds']:.4f} s  {r['reads_per_s'] / 1e6:6.1f} M reads/s  "
+                keys = ("index_s", "pack_s", "classify_s", "write_s") if mode.startswith("native") else ("upload_s", "device_s", "download_s", "write_s")
+                if mode.endswith("dgz"):
+                    keys += ("deflate_s",)
+                print(f"RUN {rep} {mode:10s} {r['seconds']:.4f} s  {r['reads_per_s'] / 1e6:6.1f} M reads/s  "
                       + "  ".join(f"{k} {st.get(k, 0):.4f}" for k in keys) + f"  batches {st.get('batches')}", flush=True)
     finally:
         shutil.rmtree(root, ignore_errors=True)
     summary = {"reads": n, "fastq_gb": n * 319 / 1e9, "where": root, "generate_s": round(gen_s, 2), "runs": runs}
-    for mode in ("native", "device"):
+    for mode in modes:
         rs = [r for r in runs if r["mode"] == mode]
         med = statistics.median(r["reads_per_s"] for r in rs)
+        secs = sorted(r["seconds"] for r in rs)
         stages = {k: statistics.median(r["stages"][k] for r in rs) for k in rs[0]["stages"] if isinstance(rs[0]["stages"][k], (int, float))}
-        summary[mode] = {"median_reads_per_s": med, "median_stage_s": stages}
-        print(f"MEDIAN {mode:6s} {med / 1e6:.1f} M reads/s  " + "  ".join(f"{k} {v:.4f}" for k, v in sorted(stages.items())))
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+        summary[mode] = {"median_reads_per_s": med, "median_stage_s": stages, "seconds_min_median_max": [secs[0], statistics.median(secs), secs[-1]]}
+        print(f"MEDIAN {mode:10s} {med / 1e6:.1f} M reads/s  wall s min {secs[0]:.4f} median {statistics.median(secs):.4f} max {secs[-1]:.4f}  " + "  ".join(f"{k} {v:.4f}" for k, v in sorted(stages.items())))
+    if argv:
+        with open(argv[0], "w") as f:
             json.dump(summary, f, indent=1)
 
 
