@@ -4,12 +4,12 @@ compiled as plain C++ and held to the checks the GPU tests hold the device to.""
 import ctypes as C
 import gzip
 import os
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
+import deflate_cases as DC
 import helpers as H
 from biodemux_jl_amd import hipabi, nativeio
 
@@ -115,32 +115,8 @@ def test_write_blocks_raw_refuses_a_block_without_a_path(tmp_path):
 # ---- the chunk encoder as plain C++ (tests/deflate_core_host.cpp) ----
 @pytest.fixture(scope="module")
 def host_encode(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("dfl") / "libdfl_host.so")
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "deflate_core_host.cpp")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, src])
-    L = C.CDLL(so)
-    L.dfl_host_encode.restype = C.c_int64
-    L.dfl_host_encode.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
-    ch = L.dfl_host_chunk()
-    assert ch == H.bdx.load_library().bdx_fq_deflate_chunk()
-
-    def encode(data: bytes) -> bytes:
-        src = np.frombuffer(data + b"\0", dtype=np.uint8)
-        cap = len(data) + 33 * -(-len(data) // ch) + 64
-        out = np.zeros(cap, dtype=np.uint8)
-        n = L.dfl_host_encode(src.ctypes.data, len(data), out.ctypes.data, cap)
-        assert 0 <= n <= cap - 64
-        comp = out[:n].tobytes()
-        assert gzip.decompress(comp) == data if data else comp == b""
-        members, p = 0, 0
-        while p < len(comp):  # the 'D','X' sizes land on the end
-            assert comp[p:p + 4] == b"\x1f\x8b\x08\x04" and comp[p + 9] == 255 and comp[p + 12:p + 16] == b"DX\x04\0"
-            p += int.from_bytes(comp[p + 16:p + 20], "little")
-            members += 1
-        assert p == len(comp) and members == -(-len(data) // ch)
-        return comp
-
-    encode.chunk = ch
+    encode = DC.build_host_encoder(tmp_path_factory.mktemp("dfl"))
+    assert encode.chunk == H.bdx.load_library().bdx_fq_deflate_chunk()
     return encode
 
 
@@ -181,3 +157,39 @@ def test_host_encoder_beats_huffman_only_on_fastq(host_encode):
     z = zlib.compressobj(6, zlib.DEFLATED, 31, 8, zlib.Z_HUFFMAN_ONLY)
     assert len(host_encode(text)) < len(z.compress(text) + z.flush())
     assert host_encode(text) == host_encode(text)
+
+
+# ---- the named cases of tests/deflate_cases.py: the host build reaches every edge the GPU tests hold the device to ----
+@pytest.mark.parametrize("case", DC.CASES, ids=repr)
+def test_case_reaches_its_edge_on_the_host_build(host_encode, case):
+    comp = host_encode(case.data, fresh=True)  # (gunzips to the input, one member per chunk)
+    dyn = host_encode.last_dynamic_bytes()
+    members = DC.split_members(comp)
+    A = [DC.anatomy(m) for m in members]
+    assert b"".join(a["data"] for a in A) == case.data
+    assert all((p - d) // DC.SUB < p // DC.SUB for a in A for t in a["tokens"] if len(t) == 3 for (_, d, p) in [t]), \
+        "a candidate from the match's own sub-block: the table was consulted after this sub-block's inserts"
+    assert case.pred(A), (case.why, [(a["btype"], a["tokens"][-3:]) for a in A])
+    if A[-1]["btype"] == 2:
+        assert dyn == len(members[-1]) - 28
+    else:  # stored for a reason
+        assert dyn >= A[-1]["n"] + 5 or dyn > DC.TAB_BYTES
+    if case.tries is not None:
+        assert dyn == case.dynamic_bytes and case.tries <= DC.SEARCH_CAP
+    assert host_encode(case.data) == comp, "the same bytes from a DflShared that another chunk has used"
+
+
+@pytest.mark.parametrize("mix", ["persistent", "scan_257", "scan_768"])
+def test_host_encoder_leaks_no_state_between_chunks(host_encode, mix):
+    """one DflShared for all chunks, as in a persistent workgroup: every class equals its encoding by a fresh one"""
+    texts = DC.persistent_mix(2 * 32 + 3, 32) if mix == "persistent" else DC.scan_mix(int(mix[5:]))
+    if mix == "persistent":
+        sizes = [len(t) for t in texts]
+        assert sizes.count(DC.CH) >= 4 and min(sizes) <= 40
+    host_encode(b"x", fresh=True)
+    shared = [host_encode(t) for t in texts]
+    alone = [host_encode(t, fresh=True) for t in texts]
+    assert shared == alone
+    if mix == "persistent":
+        kinds = {(len(t) == DC.CH, DC.anatomy(c)["btype"]) for t, c in zip(texts, shared)}
+        assert kinds == {(False, 0), (False, 2), (True, 0), (True, 2)}  # small and full, stored and dynamic

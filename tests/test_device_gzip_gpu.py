@@ -49,8 +49,8 @@ def _deflate(hc, blocks, lead=0, out_cap=None, canary=0):
     cb = np.array([len(b) for b in blocks], dtype=np.int64)
     bound = int(lib.bdx_fq_deflate_bound(cb.ctypes.data, len(cb)))
     cap = bound if out_cap is None else out_cap
-    host = np.frombuffer(b"\0" * lead + b"".join(blocks) + b"\0", dtype=np.uint8)
-    d_in = torch.from_numpy(host.copy()).to("cuda:0")
+    host = np.frombuffer(b"\0" * lead + b"".join(blocks), dtype=np.uint8)  # no pad byte: the input ends the tensor
+    d_in = torch.from_numpy(host.copy()).to("cuda:0") if len(host) else torch.zeros(1, dtype=torch.uint8, device="cuda:0")
     d_out = torch.full((max(cap + canary, 1),), 0xC5, dtype=torch.uint8, device="cuda:0")
     torch.cuda.synchronize()
     zb = np.full(len(cb), -7, dtype=np.int64)

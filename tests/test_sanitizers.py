@@ -1,9 +1,11 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer on the CPU-side native code (GPU sanitizers are
 not available on the pool): the oracle and the synthetic generator through a C driver, and the
-native FASTQ I/O library through its own self-checking executable."""
+native FASTQ I/O library through its own self-checking executable, and the chunk encoder of the device DEFLATE
+(csrc/bdx_deflate_core.h as plain C++) through a driver with exact-size heap buffers."""
 import os
 import subprocess
 
+import deflate_cases as DC
 import helpers as H
 
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1"]
@@ -88,3 +90,80 @@ def test_native_io_under_asan_ubsan(tmp_path):
     out = subprocess.run([exe, str(tmp_path)], env=ENV, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "io driver ok" in out.stdout
+
+
+DEFLATE_DRIVER = r'''
+#include <zlib.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "bdx_deflate_core.h"
+
+static DflShared S;  // one for all chunks, back to back
+
+int main(int argc, char** argv) {
+    if (argc != 3) return 2;
+    const std::string dir = argv[1];
+    const int cases = atoi(argv[2]);
+    long chunks = 0, stored = 0;
+    DFL_PHASE(dfl_ph_tables(S, t))
+    for (int k = 0; k < cases; ++k) {
+        const std::string path = dir + "/case_" + std::to_string(k) + ".bin";
+        FILE* f = fopen(path.c_str(), "rb");
+        if (!f) return 3;
+        std::vector<uint8_t> all;
+        uint8_t buf[4096];
+        for (size_t got; (got = fread(buf, 1, sizeof buf, f)) > 0;) all.insert(all.end(), buf, buf + got);
+        fclose(f);
+        for (size_t o = 0; o < all.size(); o += DFL_CHUNK) {
+            const size_t n = all.size() - o < DFL_CHUNK ? all.size() - o : DFL_CHUNK;
+            // exact sizes: a read or write one byte past any of the three is the sanitizer's to report
+            uint8_t* in = (uint8_t*)malloc(n);
+            uint32_t* tok = (uint32_t*)malloc(n * sizeof(uint32_t));
+            const size_t slot_bytes = (n + 33 + 63) & ~(size_t)63;
+            uint8_t* slot = (uint8_t*)aligned_alloc(64, slot_bytes);
+            memcpy(in, all.data() + o, n);
+            uint32_t ms = 0;
+            dfl_encode_chunk(S, in, (int)n, tok, slot, &ms);
+            if (ms < 28 || ms > n + 33) { fprintf(stderr, "case %d: member of %u bytes for %zu\\n", k, ms, n); return 4; }
+            stored += S.stored;
+            uint8_t* back = (uint8_t*)malloc(n);
+            z_stream z;
+            memset(&z, 0, sizeof z);
+            if (inflateInit2(&z, 31) != Z_OK) return 5;
+            z.next_in = slot;
+            z.avail_in = ms;
+            z.next_out = back;
+            z.avail_out = (uInt)n;
+            const int rc = inflate(&z, Z_FINISH);
+            if (rc != Z_STREAM_END || z.total_out != n || z.avail_in != 0 || memcmp(back, in, n) != 0) {
+                fprintf(stderr, "case %d chunk at %zu: inflate %d, %lu of %zu bytes\\n", k, o, rc, z.total_out, n);
+                return 6;
+            }
+            inflateEnd(&z);
+            free(back); free(slot); free(tok); free(in);
+            ++chunks;
+        }
+    }
+    printf("deflate driver ok: %ld chunks, %ld stored\\n", chunks, stored);
+    return 0;
+}
+'''
+
+
+def test_deflate_encoder_under_asan_ubsan(tmp_path):
+    texts = [c.data for c in DC.CASES] + DC.persistent_mix(2 * 8 + 3, 8) + DC.scan_mix(257)[:40]
+    for k, t in enumerate(texts):
+        (tmp_path / ("case_%d.bin" % k)).write_bytes(t)
+    src = tmp_path / "deflate_driver.cpp"
+    src.write_text(DEFLATE_DRIVER)
+    exe = str(tmp_path / "deflate_driver")
+    subprocess.check_call(["g++", *SAN, "-std=c++17", "-I", os.path.join(H.ROOT, "biodemux.jl_amd", "csrc"), "-o", exe, str(src), "-lz"])
+    out = subprocess.run([exe, str(tmp_path), str(len(texts))], env=ENV, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert "deflate driver ok: %d chunks" % sum(-(-len(t) // DC.CH) for t in texts) in out.stdout
