@@ -22,7 +22,7 @@ from .classification import DemuxStats, filename_for, merge_stats_tables
 from .config import DemuxConfig, build_config
 from .fileio import read_fastq
 from . import deviceio, nativeio
-from .hipabi import HipClassifier
+from .hipabi import HipClassifier, load_library
 from .reporting import canonical_duration, generate_summary_report
 
 _PREFIX_RE = re.compile(r"\.fastq(\.gz)?$")
@@ -196,7 +196,8 @@ def _close_all(classifiers) -> None:
 
 def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxConfig], object]] = None,
                            _batch_reads: int = DEFAULT_BATCH_READS, _io: str = "auto", device: int = 0,
-                           devices=None, _timings: Optional[dict] = None, _gzip: str = "host", **kw):
+                           devices=None, _timings: Optional[dict] = None, _gzip: str = "host", _gunzip: str = "host",
+                           **kw):
     """execute_demultiplexing(FASTQ_file, barcode_file, output_directory; kwargs...)      core.jl:500
     execute_demultiplexing(FASTQ_file1, FASTQ_file2, barcode_file, output_directory; ...)  core.jl:360
 
@@ -215,6 +216,12 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
     ``_gzip`` selects who compresses gzip output: "host" (zlib on the writer's threads) or "device" (csrc/bdx_deflate.hip:
     the device pipeline deflates each batch's blocks and downloads finished gzip members; needs ``_io="device"``, inert
     when the output is not gzip; _timings then also holds deflate_s, plain_bytes and compressed_bytes).
+    ``_gunzip`` selects who inflates a ``.gz`` input: "host" (zlib on host threads, csrc/bdx_io.cpp) or "device"
+    (csrc/bdx_inflate.hip: the device pipeline uploads the compressed members and inflates them on the GPU, checking
+    every member's CRC-32 and ISIZE there; needs ``_io="device"``; inert for a plain input; a ``.gz`` input must be a
+    chain of size-tagged gzip members — BGZF, or what ``_gzip="device"`` writes — of at most 64 KiB each, anything else
+    is a ValueError; _timings then also holds inflate_s, compressed_in_bytes and plain_in_bytes, and upload_s covers
+    compressed bytes only).
     Returns the DemuxStats scalar counters (the reference returns nothing)."""
     if len(args) == 3:
         fastq1, barcode_file, output_directory = args
@@ -229,6 +236,10 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         raise ValueError("_gzip must be 'host' or 'device'")
     if _gzip == "device" and _io != "device":  # (no silent fallback to the host deflate)
         raise ValueError("_gzip='device' compresses inside the device FASTQ pipeline: it needs _io='device'")
+    if _gunzip not in ("host", "device"):
+        raise ValueError("_gunzip must be 'host' or 'device'")
+    if _gunzip == "device" and _io != "device":  # (no silent fallback to the host inflate)
+        raise ValueError("_gunzip='device' inflates inside the device FASTQ pipeline: it needs _io='device'")
 
     defaults = dict(
         barcode_file2=None, gzip_output=None, max_error_rate=0.2, min_delta=0.0, match=0, mismatch=1, indel=1,
@@ -256,6 +267,9 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         _log(f"  - Barcode File: {os.path.basename(barcode_file)}")
         _log(f"  - Output Directory: {output_directory}")
         _log(f"  - Max Error Rate: {o['max_error_rate']}")
+
+    if _gunzip == "device":  # an input the device inflate cannot take: refused before the output directory is touched
+        deviceio.check_gunzip_inputs([fastq1, fastq2] if paired else [fastq1], load_library())
 
     if not os.path.isdir(output_directory):  # core.jl:410-412
         os.mkdir(output_directory)
@@ -304,7 +318,7 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
             _timings["pre_s"] = (_dt.datetime.now() - start_time).total_seconds()  # everything before the first batch can be read
         if _io == "device":
             deviceio.demux_device(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifier, _batch_reads,
-                                  _timings, gzip_device=_gzip == "device")
+                                  _timings, gzip_device=_gzip == "device", gunzip_device=_gunzip == "device")
         elif use_native:
             t_call = _dt.datetime.now()
             nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2,

@@ -1929,6 +1929,7 @@ void bdx_destroy(bdx_ctx *ctx) {
     ctx->st_flag.release();
     for (DevBuf &b : ctx->fq) b.release();
     for (DevBuf &b : ctx->dfl) b.release();
+    for (DevBuf &b : ctx->inf) b.release();
     delete ctx;
 }
 

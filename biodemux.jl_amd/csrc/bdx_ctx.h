@@ -9,6 +9,7 @@
 
 #define BDX_FQ_SCRATCH 12  // scratch buffers of the device FASTQ pipeline (bdx_fastq.hip)
 #define BDX_DFL_SCRATCH 4  // scratch buffers of the device DEFLATE encoder (bdx_deflate.hip)
+#define BDX_INF_SCRATCH 2  // scratch buffers of the device inflate (bdx_inflate.hip)
 
 struct DevBuf {
     void *p = nullptr;
@@ -181,6 +182,7 @@ struct bdx_ctx {
     DevBuf counts_sum;
     DevBuf fq[BDX_FQ_SCRATCH];  // scratch of the device FASTQ pipeline (bdx_fastq.hip)
     DevBuf dfl[BDX_DFL_SCRATCH];  // scratch of the device DEFLATE encoder (bdx_deflate.hip): chunk table, member sizes / offsets, tokens, slots
+    DevBuf inf[BDX_INF_SCRATCH];  // scratch of the device inflate (bdx_inflate.hip): member table, member status
     std::string err;
     std::string path;
     std::string launch_log;      // the classify kernels the last classify call enqueued (bdx_last_launches)

@@ -20,6 +20,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "bdx_crc32_core.h"
+
 #define DFL_CHUNK 32768      // uncompressed bytes of a member at most (distances and positions fit 15 bits)
 #define DFL_THREADS 256
 #define DFL_HASH_BITS 13
@@ -33,7 +35,7 @@
 #define DFL_HDR_FIXED_BITS 74  // BFINAL + BTYPE (3), HLIT (5), HDIST (5), HCLEN (4), 19 code-length code lengths (57)
 #define DFL_MEMBER_OVERHEAD 28 // gzip header with the 'D','X' subfield (20) + CRC-32 + ISIZE (8)
 #define DFL_STORED_OVERHEAD 5  // stored block: header byte, LEN, NLEN
-#define DFL_CRC_POLY 0xedb88320u
+#define DFL_CRC_POLY BDX_CRC_POLY
 
 #if defined(__HIPCC__)
 #define DFL_FN __device__ inline
@@ -83,33 +85,15 @@ DFL_FN uint64_t dfl_load64(const uint8_t *p) {
     return v;
 }
 
-// ---- CRC-32 arithmetic: polynomials over GF(2) modulo P, reflected (bit 31 is x^0) ----
-DFL_FN uint32_t dfl_multmodp(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b & 1) ? (b >> 1) ^ DFL_CRC_POLY : b >> 1;
-    }
-    return p;
-}
+// ---- CRC-32 arithmetic: bdx_crc32_core.h (shared with the device inflate) ----
+DFL_FN uint32_t dfl_multmodp(uint32_t a, uint32_t b) { return bdx_crc_multmodp(a, b); }
 // x^(8 n) mod P
-DFL_FN uint32_t dfl_x8n(const DflShared &S, uint32_t n) {
-    uint32_t p = 0x80000000u;
-    for (int k = 3; n; n >>= 1, ++k)
-        if (n & 1) p = dfl_multmodp(S.x2n[k & 31], p);
-    return p;
-}
+DFL_FN uint32_t dfl_x8n(const DflShared &S, uint32_t n) { return bdx_crc_x8n(S.x2n, n); }
 
 // once per workgroup
 DFL_FN void dfl_ph_tables(DflShared &S, int t) {
-    uint32_t c = (uint32_t)t;
-    for (int k = 0; k < 8; ++k) c = (c & 1) ? DFL_CRC_POLY ^ (c >> 1) : c >> 1;
-    S.crc_tab[t] = c;
-    if (t == 0) {
-        uint32_t p = 0x40000000u;  // x^1
-        S.x2n[0] = p;
-        for (int k = 1; k < 32; ++k) S.x2n[k] = p = dfl_multmodp(p, p);
-    }
+    S.crc_tab[t] = bdx_crc_table_entry(t);
+    if (t == 0) bdx_crc_x2n_init(S.x2n);
 }
 
 DFL_FN void dfl_ph_init(DflShared &S, int t) {

@@ -334,6 +334,97 @@ void bdx_fq_release(bdx_fq_file *f, int64_t upto) {
     if (n > 0) madvise((void *)f->data, (size_t)n, MADV_DONTNEED);
 }
 
+// A .gz input opened WITHOUT inflating it (the device pipeline inflates on the GPU, bdx_fq_inflate_device): the
+// compressed bytes mapped, and the member table of its size-tagged chain — per member its compressed offset and length
+// and its ISIZE.  The file is ELIGIBLE for the device decoder when every member is tagged, every ISIZE is at most
+// `member_max` and the tags land exactly on the file's end; an empty member (the BGZF end marker) is a member like any
+// other.  The walk stops at the first member that breaks a rule: the table then holds the members before it.
+struct bdx_gz_members {
+    const uint8_t *data = nullptr;
+    int64_t size = 0;
+    std::vector<int64_t> coff;
+    std::vector<int32_t> clen, isize;
+    bool eligible = false;
+    std::string why;  // not eligible: the reason
+};
+
+int32_t bdx_fq_members_open(const char *path, int64_t member_max, bdx_gz_members **out) {
+    *out = nullptr;
+    const std::string p(path);
+    int fd = open(path, O_RDONLY);
+    struct stat st;
+    if (fd < 0 || fstat(fd, &st) != 0) {
+        g_io_err = "cannot open " + p;
+        if (fd >= 0) close(fd);
+        return -1;
+    }
+    auto g = std::make_unique<bdx_gz_members>();
+    g->size = (int64_t)st.st_size;
+    if (g->size > 0) {
+        void *m = mmap(nullptr, (size_t)g->size, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (m == MAP_FAILED) {
+            g_io_err = "mmap failed on " + p;
+            close(fd);
+            return -1;
+        }
+        g->data = (const uint8_t *)m;
+    }
+    close(fd);
+    const size_t csize = (size_t)g->size;
+    size_t coff = 0;
+    g->eligible = true;
+    while (coff < csize) {
+        const std::string at = "member " + std::to_string(g->coff.size()) + " (at byte " + std::to_string(coff) + ")";
+        const size_t clen = tagged_member_size(g->data + coff, csize - coff);
+        if (clen == 0) {
+            g->why = at + " carries no size tag (an ordinary gzip stream)";
+        } else if (clen < 26 || clen > (size_t)INT32_MAX) {
+            g->why = at + " has an impossible size tag";
+        } else if (clen > csize - coff) {
+            g->why = at + " is tagged past the end of the file";
+        } else {
+            const uint8_t *t = g->data + coff + clen - 4;
+            const int64_t ulen = (int64_t)t[0] | ((int64_t)t[1] << 8) | ((int64_t)t[2] << 16) | ((int64_t)t[3] << 24);
+            if (ulen > member_max) {
+                g->why = at + " inflates to " + std::to_string(ulen) + " bytes, the device decoder takes " + std::to_string(member_max) + " at most";
+            } else {
+                g->coff.push_back((int64_t)coff);
+                g->clen.push_back((int32_t)clen);
+                g->isize.push_back((int32_t)ulen);
+                coff += clen;
+                continue;
+            }
+        }
+        g->eligible = false;
+        break;
+    }
+    *out = g.release();
+    return 0;
+}
+
+int64_t bdx_fq_members_count(const bdx_gz_members *g) { return (int64_t)g->coff.size(); }
+int32_t bdx_fq_members_eligible(const bdx_gz_members *g) { return g->eligible ? 1 : 0; }
+const char *bdx_fq_members_reason(const bdx_gz_members *g) { return g->why.c_str(); }
+const uint8_t *bdx_fq_members_data(const bdx_gz_members *g) { return g->data; }
+int64_t bdx_fq_members_size(const bdx_gz_members *g) { return g->size; }
+// the table: bdx_fq_members_count entries each
+void bdx_fq_members_table(const bdx_gz_members *g, int64_t *comp_off, int32_t *comp_len, int32_t *isize) {
+    std::copy(g->coff.begin(), g->coff.end(), comp_off);
+    std::copy(g->clen.begin(), g->clen.end(), comp_len);
+    std::copy(g->isize.begin(), g->isize.end(), isize);
+}
+// The compressed bytes below `upto` have been uploaded: give their pages back.
+void bdx_fq_members_release(bdx_gz_members *g, int64_t upto) {
+    const int64_t page = 1 << 12;
+    const int64_t n = (std::min(upto, g->size) / page) * page;
+    if (g->data && n > 0) madvise((void *)g->data, (size_t)n, MADV_DONTNEED);
+}
+void bdx_fq_members_close(bdx_gz_members *g) {
+    if (!g) return;
+    if (g->data) munmap((void *)g->data, (size_t)g->size);
+    delete g;
+}
+
 // Blocks until at least `target` bytes of the input are there or the stream has ended (plain files: at once):
 // *avail = bytes readable from bdx_fq_data, *final = 1 when that is the whole input.  -1 when the stream failed.
 int32_t bdx_fq_wait(bdx_fq_file *f, int64_t target, int64_t *avail, int32_t *final) {

@@ -13,6 +13,12 @@ Same files, bytes, counters and reports as nativeio.demux_native.
 With ``gzip_device`` (``execute_demultiplexing(..., _gzip="device")``) and gzip output the calling thread also deflates
 the batch's blocks on the device (csrc/bdx_deflate.hip, bdx_fq_deflate_device): only finished gzip members come back
 and the writer appends them verbatim (bdx_fq_write_blocks_raw); the files then gunzip to the same bytes.
+
+With ``gunzip_device`` (``execute_demultiplexing(..., _gunzip="device")``) a ``.gz`` input that is a chain of size-tagged
+gzip members (BGZF, or this library's own output) is not inflated on the host: the upload thread copies the COMPRESSED
+members that cover the batch's byte window and the calling thread inflates them on the device right before the line
+index (csrc/bdx_inflate.hip, bdx_fq_inflate_device, which checks every member's CRC-32 and ISIZE).  The cursor stays in
+plain-text coordinates; the member at a batch's end is simply inflated again by the next batch.
 """
 from __future__ import annotations
 
@@ -118,12 +124,40 @@ def _io():
     return _io_lib
 
 
-class _Input:
-    """One FASTQ input: its host bytes (mapped, or inflated in the background) and its device side (two byte windows, the
-    line table of the current batch)."""
+def _is_gz(path: str) -> bool:
+    return path.lower().endswith(".gz")  # fileio's rule (fileio.jl:78)
 
-    def __init__(self, path: str, rt: _Runtime, batch_reads: int):
-        self.f = nativeio.FastqFile(path)
+
+def open_members(path: str, lib) -> "nativeio.GzMembers":
+    """The member table of a .gz input for the device inflate; ValueError (naming the file and the reason) when the file
+    is not a chain of size-tagged members the device decoder takes — there is no silent fall-back to the host inflate."""
+    g = nativeio.GzMembers(path, int(lib.bdx_fq_inflate_member_max()))
+    if not g.eligible:
+        why = g.reason
+        g.close()
+        raise ValueError(f"_gunzip='device' cannot take {path}: {why}; it inflates chains of size-tagged gzip members "
+                         "(BGZF, or the output of _gzip='device') — use _gunzip='host'")
+    return g
+
+
+def check_gunzip_inputs(paths, lib) -> None:
+    """execute_demultiplexing calls this before it makes the output directory: every .gz input must be eligible"""
+    for p in paths:
+        if _is_gz(p):
+            open_members(p, lib).close()
+
+
+class _Input:
+    """One FASTQ input: its host bytes (mapped, or inflated in the background; or, for the device inflate, the mapped
+    COMPRESSED members and their table) and its device side (two byte windows, the line table of the current batch)."""
+
+    def __init__(self, path: str, rt: _Runtime, batch_reads: int, members=None):
+        self.path = path
+        self.gz = members  # nativeio.GzMembers: this input is inflated on the device
+        self.f = nativeio.FastqFile(path) if members is None else None
+        self.comp = [_DevBuf(rt), _DevBuf(rt)]  # compressed form: the members of the window
+        self.wmem = [(0, 0), (0, 0)]            # ... which ones: [first, last)
+        self.d_text = [0, 0]                    # where the window's text starts on the device
         self.cursor = 0
         self.avg_record = 330.0  # bytes per record, learned from the batches so far
         self.text = [_DevBuf(rt), _DevBuf(rt)]
@@ -133,18 +167,31 @@ class _Input:
         self.d_off.ensure(4 * batch_reads * 8)
         self.d_len.ensure(4 * batch_reads * 4)
 
+    def release(self):
+        """everything below the cursor is uploaded: the host pages can go"""
+        if self.gz is None:
+            self.f.release(self.cursor)
+        elif len(self.gz):
+            m = min(int(np.searchsorted(self.gz.plain_off, self.cursor, side="right")) - 1, len(self.gz) - 1)
+            self.gz.release(int(self.gz.comp_off[m]))
+
     def close(self):
-        for b in (*self.text, self.d_off, self.d_len):
+        for b in (*self.text, *self.comp, self.d_off, self.d_len):
             b.free()
-        self.f.close()
+        for f in (self.f, self.gz):
+            if f is not None:
+                f.close()
 
 
 def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
-                 classifier, batch_reads: int, timings: Optional[dict] = None, gzip_device: bool = False) -> None:
+                 classifier, batch_reads: int, timings: Optional[dict] = None, gzip_device: bool = False,
+                 gunzip_device: bool = False) -> None:
     """Device counterpart of nativeio.demux_native (same arguments but ``on_batch``: the HIP classifier keeps the
     summary tables itself).  ``classifier`` must be the HIP classifier.  ``gzip_device``: gzip output is compressed by
     bdx_fq_deflate_device after the gathers, only finished gzip members are downloaded and the writer appends them as
-    they are (inert when the output is not gzip)."""
+    they are (inert when the output is not gzip).  ``gunzip_device``: every input whose name ends in .gz is uploaded
+    compressed and inflated by bdx_fq_inflate_device (inert for a plain input; ValueError for a .gz that is no chain of
+    size-tagged members of at most bdx_fq_inflate_member_max() bytes)."""
     if not hasattr(classifier, "classify_device"):
         raise ValueError("the device FASTQ pipeline (_io='device') needs the HIP classifier")
     t_wall = time.perf_counter()
@@ -182,9 +229,16 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
     fut = None
     writer = None
     try:
-        ins.append(_Input(fastq1, rt, batch_reads))
-        if paired:
-            ins.append(_Input(fastq2, rt, batch_reads))
+        for path in (fastq1, fastq2) if paired else (fastq1,):  # (each input judged on its own)
+            members = open_members(path, classifier.lib) if gunzip_device and _is_gz(path) else None
+            try:
+                ins.append(_Input(path, rt, batch_reads, members))
+            except BaseException:
+                if members is not None:
+                    members.close()
+                raise
+        if any(inp.gz is not None for inp in ins):
+            busy.update(inflate_s=0.0, compressed_in_bytes=0, plain_in_bytes=0)
         s_main, s_copy = rt.stream(), rt.stream()
         classifier.set_stream(s_main)
         d_seq, d_seq_off, d_out, d_gz = _DevBuf(rt), _DevBuf(rt), _DevBuf(rt), _DevBuf(rt)
@@ -203,6 +257,10 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
             """bytes [cursor, cursor + want) of the input (what is there of them) -> the device window `slot`"""
             t0 = time.perf_counter()
             rt.check(rt.hipSetDevice(dev), "hipSetDevice")
+            if inp.gz is not None:
+                upload_members(inp, slot, want)
+                busy["upload_s"] += time.perf_counter() - t0
+                return
             avail, fin = C.c_int64(0), C.c_int32(0)
             if L.bdx_fq_wait(inp.f.h, inp.cursor + want, C.byref(avail), C.byref(fin)) != 0:
                 raise OSError(L.bdx_io_last_error().decode())
@@ -215,7 +273,53 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
                 rt.check(rt.hipMemcpyAsync(dst, src, nbytes, _H2D, s_copy), "hipMemcpyAsync (upload)")
                 rt.check(rt.hipStreamSynchronize(s_copy), "hipStreamSynchronize (upload)")
             inp.win[slot] = (nbytes, final)
+            inp.d_text[slot] = dst
             busy["upload_s"] += time.perf_counter() - t0
+
+        def upload_members(inp: _Input, slot: int, want: int):
+            """the compressed members that cover the text bytes [cursor, cursor + want) -> the device buffer comp[slot]"""
+            g = inp.gz
+            n, po = len(g), g.plain_off
+            m0 = min(int(np.searchsorted(po, inp.cursor, side="right")) - 1, n)  # the member that holds the cursor
+            m1 = max(m0, min(int(np.searchsorted(po, inp.cursor + want, side="left")), n))
+            while m1 < n and g.isize[m1] == 0:  # (an empty member behind the window: the BGZF end marker)
+                m1 += 1
+            if m1 > m0:
+                c0 = int(g.comp_off[m0])
+                nbytes = int(g.comp_off[m1 - 1]) + int(g.comp_len[m1 - 1]) - c0
+                dst = inp.comp[slot].ensure(nbytes)
+                rt.check(rt.hipMemcpyAsync(dst, g.data + c0, nbytes, _H2D, s_copy), "hipMemcpyAsync (upload)")
+                rt.check(rt.hipStreamSynchronize(s_copy), "hipStreamSynchronize (upload)")
+                busy["compressed_in_bytes"] += nbytes
+            inp.wmem[slot] = (m0, m1)
+            inp.win[slot] = (max(0, int(po[m1]) - inp.cursor), m1 == n)
+
+        def inflate(inp: _Input, slot: int):
+            """comp[slot] -> text[slot] on the context's stream (the calling thread); the window's text starts at the
+            cursor, somewhere inside the first member"""
+            t_i = time.perf_counter()
+            g = inp.gz
+            m0, m1 = inp.wmem[slot]
+            k = m1 - m0
+            total = int(g.plain_off[m1] - g.plain_off[m0])
+            d_text = inp.text[slot].ensure(total + 64)
+            if k:
+                coff = np.ascontiguousarray(g.comp_off[m0:m1] - g.comp_off[m0])
+                poff = np.ascontiguousarray(g.plain_off[m0:m1] - g.plain_off[m0])
+                clen = np.ascontiguousarray(g.comp_len[m0:m1])
+                plen = np.ascontiguousarray(g.isize[m0:m1])
+                status = np.zeros(k, dtype=np.int32)
+                rc = lib.bdx_fq_inflate_device(h, inp.comp[slot].p, coff.ctypes.data, clen.ctypes.data, poff.ctypes.data,
+                                               plen.ctypes.data, k, d_text, total, status.ctypes.data)
+                if rc != 0:
+                    bad = np.flatnonzero(status)
+                    msg = lib.bdx_last_error(h).decode()
+                    if len(bad):
+                        msg = f"{inp.path}: gzip member {m0 + int(bad[0])} is refused by the device inflate ({msg})"
+                    raise BdxError(msg)
+                busy["plain_in_bytes"] += total
+            inp.d_text[slot] = d_text + (inp.cursor - int(g.plain_off[m0]))
+            busy["inflate_s"] += time.perf_counter() - t_i
 
         def want_bytes(inp: _Input) -> int:
             return int(batch_reads * inp.avg_record * 1.05) + 65536
@@ -286,9 +390,11 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
             for inp in ins:
                 want = want_bytes(inp)
                 while True:
+                    if inp.gz is not None:
+                        inflate(inp, slot)
                     nbytes, final = inp.win[slot]
                     n, nxt = C.c_int64(0), C.c_int64(0)
-                    check(lib.bdx_fq_index_device(h, inp.text[slot].p, nbytes, int(final), batch_reads, inp.d_off.p,
+                    check(lib.bdx_fq_index_device(h, inp.d_text[slot], nbytes, int(final), batch_reads, inp.d_off.p,
                                                   inp.d_len.p, C.byref(n), C.byref(nxt)))
                     if n.value >= batch_reads or final:
                         break
@@ -306,7 +412,7 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
                 if k:
                     inp.avg_record = nx / k
                 inp.cursor += nx
-                inp.f.release(inp.cursor)  # uploaded: the host pages of this batch can go
+                inp.release()  # uploaded: the host pages of this batch can go
             r1 = ins[0]
             wins = [inp.win[slot][0] for inp in ins]
             if not last:
@@ -314,7 +420,7 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
             # pack -> ONE classify call -> the gathers
             nb1 = wins[0]
             d_seq.ensure(nb1 + 64)
-            check(lib.bdx_fq_pack_device(h, r1.text[slot].p, nb1, r1.d_off.p, r1.d_len.p, n, d_seq.p, d_seq.cap,
+            check(lib.bdx_fq_pack_device(h, r1.d_text[slot], nb1, r1.d_off.p, r1.d_len.p, n, d_seq.p, d_seq.cap,
                                          d_seq_off.p, None))
             classifier.classify_device(d_seq.p, d_seq_off.p, n, **{k: b.p for k, b in d_v.items()})
             out_cap = sum(wins[i] + 64 for i, _, _ in outs)
@@ -323,7 +429,7 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
             for i, prefix, trim in outs:
                 inp = ins[i]
                 cb = np.zeros(n_classes, dtype=np.int64)
-                check(lib.bdx_fq_gather_device(h, inp.text[slot].p, wins[i], inp.d_off.p, inp.d_len.p, n, d_v["bc1"].p,
+                check(lib.bdx_fq_gather_device(h, inp.d_text[slot], wins[i], inp.d_off.p, inp.d_len.p, n, d_v["bc1"].p,
                                                d_v["bc2"].p, stride, n_classes, d_v["keep_start"].p, d_v["keep_end"].p,
                                                int(bool(trim)), d_out.p + pos, d_out.cap - pos, cb.ctypes.data))
                 blocks.append((pos, cb, prefix))

@@ -40,6 +40,8 @@ ABI_SYMBOLS = [
     "bdx_fq_index_device", "bdx_fq_pack_device", "bdx_fq_gather_device",
     # device DEFLATE of the pipeline's gzip output (bdx_deflate.hip)
     "bdx_fq_deflate_chunk", "bdx_fq_deflate_bound", "bdx_fq_deflate_device",
+    # device inflate of the pipeline's .gz input (bdx_inflate.hip)
+    "bdx_fq_inflate_member_max", "bdx_fq_inflate_device",
 ]
 STATS_WHICH = {"pos": 0, "len": 1, "raw": 2}
 BDX_COMM_ID_BYTES = 128
@@ -249,6 +251,10 @@ def load_library(path: Optional[str] = None):
     L.bdx_fq_deflate_bound.argtypes = [vp, C.c_int32]
     L.bdx_fq_deflate_device.restype = C.c_int32
     L.bdx_fq_deflate_device.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int64, vp]
+    L.bdx_fq_inflate_member_max.restype = C.c_int32
+    L.bdx_fq_inflate_member_max.argtypes = []
+    L.bdx_fq_inflate_device.restype = C.c_int32
+    L.bdx_fq_inflate_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_int64, vp]
     if path is None:
         _lib = L
     return L

@@ -64,6 +64,24 @@ def _load():
         L.bdx_fq_demux_write_range.restype = C.c_int32
         L.bdx_fq_demux_write_range.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int32, C.POINTER(C.c_char_p), vp, vp,
                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        L.bdx_fq_members_open.restype = C.c_int32
+        L.bdx_fq_members_open.argtypes = [C.c_char_p, C.c_int64, C.POINTER(vp)]
+        L.bdx_fq_members_count.restype = C.c_int64
+        L.bdx_fq_members_count.argtypes = [vp]
+        L.bdx_fq_members_eligible.restype = C.c_int32
+        L.bdx_fq_members_eligible.argtypes = [vp]
+        L.bdx_fq_members_reason.restype = C.c_char_p
+        L.bdx_fq_members_reason.argtypes = [vp]
+        L.bdx_fq_members_data.restype = vp
+        L.bdx_fq_members_data.argtypes = [vp]
+        L.bdx_fq_members_size.restype = C.c_int64
+        L.bdx_fq_members_size.argtypes = [vp]
+        L.bdx_fq_members_table.restype = None
+        L.bdx_fq_members_table.argtypes = [vp, vp, vp, vp]
+        L.bdx_fq_members_release.restype = None
+        L.bdx_fq_members_release.argtypes = [vp, C.c_int64]
+        L.bdx_fq_members_close.restype = None
+        L.bdx_fq_members_close.argtypes = [vp]
         _lib = L
     return _lib
 
@@ -131,6 +149,44 @@ class FastqFile:
     def close(self):
         if self.h:
             self.L.bdx_fq_close(self.h)
+            self.h = None
+
+
+class GzMembers:
+    """A .gz file opened WITHOUT inflating it: its compressed bytes mapped (``data``, ``size``) and the member table of
+    its size-tagged chain (BGZF 'B','C' or this library's 'D','X'): ``comp_off`` int64, ``comp_len`` and ``isize`` int32,
+    one entry per member, and ``plain_off`` (n + 1 entries: the prefix sums of ISIZE, a member's place in the text).
+    ``eligible``: every member is tagged, every ISIZE is at most ``member_max`` and the tags land on the file's end;
+    otherwise ``reason`` says which member breaks which rule and the table holds the members before it."""
+
+    def __init__(self, path: str, member_max: int):
+        self.L = _load()
+        h = C.c_void_p()
+        if self.L.bdx_fq_members_open(path.encode(), int(member_max), C.byref(h)) != 0:
+            raise OSError(self.L.bdx_io_last_error().decode())
+        self.h = h
+        self.path = path
+        n = int(self.L.bdx_fq_members_count(h))
+        self.comp_off = np.zeros(n, dtype=np.int64)
+        self.comp_len = np.zeros(n, dtype=np.int32)
+        self.isize = np.zeros(n, dtype=np.int32)
+        self.L.bdx_fq_members_table(h, self.comp_off.ctypes.data, self.comp_len.ctypes.data, self.isize.ctypes.data)
+        self.plain_off = np.concatenate([[0], np.cumsum(self.isize, dtype=np.int64)]).astype(np.int64)
+        self.eligible = bool(self.L.bdx_fq_members_eligible(h))
+        self.reason = self.L.bdx_fq_members_reason(h).decode()
+        self.data = int(self.L.bdx_fq_members_data(h) or 0)
+        self.size = int(self.L.bdx_fq_members_size(h))
+
+    def __len__(self) -> int:
+        return len(self.comp_off)
+
+    def release(self, upto: int) -> None:
+        """The compressed bytes below `upto` are uploaded: their pages can go."""
+        self.L.bdx_fq_members_release(self.h, int(upto))
+
+    def close(self):
+        if self.h:
+            self.L.bdx_fq_members_close(self.h)
             self.h = None
 
 

@@ -303,6 +303,28 @@ int64_t bdx_fq_deflate_bound(const int64_t *class_bytes, int32_t n_classes);
 int32_t bdx_fq_deflate_device(bdx_ctx *ctx, const uint8_t *d_in, const int64_t *class_bytes, int32_t n_classes,
                               uint8_t *d_out, int64_t out_cap, int64_t *class_cbytes);
 
+/* Device inflate for the pipeline's .gz input (csrc/bdx_inflate.hip): size-tagged gzip members (BGZF, or the 'D','X'
+ * members above) already in device memory are decoded, each into a slot of its own in d_out, and every member's CRC-32
+ * and ISIZE are checked on the device.  The decoder is a complete RFC 1951 / RFC 1952 one (stored, fixed and dynamic
+ * blocks, any number of them; FEXTRA, FNAME, FCOMMENT, FHCRC) and accepts a member exactly when zlib does.  The four
+ * tables are HOST arrays of n_members entries: member m is d_comp[comp_off[m], +comp_len[m]) and inflates to
+ * d_out[plain_off[m], +plain_len[m]), plain_len being the ISIZE its trailer states.  No byte outside a member is read
+ * and none outside its slot is written, whatever the member holds.
+ *
+ * bdx_fq_inflate_member_max: the largest plain_len a member may have (65536, BGZF's); needs no context and no device.
+ *
+ * bdx_fq_inflate_device: runs on the context's stream and device and synchronises before it returns.  The tables are
+ * checked first (lengths >= 0, plain_len <= bdx_fq_inflate_member_max(), every slot inside out_cap): BDX_E_INVALID
+ * before anything is launched.  n_members == 0 is BDX_OK.  status (HOST memory, n_members entries, may be NULL)
+ * receives per member 0 or why it was refused: 1 bad header, 2 bad block type, 3 bad stored lengths, 4 bad code set,
+ * 5 bad symbol, 6 distance too far, 7 output overrun, 8 output short, 9 input exhausted, 10 CRC mismatch, 11 ISIZE
+ * mismatch.  When any member is refused the call returns BDX_E_INVALID and bdx_last_error names the first one and its
+ * reason; status is filled for all members and the slots of the good ones are valid. */
+int32_t bdx_fq_inflate_member_max(void);
+int32_t bdx_fq_inflate_device(bdx_ctx *ctx, const uint8_t *d_comp, const int64_t *comp_off, const int32_t *comp_len,
+                              const int64_t *plain_off, const int32_t *plain_len, int32_t n_members, uint8_t *d_out,
+                              int64_t out_cap, int32_t *status);
+
 /* Introspection for bench/tests: name of the kernel path a classify call will take, and numbers of the
  * last launch.  "generic": exact kernel only; "bitpar+verify": bit-vector sweep of every pair, then the exact
  * stage; "qgram+bitpar+verify": single-piece q-gram seeds in front of the sweep; "qgram2+bitpar+verify":

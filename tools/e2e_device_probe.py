@@ -2,7 +2,7 @@
 """End-to-end reads/s of execute_demultiplexing on the C2 shape: the native host pipeline (_io="native") against the device
 FASTQ pipeline (_io="device"), each run in a fresh child process (GPU box).
 
-  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device}] [out.json]
+  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device} | --gunzip] [out.json]
 
 One synthetic FASTQ of N 150 bp reads x 96 barcodes (24 bp), max_error_rate=0.1, on tmpfs (/dev/shm unless E2E_ROOT is
 set); the outputs are checked (total bytes = input bytes).  Prints every run with its stage seconds, then the medians; the
@@ -10,7 +10,12 @@ optional argument receives the same as JSON.
 
 --gzip host: both legs write gzip (gzip_output=True, zlib on the host threads): "native+gz" and "device+gz".  --gzip device
 adds the leg "device+dgz" (_gzip="device": DEFLATE on the GPU) to the same alternating series.  The check then sums the
-ISIZE fields along the members' size tags.  Every leg reports min, median and max wall seconds."""
+ISIZE fields along the members' size tags.  Every leg reports min, median and max wall seconds.
+
+--gunzip: .gz in -> .gz out through the device pipeline only.  The input is written once as 32 KiB 'D','X' members (zlib
+level 1 on host threads) and three legs alternate after one unrecorded warm-up run: "device+gz+hin" (host inflate, host
+gzip), "device+dgz+hin" (host inflate, device gzip) and "device+dgz+din" (_gunzip="device": inflate on the GPU, device
+gzip)."""
 import json
 import os
 import shutil
@@ -48,6 +53,30 @@ def make_input(root: str, n: int) -> None:
         f.write("ID,Full_seq,Full_annotation\n" + "".join(f"bc{i + 1:03d},{b},{'B' * 24}\n" for i, b in enumerate(bcs)))
 
 
+def make_gz_input(root: str, member: int = 32768) -> None:
+    """synthetic.fastq.gz beside synthetic.fastq: a chain of 'D','X'-tagged members of `member` plain bytes"""
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+
+    import numpy as np
+
+    fq = os.path.join(root, "synthetic.fastq")
+    if os.path.exists(fq + ".gz"):
+        return
+    d = np.memmap(fq, dtype=np.uint8, mode="r")
+
+    def one(o):
+        part = bytes(d[o:o + member])
+        z = zlib.compressobj(1, zlib.DEFLATED, -15)
+        body = z.compress(part) + z.flush()
+        return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x08\0DX\x04\0" + (len(body) + 28).to_bytes(4, "little") + body
+                + zlib.crc32(part).to_bytes(4, "little") + len(part).to_bytes(4, "little"))
+
+    with ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0)))) as ex, open(fq + ".gz", "wb") as f:
+        for m in ex.map(one, range(0, len(d), member)):
+            f.write(m)
+
+
 def gz_sizes(path: str):
     """(compressed, uncompressed) bytes of a file made of size-tagged gzip members"""
     import numpy as np
@@ -67,13 +96,17 @@ def child(mode: str) -> None:
 
     root = os.environ["E2E_ROOT"]
     n = int(os.environ["N"])
-    io, _, gz = mode.partition("+")
-    fq, bc, out = (os.path.join(root, x) for x in ("synthetic.fastq", "barcodes.csv", f"out_{io}_{gz}"))
+    io, gz, gin = (mode.split("+") + ["", ""])[:3]
+    fq, bc, out = (os.path.join(root, x) for x in ("synthetic.fastq", "barcodes.csv", f"out_{io}_{gz}_{gin}"))
     shutil.rmtree(out, ignore_errors=True)
     tm = {}
     kw = dict(gzip_output=True) if gz else {}
     if gz == "dgz":
         kw["_gzip"] = "device"
+    if gin:
+        fq += ".gz"
+    if gin == "din":
+        kw["_gunzip"] = "device"
     t = time.perf_counter()
     bdx.execute_demultiplexing(fq, bc, out, max_error_rate=0.1, _io=io, _timings=tm, **kw)
     dt = time.perf_counter() - t
@@ -98,18 +131,26 @@ def main() -> None:
             raise SystemExit("--gzip takes host or device")
         modes = ["native+gz", "device+gz"] + (["device+dgz"] if argv[1] == "device" else [])
         argv = argv[2:]
+    gunzip = bool(argv) and argv[0] == "--gunzip"
+    if gunzip:
+        modes = ["device+gz+hin", "device+dgz+hin", "device+dgz+din"]
+        argv = argv[1:]
     n = int(os.environ.get("N", "10000000"))
     reps = int(os.environ.get("REPS", "3"))
     root = os.environ.get("E2E_ROOT") or "/dev/shm/bdx_e2e_device_probe"
     os.makedirs(root, exist_ok=True)
     t0 = time.perf_counter()
     make_input(root, n)
+    gz_bytes = None
+    if gunzip:
+        make_gz_input(root)
+        gz_bytes = os.path.getsize(os.path.join(root, "synthetic.fastq.gz"))
     gen_s = time.perf_counter() - t0
     env = dict(os.environ, E2E_ROOT=root, N=str(n))
     runs = []
     try:
-        for rep in range(reps):
-            for mode in modes:
+        for rep in range(-1 if gunzip else 0, reps):  # (rep -1: the warm-up run, not recorded)
+            for mode in modes[:1] if rep < 0 else modes:
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode], env=env, capture_output=True,
                                    text=True, timeout=600)
                 line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
@@ -118,16 +159,22 @@ def main() -> None:
                     raise SystemExit(f"{mode} run {rep} failed (rc {p.returncode})")
                 r = json.loads(line[0][7:])
                 r["rep"] = rep
+                if rep < 0:
+                    continue
                 runs.append(r)
                 st = r["stages"]
                 keys = ("index_s", "pack_s", "classify_s", "write_s") if mode.startswith("native") else ("upload_s", "device_s", "download_s", "write_s")
-                if mode.endswith("dgz"):
+                if "+dgz" in mode:
                     keys += ("deflate_s",)
+                if mode.endswith("+din"):
+                    keys += ("inflate_s", "compressed_in_bytes", "plain_in_bytes")
                 print(f"RUN {rep} {mode:10s} {r['seconds']:.4f} s  {r['reads_per_s'] / 1e6:6.1f} M reads/s  "
                       + "  ".join(f"{k} {st.get(k, 0):.4f}" for k in keys) + f"  batches {st.get('batches')}", flush=True)
     finally:
         shutil.rmtree(root, ignore_errors=True)
     summary = {"reads": n, "fastq_gb": n * 319 / 1e9, "where": root, "generate_s": round(gen_s, 2), "runs": runs}
+    if gz_bytes is not None:
+        summary["input_gz_bytes"] = gz_bytes
     for mode in modes:
         rs = [r for r in runs if r["mode"] == mode]
         med = statistics.median(r["reads_per_s"] for r in rs)
