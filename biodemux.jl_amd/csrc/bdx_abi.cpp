@@ -1,6 +1,6 @@
 // bdx_abi.cpp — C-ABI of libbiodemux_hip.so (see include/biodemux_hip.h for the contract and
-// the reference lines each entry point replaces).  Host-side only: validation, table upload,
-// launch planning (the host entry point, bdx_classify_host, is bdx_host.cpp).  All arithmetic of the hot path runs in the gfx950
+// the reference lines each entry point replaces).  Host-side only: validation, upload of what the create-time planner
+// (bdx_plan.cpp) produced, per-call launch planning (the host entry point, bdx_classify_host, is bdx_host.cpp).  All arithmetic of the hot path runs in the gfx950
 // kernels of bdx_device.hip / bdx_filter.hip; there is NO CPU fallback — without a usable
 // HIP device every entry point fails with BDX_E_DEVICE.
 #include <cmath>
@@ -84,826 +84,17 @@ BdxTuning read_tuning() {
     // BDX_NO_WAVE_FALLBACK: known-score forms of the wave kernel list a read whose record tables overflow instead of sweeping
     // it over every barcode themselves (results identical; bdx_last_list_reads shows the difference) — bit 30 of the kernels' dbg word
     if (getenv("BDX_NO_WAVE_FALLBACK")) t.debug |= 1 << 30;
+    t.no_band_roll = getenv("BDX_NO_BAND_ROLL") != nullptr;
+    t.no_known_exact = getenv("BDX_NO_KNOWN_EXACT") != nullptr;
+    t.no_kaln = getenv("BDX_NO_KALN") != nullptr;
+    t.trace_launch = getenv("BDX_TRACE_LAUNCH") != nullptr;
+    if (const char *e = getenv("BDX_WAVE_CHANCE")) t.wave_chance = atof(e);
+    if (const char *e = getenv("BDX_PAIRS_NW")) t.pairs_nw = atoi(e);
     return t;
-}
-
-BdxDevRange cvt_range(const bdx_range_t &r) {
-    BdxDevRange d;
-    d.start_offset = r.start_offset;
-    d.end_offset = r.end_offset;
-    d.start_from_end = r.start_from_end != 0;
-    d.end_from_end = r.end_from_end != 0;
-    return d;
 }
 
 const size_t LDS_MAX = 160 * 1024;
 
-// Launch planning for the exact-evaluation kernel: per-lane DP (+origin) columns, barcode
-// tables, count histogram and the read staging area must fit the CU's 160 KiB of LDS.
-int plan_generic(bdx_ctx *ctx) {
-    const BdxDevCfg &d = ctx->dev;
-    BdxGenericPlan &p = ctx->plan;
-    // SimpleScoring barcodes of <= 32 rows run the register-resident DP: no LDS columns at all
-    p.reg_rows = (!d.has_nindel && d.algorithm == BDX_ALG_SEMIGLOBAL && !d.force_lds_dp)
-                     ? (d.max_m <= 24 ? 24 : (d.max_m <= 32 ? 32 : 0)) : 0;
-    // clean class (bdx_core.h sg_core_clean): costs match >= 0, mismatch / indel >= 1, and barcode_start_range /
-    // barcode_end_range that resolve to 1:n for every read (no offset from either end) — then neither binds
-    p.clean = 0;
-    p.uniform_m = 0;
-    p.uniform_len = 0;
-    if (p.reg_rows && !ctx->tune.no_clean && d.match >= 0 && d.mismatch >= 1 && d.indel >= 1) {
-        bool free_ranges = true, uniform = true;
-        int len0 = -1;
-        bool same_len = true;
-        for (int k = 0; k < (d.is_dual ? 2 : 1); ++k) {
-            const bdx_pass_t &ps = ctx->cfg.pass[k];
-            const auto whole = [](const bdx_range_t &r) { return !r.start_from_end && r.start_offset <= 1 && r.end_from_end && r.end_offset >= 0; };
-            free_ranges = free_ranges && ps.explicit_window == 0 && whole(ps.barcode_start_range) && whole(ps.barcode_end_range);
-            for (int b = 0; b < ps.n_barcodes; ++b) {
-                const int m = (int)(ps.bc_off[b + 1] - ps.bc_off[b]);
-                uniform = uniform && m == p.reg_rows;
-                if (len0 < 0) len0 = m;
-                same_len = same_len && m == len0;
-            }
-        }
-        p.clean = free_ranges;
-        p.uniform_m = free_ranges && uniform;
-        // the diagonal-band bodies exist for these barcode lengths (every barcode of the config alike)
-        const bool band_len = len0 == 8 || len0 == 10 || len0 == 12 || len0 == 16 || len0 == 20 || len0 == 24 || len0 == 32;
-        p.uniform_len = (free_ranges && same_len && band_len) ? len0 : 0;
-    }
-    // Barcodes beyond the register DP's 32 rows inside the clean class: the rolling diagonal band (bdx_core.h sg_band_roll) —
-    // H = two operation budgets at the configured rate + 9 end columns per chunk — instead of max_m + 1 LDS rows per lane
-    // (80-nt barcodes with trimming: 648 B per lane = ONE 128-lane workgroup per CU; 26 cells: two 256-lane workgroups).
-    p.band_roll = 0;
-    p.same_len = 0;
-    ctx->dev.band_hcap = 0;
-    // (only behind a filter: without hand-over windows — filter off, barcodes beyond the sweep's 128 rows — every candidate
-    // would be walked over its whole window in chunks, three times the full matrix, where sg_core's cut-off visits a few rows
-    // per column: 160-nt barcodes unfiltered 0.3 -> 0.03 M reads/s, measured; bdx_create plans again once the filter is known)
-    if (!p.reg_rows && d.max_m > 32 && !d.has_nindel && d.algorithm == BDX_ALG_SEMIGLOBAL && !d.force_lds_dp && !ctx->tune.no_clean &&
-        !ctx->band_roll_off && !getenv("BDX_NO_BAND_ROLL") && d.match >= 0 && d.mismatch >= 1 && d.indel >= 1) {
-        bool free_ranges = true, same_len = true;
-        int len0 = -1, kb_max = 0;
-        const int cmin = d.mismatch < d.indel ? d.mismatch : d.indel;
-        for (int k = 0; k < (d.is_dual ? 2 : 1); ++k) {
-            const bdx_pass_t &ps = ctx->cfg.pass[k];
-            const auto whole = [](const bdx_range_t &r) { return !r.start_from_end && r.start_offset <= 1 && r.end_from_end && r.end_offset >= 0; };
-            free_ranges = free_ranges && ps.explicit_window == 0 && whole(ps.barcode_start_range) && whole(ps.barcode_end_range);
-            for (int b = 0; b < ps.n_barcodes; ++b) {
-                const int m = (int)(ps.bc_off[b + 1] - ps.bc_off[b]);
-                if (len0 < 0) len0 = m;
-                same_len = same_len && m == len0;
-                const int kb = (int)std::floor(d.max_error_rate * (double)m) / cmin;  // (ae as the device computes it, :254; the threshold only tightens)
-                kb_max = kb > kb_max ? kb : kb_max;
-            }
-        }
-        // H: at least two budgets + 9 end columns per chunk; up to four budgets + 9 (a clean occurrence has end columns within
-        // the budget on either side: one chunk) while two 256-lane workgroups still fit a CU (8 bytes per cell and lane)
-        int hcap = 2 * kb_max + 9;
-        {
-            size_t bc_bytes = 0;
-            int nb = 0;
-            for (int k = 0; k < (d.is_dual ? 2 : 1); ++k) {
-                bc_bytes += ctx->cfg.pass[k].bc_off[ctx->cfg.pass[k].n_barcodes];
-                nb += ctx->cfg.pass[k].n_barcodes;
-            }
-            // (what the workgroup keeps in LDS besides the cells — barcode bytes and tables, the counter histogram — as below)
-            const size_t other = (bc_bytes <= 32 * 1024 ? bc_bytes : 0) + (size_t)nb * 8 + (size_t)(d.n_counts <= 2048 ? d.n_counts : 2048) * 4 + 256;
-            const size_t room = other + 2048 < (size_t)76 * 1024 ? (size_t)76 * 1024 - other - 2048 : 0;
-            const int fit2 = (int)(room / (256 * (d.any_traceback ? 8 : 4))) - 1;  // cells per lane of a workgroup that shares the CU with another one
-            const int want = 4 * kb_max + 9;
-            const int roomy = want < fit2 ? want : fit2;
-            if (roomy > hcap) hcap = roomy;
-        }
-        if (free_ranges && hcap + 1 < d.max_m + 1 && d.max_error_rate >= 0.0 && d.max_error_rate <= 1.0) {
-            p.band_roll = 1;
-            p.same_len = same_len ? 1 : 0;
-            ctx->dev.band_hcap = hcap;
-        }
-    }
-    p.dp_rows = p.reg_rows ? 1 : (p.band_roll ? ctx->dev.band_hcap + 1 : d.max_m + 1);
-    p.dp_rows_fused = d.max_m + 1;
-    const size_t per_thread = (size_t)p.dp_rows * 4 * (d.any_traceback ? 2 : 1);
-    const int B0 = d.pass[0].n_barcodes, B1 = d.is_dual ? d.pass[1].n_barcodes : 0;
-    size_t bc_total = 0;
-    for (int k = 0; k < (d.is_dual ? 2 : 1); ++k) bc_total += ctx->cfg.pass[k].bc_off[ctx->cfg.pass[k].n_barcodes];
-    p.bc_stage_bytes = bc_total <= 32 * 1024 ? (int)((bc_total + 15) & ~(size_t)15) : 0;
-    p.hist_entries = d.n_counts <= 2048 ? d.n_counts : 2048;  // LDS histogram: the scalars + the first per-barcode slots (>= 4)
-    const size_t fixed = (size_t)(B0 + 1 + B1 + 1 + B0 + B1) * 4 + 16 + (size_t)p.bc_stage_bytes + 16 +
-                         (size_t)p.hist_entries * 4 + 16;
-    const int tries[3] = {256, 128, 64};
-    for (int t : tries) {
-        const size_t need = fixed + per_thread * (size_t)t;
-        if (need + 4096 > LDS_MAX && !(t == 64 && need <= LDS_MAX)) continue;
-        p.threads = t;
-        // Read staging: aim for two resident workgroups per CU (<= 80 KiB each) when that
-        // still leaves room for ~192 B per read; otherwise take what is left of the CU.
-        // two workgroups per CU (the exact kernels are compiled for two waves per SIMD); the rolling band keeps clear of the last
-        // granules (measured on the fused kernel: three workgroups of 54 128 B do not share a CU, three of 51 872 B do)
-        const size_t share = p.band_roll ? 77 * 1024 : 80 * 1024;
-        size_t budget = need < share ? share - need : 0;
-        // (the rolling band is bound by the latency of its LDS chain: resident waves first — two workgroups per CU with whatever
-        // staging still fits, reads that do not fit come straight from L2)
-        if (budget < (size_t)t * 192 && !(p.band_roll && need <= share)) budget = LDS_MAX - need;
-        size_t stage = budget > 64 * 1024 ? 64 * 1024 : budget;
-        stage &= ~(size_t)15;
-        if (stage < 1024 || p.bc_stage_bytes == 0) stage = 0;
-        p.stage_bytes = (int)stage;
-        p.lds_bytes = need + stage;
-        return BDX_OK;
-    }
-    return fail(ctx, BDX_E_INVALID,
-                "barcodes too long for the on-chip DP columns: max length %d needs %zu B of LDS per lane "
-                "(limit: 64 lanes within 160 KiB)",
-                d.max_m, per_thread);
-}
-
-// ---- tiered budgets --------------------------------------------------------------------------
-// Single q-gram seeds are only selective when a barcode's kb + 1 pieces keep >= 8 bases (C2: kb = 2 on 24 nt).
-// The reference's default rate 0.2 allows kb = 4 there, which needs the much costlier two-intact-pieces
-// filter — although nearly every read that carries a barcode carries it with 0..2 errors.  Tier 1 therefore
-// filters with budgets CAPPED at kb1 = m / 8 - 1: it finds, losslessly, every barcode within kb1 operations
-// (exact unit distances).  Both reducers of the reference only ever look at the smallest (and second
-// smallest) score, so whenever tier 1 finds a barcode and no barcode it cannot see could tie or beat it
-// (bdx_bitpar.hip, "tier settle rule"), the read's verdict is final; only the other reads — those without a
-// barcode, or with one beyond kb1 — are filtered again at the full budget (tier 0, in list mode).
-long long tier_cap(const bdx_ctx *ctx, int m) {
-    if (ctx->cur == 0) return (1LL << 40);
-    if (ctx->tier_cap_fixed >= 0) return ctx->tier_cap_fixed;  // (the pairs tier)
-    const int q = ctx->tier_q >= 5 && ctx->tier_q <= 8 ? ctx->tier_q : 8;
-    const int c = m / q - 1;
-    return c > 0 ? c : 0;
-}
-
-// ---- bit-parallel pre-filter: eligibility and tables (see bdx_bitpar.hip for the argument) ----
-int build_bitpar_tables(bdx_ctx *ctx) {
-    const bdx_config_t &c = ctx->cfg;
-    BdxBitparPlan &bp = ctx->F().bplan;
-    bp = BdxBitparPlan{};
-    bp.tier_slo[0] = bp.tier_slo[1] = HUGE_VAL;
-    if (c.filter == BDX_FILTER_OFF) return BDX_OK;
-    const int npass = c.is_dual ? 2 : 1;
-    // cost domain: every edit operation must cost >= 1 and a match >= 0
-    int cmin = 1;
-    if (c.algorithm == BDX_ALG_SEMIGLOBAL) {
-        cmin = c.mismatch < c.indel ? c.mismatch : c.indel;
-        if (c.has_nindel && c.nindel < cmin) cmin = c.nindel;
-        if (c.match < 0 || cmin < 1) return BDX_OK;
-    }
-    const bool n_wild = (c.algorithm == BDX_ALG_SEMIGLOBAL && c.has_nindel) || c.algorithm == BDX_ALG_HAMMING;
-    // alphabet = distinct barcode bytes (<= 15: the IUPAC letters), everything else shares the "other" code
-    int code_of[256];
-    for (int i = 0; i < 256; ++i) code_of[i] = -1;
-    int K = 0;
-    size_t cand_words = 0;
-    size_t wb = 4;
-    for (int k = 0; k < npass; ++k) {
-        const bdx_pass_t &p = c.pass[k];
-        cand_words += (size_t)(p.n_barcodes + 31) / 32;
-        for (int b = 0; b < p.n_barcodes; ++b) {
-            const uint32_t m = p.bc_off[b + 1] - p.bc_off[b];
-            if (m > 128) return BDX_OK;  // one sweep word per barcode: 32 bits, 64 for barcodes of 33..64 nt, 128 for 65..128 nt
-            if (m > 64) wb = 16;
-            else if (m > 32 && wb < 8) wb = 8;
-            for (uint32_t i = 0; i < m; ++i) {
-                const uint8_t ch = p.bc_bytes[p.bc_off[b] + i];
-                if (code_of[ch] < 0) {
-                    if (K == 15) return BDX_OK;
-                    code_of[ch] = K++;
-                }
-            }
-        }
-    }
-    if (cand_words > 128) return BDX_OK;  // <= 4096 barcodes per config (both passes together)
-    bp.ncodes = K + 1;
-    bp.ncode_N = code_of['N'] >= 0 ? code_of['N'] : 255;
-    std::vector<uint8_t> lut(256);
-    for (int i = 0; i < 256; ++i) lut[i] = (uint8_t)(code_of[i] < 0 ? K : code_of[i]);
-    size_t bytes = 256;
-    bp.word_bytes = (int)wb;
-    size_t o_peq[2] = {0, 0}, o_pv[2] = {0, 0}, o_kb[2] = {0, 0};
-    for (int k = 0; k < npass; ++k) {
-        const int B = c.pass[k].n_barcodes;
-        bp.bpad[k] = 32;  // power of two >= B: peq row address = code << log2(4*bpad)
-        while (bp.bpad[k] < B) bp.bpad[k] <<= 1;
-        if ((size_t)bp.ncodes * bp.bpad[k] * wb > 96 * 1024) return BDX_OK;  // the table lives in LDS
-        bytes = (bytes + 15) & ~(size_t)15;
-        o_peq[k] = bytes;
-        bytes += (size_t)bp.ncodes * bp.bpad[k] * wb;
-        o_pv[k] = bytes;
-        bytes += (size_t)B * wb;
-        o_kb[k] = bytes;
-        bytes += (size_t)B * 4;
-    }
-    std::vector<uint8_t> blob(bytes, 0);
-    memcpy(blob.data(), lut.data(), 256);
-    for (int k = 0; k < npass; ++k) {
-        const bdx_pass_t &p = c.pass[k];
-        uint8_t *peq = blob.data() + o_peq[k];
-        uint8_t *pv = blob.data() + o_pv[k];
-        int32_t *kb = (int32_t *)(blob.data() + o_kb[k]);
-        const int bits = (int)wb * 8;
-        bp.kb_uniform[k] = -2;  // (unset)
-        typedef unsigned __int128 u128;
-        const auto put = [&](uint8_t *dst, size_t idx, u128 v) {
-            if (wb == 16)
-                memcpy(dst + idx * 16, &v, 16);
-            else if (wb == 8)
-                ((uint64_t *)dst)[idx] = (uint64_t)v;
-            else
-                ((uint32_t *)dst)[idx] = (uint32_t)v;
-        };
-        for (int b = 0; b < p.n_barcodes; ++b) {
-            const int m = (int)(p.bc_off[b + 1] - p.bc_off[b]);
-            const int shift = bits - m;
-            const u128 all = bits == 128 ? ~(u128)0 : (((u128)1 << bits) - 1);
-            const u128 rows = m == bits ? all : ((((u128)1 << m) - 1) << shift);
-            const u128 pad = ~rows & all;  // virtual rows below the barcode: match everything, D stays 0
-            put(pv, (size_t)b, rows);
-            for (int code = 0; code < bp.ncodes; ++code) {
-                u128 mask = pad;
-                for (int i = 0; i < m; ++i) {
-                    const uint8_t ch = p.bc_bytes[p.bc_off[b] + i];
-                    const bool wild = n_wild && ch == 'N';
-                    if (wild || (code < K && code_of[ch] == code)) mask |= (u128)1 << (shift + i);
-                }
-                put(peq, (size_t)code * bp.bpad[k] + b, mask);
-            }
-            // allowed_error at the initial threshold, exactly as the device computes it
-            long long ae;
-            if (c.algorithm == BDX_ALG_EXACT)
-                ae = 0;
-            else if (c.algorithm == BDX_ALG_HAMMING)
-                ae = (long long)std::floor(c.max_error_rate * (double)m);
-            else
-                ae = (long long)std::floor(c.max_error_rate * (double)(c.has_nindel ? p.bc_len_no_N[b] : m));
-            long long kfull = ae < 0 ? -1 : ae / cmin;
-            long long kcap = kfull;
-            if (kcap > tier_cap(ctx, m)) kcap = tier_cap(ctx, m);
-            kb[b] = (int32_t)kcap;
-            bp.kb_uniform[k] = bp.kb_uniform[k] == -2 ? (int)kcap : (bp.kb_uniform[k] == (int)kcap ? (int)kcap : -1);
-            if (kcap < kfull) {
-                // the smallest score a barcode tier 1 cannot see may have: (kb1 + 1) operations of cost >= cmin
-                // each, over this barcode's normalisation (computed as the device computes a score)
-                const double norm = (c.algorithm == BDX_ALG_SEMIGLOBAL && c.has_nindel) ? (double)p.bc_len_no_N[b] : (double)m;
-                const double lo = (double)((kcap + 1) * cmin) / norm;
-                if (lo < bp.tier_slo[k]) bp.tier_slo[k] = lo;
-                bp.tier_capped = 1;
-            }
-        }
-    }
-    HIP_TRY(ctx, ctx->F().bp_tables.ensure(bytes));
-    HIP_TRY(ctx, hipMemcpy(ctx->F().bp_tables.p, blob.data(), bytes, hipMemcpyHostToDevice));
-    const uint8_t *base = (const uint8_t *)ctx->F().bp_tables.p;
-    bp.d_lut = base;
-    for (int k = 0; k < npass; ++k) {
-        bp.d_peq[k] = base + o_peq[k];
-        bp.d_pvinit[k] = base + o_pv[k];
-        bp.d_kb[k] = (const int32_t *)(base + o_kb[k]);
-    }
-    // Reducer replay capacity: short barcodes at high rates have many GENUINE candidates per read (a 10-mer within two
-    // edits of a random 150-base read is common: ~25 of 96 barcodes), and a read with more survivors than the replay
-    // holds costs a full exact DP per candidate.  Expected candidates per read ~ sum over barcodes of
-    // 150 * V(m, kb) / 4^m with V = sum_{e <= kb} C(m, e) 8^e (3 substitutions, 4 insertions, 1 deletion per site).
-    {
-        double expected = 0.0;
-        for (int k = 0; k < npass; ++k) {
-            const bdx_pass_t &p = c.pass[k];
-            const int32_t *kbh = (const int32_t *)(blob.data() + o_kb[k]);
-            for (int b = 0; b < p.n_barcodes; ++b) {
-                const int m = (int)(p.bc_off[b + 1] - p.bc_off[b]);
-                if (kbh[b] < 0 || m > 20) continue;
-                double v = 0.0, term = 1.0;
-                for (int e = 0; e <= kbh[b] && e <= m; ++e) {
-                    v += term;
-                    term *= 8.0 * (double)(m - e) / (double)(e + 1);
-                }
-                expected += 150.0 * v / std::pow(4.0, (double)m);
-            }
-        }
-        bp.slot_cap = expected < 1.0 ? 4 : expected < 2.5 ? 8 : expected < 8.0 ? 16 : 32;
-        int total_b = 0;
-        for (int k = 0; k < npass; ++k) total_b += c.pass[k].n_barcodes;
-        bp.dense_d = expected >= 1.0 && total_b <= 256 && !ctx->tune.no_dense;  // (used by the kernels without seeds only; they then keep four slots)
-    }
-    // known-score class (config level): SimpleScoring with unit costs, ScoreOnly output.
-    // (:exact with whole ranges IS the class at a budget of 0: exact_align, classification.jl:485-548, returns (0.0, s, s + m - 1)
-    // for an occurrence — the leftmost, or the rightmost with trim_side = 3 — else Inf: the value, the end of the first column
-    // at distance 0 and the largest origin of a distance-0 alignment; raw bytes are compared, N is a literal: SimpleScoring.
-    // With a ref_search_range its meaning differs — allowed START positions, SURVEY Q11 — so only whole ranges qualify.)
-    const auto whole_rng = [](const bdx_range_t &r) { return !r.start_from_end && r.start_offset <= 1 && r.end_from_end && r.end_offset >= 0; };
-    for (int k = 0; k < npass; ++k) {
-        const bool score_only = c.pass[k].trim_side == 0 && !c.need_traceback;
-        const bool unit_sg = c.algorithm == BDX_ALG_SEMIGLOBAL && !c.has_nindel && c.match == 0 && c.mismatch == 1 && c.indel == 1;
-        const bool exact_whole = c.algorithm == BDX_ALG_EXACT && c.pass[k].explicit_window == 0 && whole_rng(c.pass[k].ref_search_range) &&
-                                 whole_rng(c.pass[k].barcode_start_range) && whole_rng(c.pass[k].barcode_end_range) && !getenv("BDX_NO_KNOWN_EXACT");
-        bp.known_ok[k] = (unit_sg || exact_whole) && score_only && c.pass[k].explicit_window != BDX_WINDOW_ALIGN_ONE && !ctx->tune.no_known;
-    }
-    bp.enabled = 1;
-    return BDX_OK;
-}
-
-
-// ---- q-gram seeding (pigeonhole) in front of the sweep -------------------------------------
-// A recordable alignment of barcode b has at most kb[b] edit operations (see the sweep), so of
-// kb[b]+1 disjoint pieces of the barcode at least one occurs in the read unchanged; a fortiori
-// the first q bases of that piece do.  Pairs without any such seed hit cannot be candidates and
-// are not swept.  Keys use 2 bits per base (symbol code & 3): equal bytes give equal keys, other
-// bytes may alias — that only adds sweeps, never removes one.
-int build_seed_tables(bdx_ctx *ctx, bool strict, bool alt = false) {
-    const bdx_config_t &c = ctx->cfg;
-    BdxSeedPlan &sp = alt ? ctx->F().splan_alt : ctx->F().splan;
-    DevBuf &tables = alt ? ctx->F().seed_tables_alt : ctx->F().seed_tables;
-    sp = BdxSeedPlan{};
-    if (!ctx->F().bplan.enabled || c.filter == BDX_FILTER_BITPAR || ctx->tune.no_seed) return BDX_OK;
-    const int npass = c.is_dual ? 2 : 1;
-    int cmin = 1;
-    if (c.algorithm == BDX_ALG_SEMIGLOBAL) {
-        cmin = c.mismatch < c.indel ? c.mismatch : c.indel;
-        if (c.has_nindel && c.nindel < cmin) cmin = c.nindel;
-    }
-    const bool n_wild = (c.algorithm == BDX_ALG_SEMIGLOBAL && c.has_nindel) || c.algorithm == BDX_ALG_HAMMING;
-    // same symbol coding as the sweep
-    int code_of[256];
-    for (int i = 0; i < 256; ++i) code_of[i] = -1;
-    int K = 0;
-    for (int k = 0; k < npass; ++k)
-        for (uint32_t i = 0; i < c.pass[k].bc_off[c.pass[k].n_barcodes]; ++i) {
-            const uint8_t ch = c.pass[k].bc_bytes[i];
-            if (code_of[ch] < 0) code_of[ch] = K++;
-        }
-    struct Piece { int pass, b, start; };
-    std::vector<Piece> pieces;
-    std::vector<uint16_t> always[2];
-    int q = 8;
-    int total_bc = 0;
-    for (int k = 0; k < npass; ++k) {
-        const bdx_pass_t &p = c.pass[k];
-        if (p.n_barcodes > 32767) return BDX_OK;
-        total_bc += p.n_barcodes;
-        for (int b = 0; b < p.n_barcodes; ++b) {
-            const int m = (int)(p.bc_off[b + 1] - p.bc_off[b]);
-            long long ae;
-            if (c.algorithm == BDX_ALG_EXACT) ae = 0;
-            else if (c.algorithm == BDX_ALG_HAMMING) ae = (long long)std::floor(c.max_error_rate * (double)m);
-            else ae = (long long)std::floor(c.max_error_rate * (double)(c.has_nindel ? p.bc_len_no_N[b] : m));
-            if (ae < 0) continue;  // can never be recorded: neither seeded nor swept
-            long long kb = ae / cmin;
-            if (kb > tier_cap(ctx, m)) kb = tier_cap(ctx, m);
-            bool wild = false;
-            for (int i = 0; i < m; ++i) wild |= n_wild && p.bc_bytes[p.bc_off[b] + i] == 'N';
-            const long long L = m / (kb + 1);
-            if (wild || L < 5) {
-                always[k].push_back((uint16_t)b);
-                continue;
-            }
-            if (L < q) q = (int)L;
-            for (long long t = 0; t <= kb; ++t) pieces.push_back(Piece{k, b, (int)(t * L)});
-        }
-    }
-    if (pieces.empty()) return BDX_OK;
-    if ((int)(always[0].size() + always[1].size()) * 4 > total_bc) return BDX_OK;  // seeding would not pay
-    if (pieces.size() > 16384) return BDX_OK;
-    // selectivity: expected seed-hit pairs per read of ~150 bases must be well below B
-    const double space = std::pow(4.0, q);
-    const double expected = 150.0 * (double)pieces.size() / space + 1.0 + (double)(always[0].size() + always[1].size());
-    if (expected * 3.0 > (double)total_bc) return BDX_OK;
-    // strict: single seeds only when they are really selective (q = 7, 8 in practice).  With ~14 falsely
-    // seeded barcodes per read (q = 6 at B = 96) the hit queue / record tables cost more than the
-    // two-intact-pieces variant, which is tried next (measured at kb = 3: 7.5 ms vs 5.7 ms per 2 M reads).
-    if (strict && expected > 7.0) return BDX_OK;
-    sp.q = q;
-    // hashed bitmap with >= 96 bits per key (<= ~1 % false hits per position), at most the key space
-    // itself (then it is exact).  Too many false hits overflow the hit queue, and an overflow costs a
-    // whole-read sweep of every barcode.
-    sp.bm_log2 = 5;
-    while ((1u << sp.bm_log2) < pieces.size() * 96 && sp.bm_log2 < 2 * q) sp.bm_log2++;
-    // sweep records per read: the true barcode(s) plus the expected falsely seeded ones, generously
-    {
-        const double false_pairs = 150.0 * (double)pieces.size() / space;
-        sp.rcap = 8;
-        while (sp.rcap < 64 && (double)sp.rcap < 4.0 + 4.0 * false_pairs) sp.rcap *= 2;
-        // queues: the planted pair plus the chance pairs, with slack for the spread between the reads of a tile
-        sp.qmul = sp.rcap >= 16 ? 8 : 4;
-        const int want = (int)std::ceil((1.0 + false_pairs) * 1.5 + 1.0);  // (C2: 4 — one more entry per read would cost the fourth workgroup per CU)
-        if (want > sp.qmul) sp.qmul = want > 48 ? 48 : want;
-    }
-    if (ctx->tune.seed_bm_log2 > 0) sp.bm_log2 = ctx->tune.seed_bm_log2 < 2 * q ? ctx->tune.seed_bm_log2 : 2 * q;
-    sp.bm_words = (1 << sp.bm_log2) / 32;
-    sp.hash_log2 = 8;
-    while ((1u << sp.hash_log2) < pieces.size() * 2) sp.hash_log2++;
-    sp.hash_in_lds = ((size_t)5 << sp.hash_log2) <= 8 * 1024;  // larger tables are probed in L2 (a few probes per read)
-    if (ctx->tune.seed_hash_l2) sp.hash_in_lds = 0;
-    std::vector<uint32_t> bitmap(sp.bm_words, 0), hash((size_t)1 << sp.hash_log2, 0);
-    std::vector<uint8_t> hash_ps((size_t)1 << sp.hash_log2, 0);
-    const uint32_t hmask = (1u << sp.hash_log2) - 1;
-    for (const Piece &pc : pieces) {
-        const bdx_pass_t &p = c.pass[pc.pass];
-        uint32_t key = 0;
-        for (int i = 0; i < q; ++i) key |= (uint32_t)(code_of[p.bc_bytes[p.bc_off[pc.b] + pc.start + i]] & 3) << (2 * i);
-        // same cheap fold as the kernel's scan (direct index when the bitmap spans the key space)
-        const uint32_t hb = sp.bm_log2 >= 2 * q ? key : ((key ^ (key >> sp.bm_log2)) & ((1u << sp.bm_log2) - 1u));
-        bitmap[hb >> 5] |= 1u << (hb & 31);
-        const uint32_t entry = (key << 16) | ((uint32_t)pc.pass << 15) | (uint32_t)(pc.b + 1);
-        uint32_t slot = (key * 0x9E3779B1u) >> (32 - sp.hash_log2);
-        // one entry per (key, barcode, piece start): two pieces of one barcode may share a key
-        bool dup = false;
-        while (hash[slot] != 0) {
-            if (hash[slot] == entry && hash_ps[slot] == (uint8_t)pc.start) { dup = true; break; }
-            slot = (slot + 1) & hmask;
-        }
-        if (!dup) {
-            hash[slot] = entry;
-            hash_ps[slot] = (uint8_t)pc.start;
-        }
-    }
-    size_t bytes = bitmap.size() * 4 + hash.size() * 4 + ((hash_ps.size() + 15) & ~(size_t)15);
-    const size_t o_always[2] = {bytes, bytes + ((always[0].size() * 2 + 15) & ~(size_t)15)};
-    bytes = o_always[1] + ((always[1].size() * 2 + 15) & ~(size_t)15) + 16;
-    std::vector<uint8_t> blob(bytes, 0);
-    memcpy(blob.data(), bitmap.data(), bitmap.size() * 4);
-    memcpy(blob.data() + bitmap.size() * 4, hash.data(), hash.size() * 4);
-    memcpy(blob.data() + bitmap.size() * 4 + hash.size() * 4, hash_ps.data(), hash_ps.size());
-    for (int k = 0; k < 2; ++k)
-        if (!always[k].empty()) memcpy(blob.data() + o_always[k], always[k].data(), always[k].size() * 2);
-    HIP_TRY(ctx, tables.ensure(bytes));
-    HIP_TRY(ctx, hipMemcpy(tables.p, blob.data(), bytes, hipMemcpyHostToDevice));
-    const uint8_t *base = (const uint8_t *)tables.p;
-    sp.d_bitmap = (const uint32_t *)base;
-    sp.d_hash = (const uint32_t *)(base + bitmap.size() * 4);
-    sp.d_hash_ps = base + bitmap.size() * 4 + hash.size() * 4;
-    for (int k = 0; k < 2; ++k) {
-        sp.n_always[k] = (int)always[k].size();
-        sp.d_always[k] = (const uint16_t *)(base + o_always[k]);
-    }
-    sp.enabled = 1;
-    return BDX_OK;
-}
-
-// ---- two-intact-pieces ("diagonal") seeding for budgets where single pieces are too short -----
-// With kb operations allowed, kb+2 disjoint pieces of the barcode leave at least TWO untouched; they
-// occur in the read on diagonals (read position - barcode offset) that differ by at most kb (the
-// indels between them), and the alignment starts within kb of either diagonal.  The kernel keeps,
-// per read, an inverted index of its 4-mers (256 keys x position bits) and tests every (read,
-// barcode) pair with a handful of word operations per piece; only pairs with two such pieces are
-// swept, over the columns [d_min - kb - 1, d_max + m + kb + 1).  Lossless for the same reason as the
-// single-piece seeds: it only skips pairs whose unit distance exceeds kb.
-int build_diag_tables(bdx_ctx *ctx) {
-    const bdx_config_t &c = ctx->cfg;
-    BdxSeedPlan &sp = ctx->F().splan;
-    if (sp.enabled || !ctx->F().bplan.enabled || c.filter == BDX_FILTER_BITPAR || ctx->tune.no_seed || ctx->tune.no_diag ||
-        ctx->F().bplan.word_bytes != 4)  // (the diagonal variant has 32-bit sweep words)
-        return BDX_OK;
-    const int npass = c.is_dual ? 2 : 1;
-    int cmin = 1;
-    if (c.algorithm == BDX_ALG_SEMIGLOBAL) {
-        cmin = c.mismatch < c.indel ? c.mismatch : c.indel;
-        if (c.has_nindel && c.nindel < cmin) cmin = c.nindel;
-    }
-    const bool n_wild = (c.algorithm == BDX_ALG_SEMIGLOBAL && c.has_nindel) || c.algorithm == BDX_ALG_HAMMING;
-    int code_of[256];
-    for (int i = 0; i < 256; ++i) code_of[i] = -1;
-    int K = 0;
-    for (int k = 0; k < npass; ++k)
-        for (uint32_t i = 0; i < c.pass[k].bc_off[c.pass[k].n_barcodes]; ++i) {
-            const uint8_t ch = c.pass[k].bc_bytes[i];
-            if (code_of[ch] < 0) code_of[ch] = K++;
-        }
-    std::vector<uint32_t> meta[2], keys[2];
-    std::vector<uint16_t> always[2];
-    int total_bc = 0, kmax = 0;
-    double flagged = 0.0;  // expected falsely flagged pairs per read of ~150 bases
-    double flag_coef = 0.0;
-    for (int k = 0; k < npass; ++k) {
-        const bdx_pass_t &p = c.pass[k];
-        if (p.n_barcodes > 32767) return BDX_OK;
-        total_bc += p.n_barcodes;
-        meta[k].assign((size_t)p.n_barcodes, 0u);
-        keys[k].assign((size_t)p.n_barcodes * 2, 0u);
-        for (int b = 0; b < p.n_barcodes; ++b) {
-            const int m = (int)(p.bc_off[b + 1] - p.bc_off[b]);
-            long long ae;
-            if (c.algorithm == BDX_ALG_EXACT) ae = 0;
-            else if (c.algorithm == BDX_ALG_HAMMING) ae = (long long)std::floor(c.max_error_rate * (double)m);
-            else ae = (long long)std::floor(c.max_error_rate * (double)(c.has_nindel ? p.bc_len_no_N[b] : m));
-            if (ae < 0) continue;  // can never be recorded: neither seeded nor swept (meta 0 and not in `always`)
-            const long long kb = ae / cmin;
-            bool wild = false;
-            for (int i = 0; i < m; ++i) wild |= n_wild && p.bc_bytes[p.bc_off[b] + i] == 'N';
-            const long long P = kb + 2;
-            const long long L = m / P;
-            if (wild || L < 4 || P > 8 || kb > 6 || (P - 1) * L > 28) {
-                always[k].push_back((uint16_t)b);
-                continue;
-            }
-            if (kb > kmax) kmax = (int)kb;
-            meta[k][b] = (uint32_t)P | ((uint32_t)L << 8);
-            uint64_t kk = 0;
-            for (long long t = 0; t < P; ++t) {
-                uint32_t key = 0;
-                for (int i = 0; i < 4; ++i) key |= (uint32_t)(code_of[p.bc_bytes[p.bc_off[b] + t * L + i]] & 3) << (2 * i);
-                kk |= (uint64_t)key << (8 * t);
-            }
-            keys[k][2 * b] = (uint32_t)kk;
-            keys[k][2 * b + 1] = (uint32_t)(kk >> 32);
-            const double hits = 147.0 / 256.0;  // occurrences of one 4-mer in the read
-            flagged += (double)(P * (P - 1) / 2) * hits * hits * (double)(2 * kb + 1) / (150.0 + m);
-            flag_coef += (double)(P * (P - 1) / 2) * (double)(2 * kb + 1);
-        }
-    }
-    const size_t n_always = always[0].size() + always[1].size();
-    if (n_always == (size_t)total_bc) return BDX_OK;
-    if (n_always * 4 > (size_t)total_bc) return BDX_OK;
-    // worth it only if clearly fewer pairs are swept (a flagged pair costs ~ a quarter of a whole-read sweep)
-    if ((flagged + (double)n_always) * 2.0 > (double)total_bc) return BDX_OK;
-    // ... and only for enough barcodes: the index forces 4..8-read tiles, whose per-tile latency costs about
-    // as much as sweeping ~40 barcodes over a whole 150-base read (measured: 1.44 us/read + 0.017 us/pair
-    // against 0.054 us/pair of the plain sweep)
-    {
-        if (total_bc < ctx->tune.diag_min_b) return BDX_OK;  // 48 unless overridden for tuning experiments
-    }
-    const double coef_keep = flag_coef;
-    size_t bytes = 0;
-    size_t o_meta[2], o_keys[2], o_always[2];
-    for (int k = 0; k < 2; ++k) {
-        o_meta[k] = bytes;
-        bytes += (meta[k].size() * 4 + 15) & ~(size_t)15;
-        o_keys[k] = bytes;
-        bytes += (keys[k].size() * 4 + 15) & ~(size_t)15;
-        o_always[k] = bytes;
-        bytes += (always[k].size() * 2 + 15) & ~(size_t)15;
-    }
-    bytes += 16;
-    std::vector<uint8_t> blob(bytes, 0);
-    for (int k = 0; k < 2; ++k) {
-        if (!meta[k].empty()) memcpy(blob.data() + o_meta[k], meta[k].data(), meta[k].size() * 4);
-        if (!keys[k].empty()) memcpy(blob.data() + o_keys[k], keys[k].data(), keys[k].size() * 4);
-        if (!always[k].empty()) memcpy(blob.data() + o_always[k], always[k].data(), always[k].size() * 2);
-    }
-    HIP_TRY(ctx, ctx->F().seed_tables.ensure(bytes));
-    HIP_TRY(ctx, hipMemcpy(ctx->F().seed_tables.p, blob.data(), bytes, hipMemcpyHostToDevice));
-    const uint8_t *base = (const uint8_t *)ctx->F().seed_tables.p;
-    sp = BdxSeedPlan{};
-    sp.diag_flag_coef = coef_keep;
-    for (int k = 0; k < 2; ++k) {
-        sp.d_dmeta[k] = (const uint32_t *)(base + o_meta[k]);
-        sp.d_dkeys[k] = (const uint32_t *)(base + o_keys[k]);
-        sp.n_always[k] = (int)always[k].size();
-        sp.d_always[k] = (const uint16_t *)(base + o_always[k]);
-    }
-    sp.q = 4;
-    sp.diag = 1;
-    sp.diag_kmax = kmax;
-    sp.rcap = 8;
-    sp.enabled = 1;
-    return BDX_OK;
-}
-
-// ---- wave-autonomous kernel (bdx_wave.hip): tables of one filter set ------------------------------
-// Eligible: single pass in the known-score class (ScoreOnly, unit costs), strict single seeds for every barcode
-// (no barcode swept unconditionally), barcodes of plain A / C / G / T up to 32 nt, and ranges that resolve to 1:n
-// for every read (then final_search_range = 1:n, max_start_pos = n, min_end_pos = 1: neither binds, DESIGN.md
-// §3.1).  Same pieces, keys and budgets as build_seed_tables / build_bitpar_tables of the set — only the symbol
-// coding differs: the kernel transcodes arithmetically, code = (byte >> 1) & 3 (A 0, C 1, T 2, G 3).
-// (developer aid: with BDX_TRACE_LAUNCH set, build_wave_tables says where it turned a filter set away)
-#define WAVE_NO() (getenv("BDX_TRACE_LAUNCH") ? (void)fprintf(stderr, "[bdx] no wave tables for set %d: bdx_abi.cpp:%d\n", ctx->cur, __LINE__) : (void)0, BDX_OK)
-int build_wave_tables(bdx_ctx *ctx) {
-    const bdx_config_t &c = ctx->cfg;
-    BdxFilterSet &F = ctx->F();
-    BdxWavePlan &wp = F.wplan;
-    wp = BdxWavePlan{};
-    const BdxBitparPlan &bp = F.bplan;
-    const BdxSeedPlan &sp = F.splan;
-    const int npass = c.is_dual ? 2 : 1;
-    if (ctx->tune.no_wave || !bp.enabled || !sp.enabled || sp.diag || bp.word_bytes != 4 || sp.n_always[0] != 0 || sp.n_always[1] != 0 ||
-        sp.q < 6 || sp.q > 8 || (c.algorithm == BDX_ALG_SEMIGLOBAL && c.has_nindel))
-        return WAVE_NO();
-    // known-score configs: the kernel replays the reducer itself (single pass); everything else in the filters' domain:
-    // "split" — it only filters, candidate masks and column windows go to the exact kernel (either pass count)
-    bool split = false;
-    for (int k = 0; k < npass; ++k) split |= !bp.known_ok[k];
-    // :hamming / :exact (always split: their scans run in the exact kernel, restricted to the hand-over windows): the
-    // budget is floor(rate * m) substitutions / 0, one operation costs 1
-    const bool sgm = c.algorithm == BDX_ALG_SEMIGLOBAL;
-    // the known classes' config condition: unit-cost SimpleScoring, or :exact (whole ranges: checked below / in build_bitpar_tables)
-    const bool kclass = (sgm && !c.has_nindel && c.match == 0 && c.mismatch == 1 && c.indel == 1) || (c.algorithm == BDX_ALG_EXACT && !getenv("BDX_NO_KNOWN_EXACT"));
-    int cmin = sgm ? (c.mismatch < c.indel ? c.mismatch : c.indel) : 1;
-    if (cmin < 1 || (sgm && c.match < 0)) return WAVE_NO();
-    const auto whole = [](const bdx_range_t &r) { return !r.start_from_end && r.start_offset <= 1 && r.end_from_end && r.end_offset >= 0; };
-    int Btot = 0, cwt = 0;
-    bool ranged = false;
-    for (int k = 0; k < npass; ++k) {
-        const bdx_pass_t &p = c.pass[k];
-        // (a ref_search_range is allowed for :semiglobal: the kernel resolves every read's column window itself, classification.jl:795-807;
-        // start / end ranges that could bind stay on the general kernel)
-        if (p.explicit_window != 0 || !whole(p.barcode_start_range) || !whole(p.barcode_end_range)) return WAVE_NO();
-        if (!whole(p.ref_search_range)) {
-            if (c.algorithm != BDX_ALG_SEMIGLOBAL) return WAVE_NO();
-            ranged = true;
-        }
-        if (p.n_barcodes < 1) return WAVE_NO();
-        for (uint32_t i = 0; i < p.bc_off[p.n_barcodes]; ++i) {
-            const uint8_t ch = p.bc_bytes[i];
-            if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T') return WAVE_NO();
-        }
-        Btot += p.n_barcodes;
-        cwt += (p.n_barcodes + 31) / 32;
-    }
-    if (Btot > 1024 || (split && cwt > 16)) return WAVE_NO();  // (split mode keeps the candidate words of a read in LDS: up to 512 barcodes)
-    const int q = sp.q;
-    struct Piece { int g, start; const uint8_t *bc; };
-    std::vector<Piece> pieces;
-    std::vector<uint32_t> meta((size_t)Btot, 0u), peq8((size_t)Btot * 9, 0u), settle((size_t)Btot, 0u);  // (stride 9: bank spread, see the kernel)
-    std::vector<uint32_t> peq8r((size_t)Btot * 9, 0u);  // the reversed barcodes (known-trim class: trim_side = 3 passes are swept right to left)
-    int track = 1 << 20, g = 0;
-    for (int k = 0; k < npass; ++k) {
-        const bdx_pass_t &p = c.pass[k];
-        for (int b = 0; b < p.n_barcodes; ++b, ++g) {
-            const int m = (int)(p.bc_off[b + 1] - p.bc_off[b]);
-            if (m < 1 || m > 32) return WAVE_NO();
-            const uint8_t *bc = p.bc_bytes + p.bc_off[b];
-            const int shift = 32 - m;
-            const uint32_t rows = m == 32 ? 0xFFFFFFFFu : (((1u << m) - 1u) << shift);
-            const uint32_t pad = ~rows;  // virtual rows below the barcode: match everything, D stays 0
-            for (int code = 0; code < 8; ++code) {
-                uint32_t mask = pad;
-                if (code < 4)
-                    for (int i = 0; i < m; ++i)
-                        if (((bc[i] >> 1) & 3) == code) mask |= 1u << (shift + i);
-                peq8[(size_t)g * 9 + code] = mask;
-                uint32_t maskr = pad;
-                if (code < 4)
-                    for (int i = 0; i < m; ++i)
-                        if (((bc[m - 1 - i] >> 1) & 3) == code) maskr |= 1u << (shift + i);
-                peq8r[(size_t)g * 9 + code] = maskr;
-            }
-            const long long ae = c.algorithm == BDX_ALG_EXACT ? 0 : (long long)std::floor(c.max_error_rate * (double)m);  // (normalisation = m)
-            if (ae < 0) {  // can never be recorded: neither seeded nor swept (budget field 255)
-                meta[(size_t)g] = (uint32_t)m | (255u << 8) | (255u << 16);
-                continue;
-            }
-            long long kb = ae / cmin;
-            if (kb > tier_cap(ctx, m)) kb = tier_cap(ctx, m);
-            if (kb > 15) return WAVE_NO();  // (a record keeps the diagonals of its hits as 2 kb + 1 bits)
-            const long long L = m / (kb + 1);
-            if (L < q) return WAVE_NO();  // (cannot happen: the set's q is the shortest piece)
-            // lone-survivor tables of the replay (bdx_wave.hip): the reference accepts a survivor with distance d iff
-            // d <= floor(max_error_rate * m) (:254) and score = d / m <= max_error_rate (:658 / :696) — both Float64, both
-            // evaluated here exactly as the device would; tier 1 settles it iff score < slo (and, with_delta, the bound
-            // slo - score >= min_delta proves "not ambiguous")
-            int dmax = 255;
-            uint32_t sbits = 0;
-            for (long long d = 0; d <= kb && d <= 15; ++d) {
-                const double score = (double)d / (double)m;
-                if (d <= ae && score <= c.max_error_rate) dmax = (int)d;
-                const double slo = bp.tier_slo[k];
-                if (score < slo) {
-                    sbits |= 1u << d;
-                    if ((slo - score) >= c.min_delta) sbits |= 1u << (16 + d);
-                }
-            }
-            settle[(size_t)g] = sbits;
-            meta[(size_t)g] = (uint32_t)m | ((uint32_t)kb << 8) | ((uint32_t)dmax << 16);
-            if (m - (int)kb - 1 < track) track = m - (int)kb - 1;
-            for (long long t = 0; t <= kb; ++t) pieces.push_back(Piece{g, (int)(t * L), bc});
-        }
-    }
-    if (pieces.empty() || pieces.size() > 8192) return WAVE_NO();
-    // the per-read record table holds eight (barcode, diagonal cluster) records: the planted one(s) plus the chance pairs must nearly always fit
-    {
-        // chance seed hits per 150-base read: the hit queue and the sweep list of a tile are sized from it (size_wave)
-        // (measured, 24-nt barcodes, 2 M reads: B = 192 / 384 / 768 at rate 0.1 — chance 1.3 / 2.6 / 5.3 — 1.99 -> 4.85, 1.49 -> 3.52,
-        // 0.94 -> 1.62 G reads/s against the general kernel; as tier 1 of rate 0.2: 0.92 -> 1.22, 0.50 -> 0.64, 0.25 -> 0.17: whatever
-        // overflows there costs a full-budget evaluation)
-        double limit = ctx->cur == 1 ? 3.0 : 6.0;
-        if (const char *e = getenv("BDX_WAVE_CHANCE")) limit = atof(e);  // (tuning experiment)
-        wp.chance = 150.0 * (double)pieces.size() / std::pow(4.0, (double)q);
-        if (wp.chance > limit) return WAVE_NO();
-    }
-    wp.q = q;
-    wp.n_barcodes = Btot;
-    wp.b0 = c.pass[0].n_barcodes;
-    wp.split = split ? 1 : 0;
-    wp.ranged = ranged ? 1 : 0;
-    wp.cand_words = split ? cwt : (c.is_dual ? 4 : 0);  // (known-score dual configs: four survivor slots of pass 1 per read in that area)
-    wp.bm_bytes = (1 << (2 * q)) / 8;
-    wp.track_from = track < 0 ? 0 : (track > 28 ? 28 : track);
-    // seed table: the bitmap is exact (one bit per key of the 4^q key space), so a hit's entry is found by the RANK of its
-    // key among the keys present (prefix count per bitmap word + a popcount); pieces that share a key are chained
-    std::vector<uint8_t> bitmap((size_t)wp.bm_bytes, 0);
-    struct Ent { uint32_t key; int g, start; };
-    std::vector<Ent> ents;
-    for (const Piece &pc : pieces) {
-        uint32_t key = 0;
-        for (int i = 0; i < q; ++i) key |= (uint32_t)((pc.bc[pc.start + i] >> 1) & 3) << (2 * i);
-        bool dup = false;  // one entry per (key, barcode, piece start)
-        for (const Ent &e : ents) dup |= e.key == key && e.g == pc.g && e.start == pc.start;
-        if (dup) continue;
-        bitmap[key >> 3] |= (uint8_t)(1u << (key & 7));
-        ents.push_back(Ent{key, pc.g, pc.start});
-    }
-    std::stable_sort(ents.begin(), ents.end(), [](const Ent &x, const Ent &y) { return x.key < y.key; });
-    std::vector<uint32_t> ent;  // heads (one per key, in key order) first, chained entries behind them
-    std::vector<uint32_t> chain;
-    {
-        std::vector<size_t> head_of;  // index into ents of every head
-        for (size_t i = 0; i < ents.size(); ++i)
-            if (i == 0 || ents[i].key != ents[i - 1].key) head_of.push_back(i);
-        const size_t D = head_of.size();
-        if (ents.size() >= 65536) return WAVE_NO();
-        ent.assign(ents.size(), 0u);
-        size_t next_free = D;
-        for (size_t h = 0; h < D; ++h) {
-            const size_t first = head_of[h], last = h + 1 < D ? head_of[h + 1] : ents.size();
-            size_t at = h;
-            for (size_t i = first; i < last; ++i) {
-                const size_t nxt = i + 1 < last ? next_free++ : 0;
-                ent[at] = (uint32_t)(ents[i].g + 1) | ((uint32_t)ents[i].start << 11) | ((uint32_t)nxt << 16);
-                at = nxt;
-            }
-        }
-    }
-    std::vector<uint16_t> rank((size_t)wp.bm_bytes / 4, 0);
-    {
-        uint32_t run = 0;
-        for (size_t w = 0; w < rank.size(); ++w) {
-            rank[w] = (uint16_t)run;
-            uint32_t word;
-            memcpy(&word, bitmap.data() + 4 * w, 4);
-            run += (uint32_t)__builtin_popcount(word);
-        }
-    }
-    wp.n_ent = (int)ent.size();
-    // the tables must leave room for at least eight waves' work areas at the smallest tile
-    if (bdx_wave_table_bytes(wp, ctx->plan.hist_entries) > 64 * 1024) return WAVE_NO();
-    auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-    const size_t o_bm = 0, o_rank = al(bitmap.size()), o_ent = o_rank + al(rank.size() * 2), o_peq = o_ent + al(ent.size() * 4),
-                 o_meta = o_peq + al(peq8.size() * 4), o_settle = o_meta + al(meta.size() * 4), o_peqr = o_settle + al(settle.size() * 4),
-                 bytes = o_peqr + al(peq8r.size() * 4);
-    std::vector<uint8_t> blob(bytes, 0);
-    memcpy(blob.data() + o_bm, bitmap.data(), bitmap.size());
-    memcpy(blob.data() + o_rank, rank.data(), rank.size() * 2);
-    memcpy(blob.data() + o_ent, ent.data(), ent.size() * 4);
-    memcpy(blob.data() + o_peq, peq8.data(), peq8.size() * 4);
-    memcpy(blob.data() + o_meta, meta.data(), meta.size() * 4);
-    memcpy(blob.data() + o_settle, settle.data(), settle.size() * 4);
-    memcpy(blob.data() + o_peqr, peq8r.data(), peq8r.size() * 4);
-    HIP_TRY(ctx, F.wave_tables.ensure(bytes));
-    HIP_TRY(ctx, hipMemcpy(F.wave_tables.p, blob.data(), bytes, hipMemcpyHostToDevice));
-    const uint8_t *base = (const uint8_t *)F.wave_tables.p;
-    wp.d_bitmap = base + o_bm;
-    wp.d_rank = (const uint16_t *)(base + o_rank);
-    wp.d_ent = (const uint32_t *)(base + o_ent);
-    wp.d_peq8 = (const uint32_t *)(base + o_peq);
-    wp.d_meta = (const uint32_t *)(base + o_meta);
-    wp.d_settle = (const uint32_t *)(base + o_settle);
-    wp.d_peq8r = (const uint32_t *)(base + o_peqr);
-    wp.enabled = 1;
-    // Known-trim class: the known-score conditions with a trim side in some pass (either pass count, no summary).  What a trim
-    // side makes observable is one position per pass — trim_side = 5: the alignment's END (keep_start = end + 1,
-    // classification.jl:912-914; the reference keeps the leftmost end of the best score, :142-153: strict `<`); trim_side = 3: its
-    // START (keep_end = max(1, start) - 1, :910-911; the largest start among the alignments of the best score, :142-153 tie rule
-    // + :310-321 origin order) — and the sweep delivers both (bdx_wave.hip, KEND: the lowering mask of a left-to-right sweep /
-    // of a right-to-left sweep with the reversed barcode).  Such a config gets its verdicts from the non-split kernel whenever
-    // the caller does not ask for per-pass start positions (nor for end positions of a trim_side = 3 pass).
-    F.wplan_k = BdxWavePlan{};
-    bool trims_ok = true;
-    for (int k = 0; k < npass; ++k) trims_ok = trims_ok && c.pass[k].explicit_window != BDX_WINDOW_ALIGN_ONE;
-    if (split && kclass && trims_ok && !c.need_traceback &&
-        !ctx->tune.no_known && !ctx->tune.no_kend) {
-        bool fits = true;  // entry = barcode << 22 | d << 16 | position key
-        for (uint32_t x : meta) fits = fits && (((x >> 8) & 255u) == 255u || ((x >> 8) & 255u) < 64u);
-        if (fits && c.pass[0].n_barcodes <= 1023 && (!c.is_dual || c.pass[1].n_barcodes <= 1023)) {
-            F.wplan_k = wp;
-            F.wplan_k.split = 0;
-            F.wplan_k.cand_words = c.is_dual ? 4 : 0;  // (the four survivor slots of pass 1)
-            F.wplan_k.kend = 1;
-            for (int k = 0; k < npass; ++k)
-                if (c.pass[k].trim_side == 3) F.wplan_k.kend = 2;  // (reversed sweeps: bdx_wave_rev.hip)
-        }
-    }
-    // Known-alignment class: the same conditions with `summary` allowed — start AND end of every pass's winner come out of one
-    // more (anchored) sweep per pass and read, so per-pass positions and the DemuxStats histograms need no exact kernel either
-    // (bdx_wave_aln.hip); taken per launch when the caller wants positions the known-trim class does not know, or statistics.
-    F.wplan_a = BdxWavePlan{};
-    // (:exact reports the occurrence's positions whatever the output policy, classification.jl:485-548: its score-only form only
-    // serves callers that do not ask for them — the others take this class per launch, bdx_classify_device)
-    if ((split || c.algorithm == BDX_ALG_EXACT) && kclass && trims_ok && !ctx->tune.no_known &&
-        !ctx->tune.no_kend && !getenv("BDX_NO_KALN")) {
-        bool fits = true;
-        for (uint32_t x : meta) fits = fits && (((x >> 8) & 255u) == 255u || ((x >> 8) & 255u) < 64u);
-        if (fits && c.pass[0].n_barcodes <= 1023 && (!c.is_dual || c.pass[1].n_barcodes <= 1023)) {
-            F.wplan_a = wp;
-            F.wplan_a.split = 0;
-            F.wplan_a.cand_words = c.is_dual ? 4 : 0;
-            F.wplan_a.kend = 3;
-        }
-    }
-    return BDX_OK;
-}
-
-#undef WAVE_NO
 // Geometry of the wave kernel for a batch: the tile size and workgroup shape that keep the most waves resident
 // per compute unit (tables once per workgroup + one work area per wave within 160 KiB, at most 16 waves: the
 // kernel is compiled for four waves per SIMD).  false: this batch runs the general kernel.
@@ -1030,217 +221,6 @@ bool size_wave_win(bdx_ctx *ctx, BdxWavePlan &wp, int read_len, long long n_read
     wp.scan_gpr = 0;
     wp.winm = 1;
     return true;
-}
-
-// ---- pairs mode of the wave kernel (bdx_pairs.hip): tables of the FULL-budget set --------------------------------
-// Between tier 1 and the general kernel of a tiered config: the reads tier 1 lists are gathered into slots and filtered
-// by the two-intact-pieces lemma on barcode masks (one table entry per (piece, 4-base key): the barcodes whose piece has
-// that key).  Eligible: the conditions of build_wave_tables on alphabet, lengths and ranges; every barcode's budget kb
-// at most 4 with 4 (kb + 2) <= m (kb + 2 disjoint 4-base pieces at offsets 0, 4, ..); at most 128 barcodes.
-int build_pair_tables(bdx_ctx *ctx) {
-    const bdx_config_t &c = ctx->cfg;
-    BdxFilterSet &F = ctx->F();
-    BdxWavePlan &wp = F.pplan;
-    wp = BdxWavePlan{};
-    const BdxBitparPlan &bp = F.bplan;
-    const int npass = c.is_dual ? 2 : 1;
-    // (a capped set gets pair tables only as the pairs tier: budgets capped at tier_cap_fixed operations)
-    if (ctx->tune.no_wave || ctx->tune.no_pairs || !bp.enabled || bp.word_bytes != 4 || (bp.tier_capped && ctx->tier_cap_fixed < 0) || c.filter != BDX_FILTER_AUTO ||
-        (c.algorithm == BDX_ALG_SEMIGLOBAL && c.has_nindel))
-        return BDX_OK;
-    bool split = false;
-    for (int k = 0; k < npass; ++k) split |= !bp.known_ok[k];
-    const bool sgm = c.algorithm == BDX_ALG_SEMIGLOBAL;
-    const bool kclass = (sgm && !c.has_nindel && c.match == 0 && c.mismatch == 1 && c.indel == 1) || (c.algorithm == BDX_ALG_EXACT && !getenv("BDX_NO_KNOWN_EXACT"));
-    const int cmin = sgm ? (c.mismatch < c.indel ? c.mismatch : c.indel) : 1;
-    if (cmin < 1 || (sgm && c.match < 0)) return BDX_OK;
-    // the pairs tier (capped set): the filter only has to be lossless for alignments of COST <= cap x cmin — a barcode it does not
-    // flag costs more, i.e. at least (cap + 1) cmin = the tier's slo (costs are integers; the tier exists for mismatch = cmin = 1)
-    const long long cost_cap = (ctx->cur == 1 && ctx->tier_cap_fixed >= 0) ? (long long)ctx->tier_cap_fixed * cmin : (1LL << 40);
-    const auto whole = [](const bdx_range_t &r) { return !r.start_from_end && r.start_offset <= 1 && r.end_from_end && r.end_offset >= 0; };
-    int Btot = 0, cwt = 0;
-    bool ranged = false;
-    for (int k = 0; k < npass; ++k) {
-        const bdx_pass_t &p = c.pass[k];
-        // (a ref_search_range is allowed for :semiglobal: the kernel resolves every read's column window itself, classification.jl:795-807;
-        // start / end ranges that could bind stay on the general kernel)
-        if (p.explicit_window != 0 || !whole(p.barcode_start_range) || !whole(p.barcode_end_range)) return BDX_OK;
-        if (!whole(p.ref_search_range)) {
-            if (c.algorithm != BDX_ALG_SEMIGLOBAL) return BDX_OK;
-            ranged = true;
-        }
-        if (p.n_barcodes < 1) return BDX_OK;
-        for (uint32_t i = 0; i < p.bc_off[p.n_barcodes]; ++i) {
-            const uint8_t ch = p.bc_bytes[i];
-            if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T') return BDX_OK;
-        }
-        Btot += p.n_barcodes;
-        cwt += (p.n_barcodes + 31) / 32;
-    }
-    // more than 128 barcodes (known-score configs only: split mode keeps four mask words per read): groups of 128 barcodes,
-    // each with its own piece tables of four-word masks
-    if (Btot > 512 || (split && (cwt > 4 || Btot > 128))) return BDX_OK;
-    const int groups = (Btot + 127) / 128;
-    int nw = groups > 1 ? 4 : (Btot + 31) / 32;
-    if (const char *e = getenv("BDX_PAIRS_NW")) nw = atoi(e) > nw ? atoi(e) : nw;  // (tuning experiment)
-    if (nw > 4) nw = 4;
-    const int estride = nw <= 2 ? 8 : 16;
-    std::vector<uint32_t> meta((size_t)Btot, 0u), peq8((size_t)Btot * 9, 0u), settle((size_t)Btot, 0u), peq8r((size_t)Btot * 9, 0u);
-    int kmax = 0, track = 1 << 20, mmin = 1 << 20, g = 0;
-    struct Bc { int g, m, kb; const uint8_t *bc; };
-    std::vector<Bc> bcs;
-    // SAME-DIAGONAL variants (split configs whose indels cost more than their mismatches — the reference's demo2 options:
-    // mismatch 1, indel 2, budget 6 of 24): an alignment with g indels lies on at most g + 1 diagonals and has at most
-    // e(g) = g + floor((ae - g indel) / mismatch) operations; with P disjoint pieces, P - e(g) >= g + 2 for every possible g
-    // puts two intact pieces on ONE diagonal (an intact piece cannot span an indel) — far more selective than "two pieces
-    // within kb diagonals", and valid beyond the classic variant's 4 (kb + 2) <= m.  Tried per piece length: 4 bases
-    // (six pieces), then 3 (eight).  The alignment then lies within g_max columns of that diagonal (`spread`).
-    // Order of preference: six 4-base pieces on one diagonal (strictly more selective than the classic variant), the classic
-    // variant (two 4-base pieces within kb diagonals) where its conditions hold, eight 3-base pieces on one diagonal.
-    bool classic_ok = true;
-    for (int k = 0; k < npass; ++k)
-        for (int b = 0; b < c.pass[k].n_barcodes; ++b) {
-            const int m = (int)(c.pass[k].bc_off[b + 1] - c.pass[k].bc_off[b]);
-            const long long ae = std::min(cost_cap, c.algorithm == BDX_ALG_EXACT ? 0 : (long long)std::floor(c.max_error_rate * (double)m));
-            if (ae >= 0 && (ae / cmin > 4 || 4 * (ae / cmin + 2) > m)) classic_ok = false;
-        }
-    int sd_pl = 0, sd_spread = 0;
-    if (split && sgm && c.mismatch >= 1 && c.indel >= 1 && groups == 1) {
-        for (int pl = 4; pl >= 3 && !sd_pl; --pl) {
-            if (pl == 3 && classic_ok) break;
-            bool ok = true;
-            int spread = 0;
-            for (int k = 0; k < npass && ok; ++k) {
-                const bdx_pass_t &p = c.pass[k];
-                for (int b = 0; b < p.n_barcodes && ok; ++b) {
-                    const int m = (int)(p.bc_off[b + 1] - p.bc_off[b]);
-                    const long long ae = std::min(cost_cap, (long long)std::floor(c.max_error_rate * (double)m));
-                    if (ae < 0) continue;
-                    const int P = std::min(pl == 4 ? 6 : 8, m / pl);
-                    const long long gmax = ae / c.indel;
-                    for (long long gg = 0; gg <= gmax && ok; ++gg) {
-                        const long long e = gg + (ae - gg * c.indel) / c.mismatch;
-                        ok = (long long)P - e >= gg + 2;
-                    }
-                    if (gmax > spread) spread = (int)gmax;
-                    if (ae / cmin > 15 || m - (int)(ae / cmin) - 1 < 12) ok = false;  // (sweep budget field / score tracking from column 12)
-                }
-            }
-            if (ok && spread <= 8) {
-                sd_pl = pl;
-                sd_spread = spread;
-            }
-        }
-    }
-    for (int k = 0; k < npass; ++k) {
-        const bdx_pass_t &p = c.pass[k];
-        for (int b = 0; b < p.n_barcodes; ++b, ++g) {
-            const int m = (int)(p.bc_off[b + 1] - p.bc_off[b]);
-            if (m < 1 || m > 32) return BDX_OK;
-            const uint8_t *bc = p.bc_bytes + p.bc_off[b];
-            const int shift = 32 - m;
-            const uint32_t rows = m == 32 ? 0xFFFFFFFFu : (((1u << m) - 1u) << shift);
-            const uint32_t pad = ~rows;
-            for (int code = 0; code < 8; ++code) {
-                uint32_t mask = pad;
-                if (code < 4)
-                    for (int i = 0; i < m; ++i)
-                        if (((bc[i] >> 1) & 3) == code) mask |= 1u << (shift + i);
-                peq8[(size_t)g * 9 + code] = mask;
-                uint32_t maskr = pad;  // (the reversed barcode: known-trim class, see build_wave_tables)
-                if (code < 4)
-                    for (int i = 0; i < m; ++i)
-                        if (((bc[m - 1 - i] >> 1) & 3) == code) maskr |= 1u << (shift + i);
-                peq8r[(size_t)g * 9 + code] = maskr;
-            }
-            const long long ae = std::min(cost_cap, c.algorithm == BDX_ALG_EXACT ? 0 : (long long)std::floor(c.max_error_rate * (double)m));
-            if (ae < 0) {  // can never be recorded: in no table entry, never swept
-                meta[(size_t)g] = (uint32_t)m | (255u << 8) | (255u << 16);
-                continue;
-            }
-            const long long kb = ae / cmin;
-            if (!sd_pl && (kb > 4 || 4 * (kb + 2) > m)) return BDX_OK;
-            int dmax = 255;
-            for (long long d = 0; d <= kb; ++d)  // lone-survivor accept threshold of the replay, as in build_wave_tables
-                if (d <= ae && (double)d / (double)m <= c.max_error_rate) dmax = (int)d;
-            meta[(size_t)g] = (uint32_t)m | ((uint32_t)kb << 8) | ((uint32_t)dmax << 16) | ((uint32_t)sd_spread << 24);
-            if ((int)kb > kmax) kmax = (int)kb;
-            if (m - (int)kb - 1 < track) track = m - (int)kb - 1;
-            if (m < mmin) mmin = m;
-            bcs.push_back(Bc{g, m, (int)kb, bc});
-        }
-    }
-    if (bcs.empty() || track < 12) return BDX_OK;
-    const int KB = sd_pl == 4 ? 8 : sd_pl == 3 ? 9 : kmax <= 3 ? 3 : 4;  // (the kernel's variant number)
-    const int PL = sd_pl ? sd_pl : 4, P = sd_pl == 4 ? 6 : sd_pl == 3 ? 8 : KB + 2, NK = 1 << (2 * PL);
-    std::vector<uint32_t> tab((size_t)groups * P * NK * (size_t)(estride / 4), 0u);
-    for (const Bc &x : bcs) {
-        const int np = sd_pl ? std::min(P, x.m / PL) : x.kb + 2;  // pieces of this barcode
-        for (int t = 0; t < np; ++t) {
-            uint32_t key = 0;
-            for (int i = 0; i < PL; ++i) key |= (uint32_t)((x.bc[PL * t + i] >> 1) & 3) << (2 * i);
-            const int grp = x.g >> 7, gl = x.g & 127;
-            tab[(((size_t)grp * P + (size_t)t) * NK + key) * (size_t)(estride / 4) + (size_t)(gl >> 5)] |= 1u << (gl & 31);
-        }
-    }
-    wp.q = 4;
-    wp.n_barcodes = Btot;
-    wp.b0 = c.pass[0].n_barcodes;
-    wp.split = split ? 1 : 0;
-    wp.bm_bytes = (int)(tab.size() * 4);
-    wp.n_ent = 0;
-    wp.track_from = track > 28 ? 28 : track;
-    wp.pairs_kb = KB;
-    wp.pairs_spread = sd_pl ? sd_spread : KB;
-    wp.nw = nw;
-    wp.groups = groups;
-    wp.ranged = ranged ? 1 : 0;
-    wp.cand_words = split ? cwt : (c.is_dual ? 4 : 0);  // (known-score dual configs: the survivor slots of pass 1)
-    if (bdx_wave_table_bytes(wp, ctx->plan.hist_entries) > 112 * 1024) return BDX_OK;  // (at least four waves' work areas must fit beside the tables)
-    auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-    const size_t o_tab = 0, o_peq = al(tab.size() * 4), o_meta = o_peq + al(peq8.size() * 4), o_settle = o_meta + al(meta.size() * 4),
-                 o_peqr = o_settle + al(settle.size() * 4), bytes = o_peqr + al(peq8r.size() * 4);
-    std::vector<uint8_t> blob(bytes, 0);
-    memcpy(blob.data() + o_tab, tab.data(), tab.size() * 4);
-    memcpy(blob.data() + o_peq, peq8.data(), peq8.size() * 4);
-    memcpy(blob.data() + o_meta, meta.data(), meta.size() * 4);
-    memcpy(blob.data() + o_settle, settle.data(), settle.size() * 4);
-    memcpy(blob.data() + o_peqr, peq8r.data(), peq8r.size() * 4);
-    HIP_TRY(ctx, F.pair_tables.ensure(bytes));
-    HIP_TRY(ctx, hipMemcpy(F.pair_tables.p, blob.data(), bytes, hipMemcpyHostToDevice));
-    const uint8_t *base = (const uint8_t *)F.pair_tables.p;
-    wp.d_bitmap = base + o_tab;
-    wp.d_rank = (const uint16_t *)base;  // (never read)
-    wp.d_ent = (const uint32_t *)base;
-    wp.d_peq8 = (const uint32_t *)(base + o_peq);
-    wp.d_meta = (const uint32_t *)(base + o_meta);
-    wp.d_settle = (const uint32_t *)(base + o_settle);
-    wp.d_peq8r = (const uint32_t *)(base + o_peqr);
-    ctx->pair_mmin = mmin;
-    wp.enabled = 1;
-    // known-trim class (see build_wave_tables): the listed reads of a config with trim sides get verdict and keep range from
-    // the pairs mode too, in its non-split form
-    F.pplan_k = BdxWavePlan{};
-    bool trims_ok = true;
-    for (int k = 0; k < npass; ++k) trims_ok = trims_ok && c.pass[k].explicit_window != BDX_WINDOW_ALIGN_ONE;
-    if (split && kclass && trims_ok && !c.need_traceback &&
-        !ctx->tune.no_known && !ctx->tune.no_kend && groups == 1 && wp.pairs_kb <= 4) {  // (the same-diagonal variants only exist in split mode)
-        F.pplan_k = wp;
-        F.pplan_k.split = 0;
-        F.pplan_k.cand_words = c.is_dual ? 4 : 0;
-        F.pplan_k.kend = 1;
-        for (int k = 0; k < npass; ++k)
-            if (c.pass[k].trim_side == 3) F.pplan_k.kend = 2;
-    }
-    F.pplan_a = BdxWavePlan{};  // known-alignment class (build_wave_tables): the same with `summary` allowed
-    if (split && kclass && trims_ok && !ctx->tune.no_known &&
-        !ctx->tune.no_kend && !getenv("BDX_NO_KALN") && groups == 1 && wp.pairs_kb <= 4) {
-        F.pplan_a = wp;
-        F.pplan_a.split = 0;
-        F.pplan_a.cand_words = c.is_dual ? 4 : 0;
-        F.pplan_a.kend = 3;
-    }
-    return BDX_OK;
 }
 
 // Geometry of the pairs mode for a batch: 16-read tiles of slots of `read_len` rounded up to 16 bytes.
@@ -1477,69 +457,91 @@ int validate(const bdx_config_t *c) {
     return BDX_OK;
 }
 
-int upload_tables(bdx_ctx *ctx) {
-    const bdx_config_t &c = ctx->cfg;
-    BdxDevCfg &d = ctx->dev;
-    d.algorithm = c.algorithm;
-    d.is_dual = c.is_dual != 0;
-    d.max_error_rate = c.max_error_rate;
-    d.min_delta = c.min_delta;
-    d.match = c.match;
-    d.mismatch = c.mismatch;
-    d.indel = c.indel;
-    d.has_nindel = c.has_nindel != 0;
-    d.nindel = c.has_nindel ? c.nindel : 0;
-    d.need_traceback = c.need_traceback != 0;
-    d.force_lds_dp = ctx->tune.lds_dp;
-    d.band_kb[0] = d.band_kb[1] = -1;
-    d.band_m = 0;
-    d.dense_w = 0;
-    d.band_lb[0] = d.band_lb[1] = 0;
-    d.max_m = 1;
-    d.any_traceback = d.need_traceback;
-    const int npass = d.is_dual ? 2 : 1;
+// One table on the device: `bytes` of src in a buffer of at least bytes + room.
+int upload(bdx_ctx *ctx, DevBuf &buf, const void *src, size_t bytes, size_t room = 0) {
+    HIP_TRY(ctx, buf.ensure(bytes + room));
+    HIP_TRY(ctx, hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice));
+    return BDX_OK;
+}
+
+const uint8_t *at(const DevBuf &t, size_t off) { return (const uint8_t *)t.p + off; }
+
+void bind(BdxBitparPlan &bp, const DevBuf &t, const BdxBitparOff &o, int npass) {
+    if (!bp.enabled) return;
+    bp.d_lut = at(t, o.lut);
+    for (int k = 0; k < npass; ++k) {
+        bp.d_peq[k] = at(t, o.peq[k]);
+        bp.d_pvinit[k] = at(t, o.pvinit[k]);
+        bp.d_kb[k] = (const int32_t *)at(t, o.kb[k]);
+    }
+}
+
+void bind(BdxSeedPlan &sp, const DevBuf &t, const BdxSeedOff &o) {
+    if (!sp.enabled) return;
+    if (!sp.diag) {
+        sp.d_bitmap = (const uint32_t *)at(t, o.bitmap);
+        sp.d_hash = (const uint32_t *)at(t, o.hash);
+        sp.d_hash_ps = at(t, o.hash_ps);
+    }
     for (int k = 0; k < 2; ++k) {
-        BdxDevPass &P = d.pass[k];
-        memset(&P, 0, sizeof P);
-        if (k >= npass) continue;
+        sp.d_always[k] = (const uint16_t *)at(t, o.always[k]);
+        if (!sp.diag) continue;
+        sp.d_dmeta[k] = (const uint32_t *)at(t, o.dmeta[k]);
+        sp.d_dkeys[k] = (const uint32_t *)at(t, o.dkeys[k]);
+    }
+}
+
+void bind(BdxWavePlan &wp, const DevBuf &t, const BdxWaveOff &o) {
+    if (!wp.enabled) return;
+    wp.d_bitmap = at(t, o.bitmap);
+    wp.d_rank = (const uint16_t *)at(t, o.rank);
+    wp.d_ent = (const uint32_t *)at(t, o.ent);
+    wp.d_peq8 = (const uint32_t *)at(t, o.peq8);
+    wp.d_meta = (const uint32_t *)at(t, o.meta);
+    wp.d_settle = (const uint32_t *)at(t, o.settle);
+    wp.d_peq8r = (const uint32_t *)at(t, o.peq8r);
+}
+
+// Everything the planner produced goes to the device here: the barcode arrays, the counters, and per filter set every
+// table a plan left enabled refers to (also one a rejected tier attempt left behind: plan_call walks both sets); then
+// the plans' pointers are bound from base + offset.
+int upload_plan(bdx_ctx *ctx, const bdx_config_t &c, const BdxPlanOut &po) {
+    ctx->dev = po.dev;
+    ctx->plan = po.plan;
+    static_cast<BdxPlanChoice &>(*ctx) = po;
+    const int npass = c.is_dual ? 2 : 1;
+    int rc = BDX_OK;
+    for (int k = 0; k < npass; ++k) {
         const bdx_pass_t &p = c.pass[k];
-        P.ref_search = cvt_range(p.ref_search_range);
-        P.bc_start = cvt_range(p.barcode_start_range);
-        P.bc_end = cvt_range(p.barcode_end_range);
-        P.trim_side = p.trim_side;
-        P.n_barcodes = p.n_barcodes;
-        P.cand_words = (p.n_barcodes + 31) / 32;
-        P.explicit_window = p.explicit_window;
-        P.win_first = p.win_first;
-        P.win_last = p.win_last;
-        P.win_max_start = p.win_max_start_pos;
-        P.win_min_end = p.win_min_end_pos;
-        if (p.trim_side != 0) d.any_traceback = 1;
-        const size_t nbytes = p.bc_off[p.n_barcodes];
-        for (int i = 0; i < p.n_barcodes; ++i) {
-            const int m = (int)(p.bc_off[i + 1] - p.bc_off[i]);
-            if (m > d.max_m) d.max_m = m;
-        }
-        HIP_TRY(ctx, ctx->bc_bytes[k].ensure(nbytes + 16));
-        HIP_TRY(ctx, ctx->bc_off[k].ensure((size_t)(p.n_barcodes + 1) * 4));
-        HIP_TRY(ctx, ctx->bc_nn[k].ensure((size_t)p.n_barcodes * 4));
-        HIP_TRY(ctx, hipMemcpy(ctx->bc_bytes[k].p, p.bc_bytes, nbytes, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(ctx->bc_off[k].p, p.bc_off, (size_t)(p.n_barcodes + 1) * 4, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(ctx->bc_nn[k].p, p.bc_len_no_N, (size_t)p.n_barcodes * 4, hipMemcpyHostToDevice));
+        BdxDevPass &P = ctx->dev.pass[k];
+        if ((rc = upload(ctx, ctx->bc_bytes[k], p.bc_bytes, p.bc_off[p.n_barcodes], 16)) != BDX_OK) return rc;
+        if ((rc = upload(ctx, ctx->bc_off[k], p.bc_off, (size_t)(p.n_barcodes + 1) * 4)) != BDX_OK) return rc;
+        if ((rc = upload(ctx, ctx->bc_nn[k], p.bc_len_no_N, (size_t)p.n_barcodes * 4)) != BDX_OK) return rc;
         P.bc_bytes = (const uint8_t *)ctx->bc_bytes[k].p;
         P.bc_off = (const uint32_t *)ctx->bc_off[k].p;
         P.bc_len_no_N = (const int32_t *)ctx->bc_nn[k].p;
     }
-    d.counts_stride2 = d.is_dual ? (d.pass[1].n_barcodes > 1 ? d.pass[1].n_barcodes : 1) : 1;
-    const long long nc = 4LL + (long long)d.pass[0].n_barcodes * d.counts_stride2;
-    if (nc > (1LL << 28)) return fail(ctx, BDX_E_INVALID, "sample_counts table too large (%lld entries)", nc);
-    d.n_counts = (int)nc;
-    // allowed_error = floor(rate * normalisation) must stay inside the int32 DP domain
-    if (std::fabs(c.max_error_rate) * (double)d.max_m >= (double)(1 << 27))
-        return fail(ctx, BDX_E_INVALID, "max_error_rate * barcode length exceeds the supported range");
-    HIP_TRY(ctx, ctx->counts_own.ensure((size_t)d.n_counts * 8));
-    HIP_TRY(ctx, hipMemset(ctx->counts_own.p, 0, (size_t)d.n_counts * 8));
+    HIP_TRY(ctx, ctx->counts_own.ensure((size_t)ctx->dev.n_counts * 8));
+    HIP_TRY(ctx, hipMemset(ctx->counts_own.p, 0, (size_t)ctx->dev.n_counts * 8));
     ctx->counts = (unsigned long long *)ctx->counts_own.p;
+    for (int s = 0; s < 2; ++s) {
+        BdxFilterSet &F = ctx->fs[s];
+        const BdxPlanSet &P = po.fs[s];
+        static_cast<BdxSetPlans &>(F) = P;
+        const struct { DevBuf &buf; const BdxBlob &blob; int used; } tables[5] = {
+            {F.bp_tables, P.bp_tables, F.bplan.enabled},
+            {F.seed_tables, P.seed_tables, F.splan.enabled},
+            {F.seed_tables_alt, P.seed_tables_alt, F.splan_alt.enabled},
+            {F.wave_tables, P.wave_tables, F.wplan.enabled | F.wplan_k.enabled | F.wplan_a.enabled},
+            {F.pair_tables, P.pair_tables, F.pplan.enabled | F.pplan_k.enabled | F.pplan_a.enabled}};
+        for (const auto &t : tables)
+            if (t.used && (rc = upload(ctx, t.buf, t.blob.bytes.data(), t.blob.bytes.size())) != BDX_OK) return rc;
+        bind(F.bplan, F.bp_tables, P.bp_off, npass);
+        bind(F.splan, F.seed_tables, P.seed_off);
+        bind(F.splan_alt, F.seed_tables_alt, P.seed_alt_off);
+        for (BdxWavePlan *wp : {&F.wplan, &F.wplan_k, &F.wplan_a}) bind(*wp, F.wave_tables, P.wave_off);
+        for (BdxWavePlan *wp : {&F.pplan, &F.pplan_k, &F.pplan_a}) bind(*wp, F.pair_tables, P.pair_off);
+    }
     return BDX_OK;
 }
 
@@ -1640,7 +642,8 @@ int init_stats(bdx_ctx *ctx) {
             const bdx_range_t &r = c.pass[p].ref_search_range;
             sg_window = sg_window || r.start_from_end || r.start_offset > 1 || c.pass[p].explicit_window != 0;
         }
-    ctx->st_len_fixed = (ctx->plan.clean || ctx->plan.band_roll || c.algorithm != BDX_ALG_SEMIGLOBAL) && !sg_window;
+    // (band_roll_off: inside the rolling band's class, though without a filter the exact kernel keeps its LDS columns)
+    ctx->st_len_fixed = (ctx->plan.clean || ctx->plan.band_roll || ctx->band_roll_off || c.algorithm != BDX_ALG_SEMIGLOBAL) && !sg_window;
     ctx->st_len_rows = ctx->st_len_fixed ? 2 * ctx->dev.max_m + 2 : 0;
     for (int p = 0; p < npass; ++p)
         for (int w = (ctx->st_len_fixed ? 1 : 2); w < 3; ++w) {
@@ -1679,7 +682,7 @@ int32_t bdx_create(const bdx_config_t *config, bdx_ctx **out) {
     if (!ctx) return fail(nullptr, BDX_E_DEVICE, "out of host memory");
     ctx->cfg = *config;
     ctx->device = config->device;
-    ctx->tune = read_tuning();  // the environment is consulted here and nowhere else
+    ctx->tune = read_tuning();  // the environment is consulted here and nowhere else (the planner gets this struct)
     auto bail = [&](int code) {
         g_create_error = ctx->err;
         bdx_destroy(ctx);
@@ -1700,154 +703,24 @@ int32_t bdx_create(const bdx_config_t *config, bdx_ctx **out) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus < 1) cus = 256;
         ctx->n_cu = ctx->tune.cu_count > 0 ? ctx->tune.cu_count : cus;
     }
-    rc = upload_tables(ctx);
-    if (rc != BDX_OK) return bail(rc);
+    {
+        BdxPlanOut po;  // host only: which kernels, which tables (bdx_plan.cpp); needs the caller's host tables
+        rc = bdx_plan(*config, ctx->tune, ctx->n_cu, po);
+        if (rc != BDX_OK) {
+            ctx->err = po.err;
+            return bail(rc);
+        }
+        rc = upload_plan(ctx, *config, po);
+        if (rc != BDX_OK) return bail(rc);
+    }
     if (ctx->d_dbg.ensure(256) != hipSuccess || hipMemset(ctx->d_dbg.p, 0, 256) != hipSuccess) {
         ctx->err = "hipMalloc failed";
         return bail(BDX_E_DEVICE);
     }
     ctx->dev.dbg_rejected = (unsigned int *)ctx->d_dbg.p;
-    rc = plan_generic(ctx);  // needs the caller's host tables: run before they are dropped
-    if (rc != BDX_OK) return bail(rc);
-    ctx->plan.n_cu = ctx->n_cu;
     rc = init_stats(ctx);
     if (rc != BDX_OK) return bail(rc);
-    rc = build_bitpar_tables(ctx);
-    if (rc != BDX_OK) return bail(rc);
-    if (ctx->plan.band_roll && !ctx->F().bplan.enabled) {  // no filter, no hand-over windows: the rolling band would walk whole windows
-        ctx->band_roll_off = true;
-        rc = plan_generic(ctx);
-        if (rc != BDX_OK) return bail(rc);
-        ctx->plan.n_cu = ctx->n_cu;
-    }
-    rc = build_seed_tables(ctx, true);
-    if (rc != BDX_OK) return bail(rc);
-    rc = build_diag_tables(ctx);
-    if (rc != BDX_OK) return bail(rc);
-    if (!ctx->F().splan.enabled) {  // neither: moderately selective single seeds still beat sweeping every pair
-        rc = build_seed_tables(ctx, false);
-        if (rc != BDX_OK) return bail(rc);
-    } else if (ctx->F().splan.diag) {  // the fallback of size_bitpar when the index does not fit a batch
-        rc = build_seed_tables(ctx, false, true);
-        if (rc != BDX_OK) return bail(rc);
-    }
-    rc = build_wave_tables(ctx);
-    if (rc != BDX_OK) return bail(rc);
-    rc = build_pair_tables(ctx);
-    if (rc != BDX_OK) return bail(rc);
-    // tier 1 (capped budgets, strict single seeds) beside a full-budget set that is NOT already strict single seeds
-    {
-        const BdxFilterSet &full = ctx->fs[0];
-        const bool strict_full = full.splan.enabled && !full.splan.diag && full.splan.q >= 7;
-        // (the unit-level API's hand-made windows stay on the plain path)
-        bool plain_windows = true;
-        for (int k = 0; k < (config->is_dual ? 2 : 1); ++k) {
-            plain_windows = plain_windows && config->pass[k].explicit_window == 0;
-            // N-scoring with real wildcards: position-dependent indel costs — "an alignment's result does not depend on
-            // the running threshold" is only argued (and fuzzed) for uniform costs; such configs stay on one tier
-            if (config->algorithm == BDX_ALG_SEMIGLOBAL && config->has_nindel)
-                for (uint32_t i = 0; i < config->pass[k].bc_off[config->pass[k].n_barcodes]; ++i)
-                    if (config->pass[k].bc_bytes[i] == 'N') plain_windows = false;
-        }
-        if (full.bplan.enabled && plain_windows && !strict_full && !ctx->tune.no_tier && config->filter == BDX_FILTER_AUTO) {
-            // Piece length behind tier 1's capped budgets, cap(m) = m / q - 1: 8-base seeds are the most selective; 7- or
-            // 6-base pieces raise the cap of some lengths by one (14-15 and 21-23 bases with q = 7, 12-13 with q = 6), so
-            // that tier 1 settles reads with one more error and tier 0 — a plain sweep or the two-intact-pieces kernel —
-            // sees far fewer reads (m = 14, B = 96, rate 0.2: 444 -> 724 M reads/s), as long as the chance hits per
-            // read stay few and no cap goes beyond 2 (measured: caps of 3 — m = 24 with q = 6, m = 28 with q = 7 — cost
-            // more in tier 1 than they save in tier 0, at 24 and at 96 barcodes).
-            {
-                int cmin = 1;
-                if (config->algorithm == BDX_ALG_SEMIGLOBAL) {
-                    cmin = config->mismatch < config->indel ? config->mismatch : config->indel;
-                    if (config->has_nindel && config->nindel < cmin) cmin = config->nindel;
-                    if (cmin < 1) cmin = 1;
-                }
-                long long best_caps = -1;
-                int best_q = 8;
-                const double limit[9] = {0, 0, 0, 0, 0, 0, 8.0, 4.0, 1e30};
-                for (int q = 8; q >= 6; --q) {
-                    long long caps = 0, pieces = 0, cap_max = 0;
-                    for (int k = 0; k < (config->is_dual ? 2 : 1); ++k)
-                        for (int b = 0; b < config->pass[k].n_barcodes; ++b) {
-                            const int m = (int)(config->pass[k].bc_off[b + 1] - config->pass[k].bc_off[b]);
-                            const double norm = (config->algorithm == BDX_ALG_SEMIGLOBAL && config->has_nindel) ? (double)config->pass[k].bc_len_no_N[b] : (double)m;
-                            const long long ae = config->algorithm == BDX_ALG_EXACT ? 0 : (long long)std::floor(config->max_error_rate * norm);
-                            if (ae < 0) continue;
-                            long long cap = m / q - 1;
-                            if (cap < 0) cap = 0;
-                            if (cap > ae / cmin) cap = ae / cmin;
-                            caps += cap;
-                            pieces += cap + 1;
-                            if (cap > cap_max) cap_max = cap;
-                        }
-                    const double chance = 150.0 * (double)pieces / std::pow(4.0, (double)q);
-                    // a cap lifted from 0 to 1 pays at once, 1 -> 2 a little, 2 -> 3 never did (measured, B = 24 and 96)
-                    if (q < 8 && cap_max > (q == 6 ? 1 : 2)) continue;
-                    if (chance <= limit[q] && caps > best_caps) {
-                        best_caps = caps;
-                        best_q = q;
-                    }
-                }
-                ctx->tier_q = best_q;
-            }
-            if (ctx->tune.tier_q >= 5 && ctx->tune.tier_q <= 8) ctx->tier_q = ctx->tune.tier_q;
-            ctx->cur = 1;
-            rc = build_bitpar_tables(ctx);
-            if (rc == BDX_OK && ctx->fs[1].bplan.enabled && ctx->fs[1].bplan.tier_capped) {
-                rc = build_seed_tables(ctx, true);
-                // very many barcodes: moderately selective 8-base seeds (a dozen chance pairs per read) still beat
-                // the full-budget filter by far
-                if (rc == BDX_OK && !ctx->fs[1].splan.enabled) rc = build_seed_tables(ctx, false);
-                if (rc == BDX_OK && ctx->fs[1].splan.enabled && ctx->fs[1].splan.q < ctx->tier_q) ctx->fs[1].splan.enabled = 0;
-                if (rc == BDX_OK) rc = build_wave_tables(ctx);
-            }
-            ctx->cur = 0;
-            if (rc != BDX_OK) return bail(rc);
-            ctx->tiered = ctx->fs[1].bplan.enabled && ctx->fs[1].bplan.tier_capped && ctx->fs[1].splan.enabled;
-            // with_delta and a min_delta beyond the score of an unseen barcode: not even a perfect match can be
-            // proven unambiguous at the capped budgets (only a visible runner-up could settle a read) — tier 1
-            // would be a pass over the whole batch for next to nothing
-            if (ctx->tiered && config->min_delta != 0.0)
-                for (int k = 0; k < (config->is_dual ? 2 : 1); ++k)
-                    if (!(ctx->fs[1].bplan.tier_slo[k] >= config->min_delta)) ctx->tiered = 0;
-        }
-    }
-    // The PAIRS TIER: a split config with min_delta whose seed tier proves nothing (above), mismatch = cmin = 1 and indels dearer —
-    // the reference's demo2 options (mismatch 1, indel 2, rate 0.25, min_delta 0.15): tier 1 = the same-diagonal pairs mode with
-    // six 4-base pieces over the WHOLE batch at budgets capped at 4 (3) operations — ~3 chance flags per read instead of the ~90 of
-    // the full-budget variant — followed by the exact kernel, which settles every read whose winner leaves min_delta of room below
-    // slo = (cap + 1) / m (a perfect match or one mismatch under demo2's options: ~75 % of the reads) and lists the rest for tier 0.
-    if (!ctx->tiered && ctx->fs[0].bplan.enabled && ctx->fs[0].pplan.enabled && ctx->fs[0].pplan.split && !ctx->tune.no_tier && !ctx->tune.no_pairs &&
-        config->filter == BDX_FILTER_AUTO && config->algorithm == BDX_ALG_SEMIGLOBAL && !config->has_nindel && config->mismatch == 1 &&
-        config->indel >= 2 && config->match == 0 && config->min_delta != 0.0) {
-        bool plain = true;
-        for (int k = 0; k < (config->is_dual ? 2 : 1); ++k) plain = plain && config->pass[k].explicit_window == 0;
-        for (int cap = 4; cap >= 3 && plain && !ctx->tiered; --cap) {
-            ctx->tier_cap_fixed = cap;
-            ctx->cur = 1;
-            ctx->fs[1].splan = BdxSeedPlan{};
-            ctx->fs[1].wplan = BdxWavePlan{};
-            rc = build_bitpar_tables(ctx);
-            bool ok = rc == BDX_OK && ctx->fs[1].bplan.enabled && ctx->fs[1].bplan.tier_capped;
-            for (int k = 0; ok && k < (config->is_dual ? 2 : 1); ++k) ok = ctx->fs[1].bplan.tier_slo[k] >= config->min_delta;
-            if (ok) rc = build_pair_tables(ctx);
-            ok = ok && rc == BDX_OK && ctx->fs[1].pplan.enabled && ctx->fs[1].pplan.pairs_kb == 8 && ctx->fs[1].pplan.split;
-            ctx->cur = 0;
-            if (rc != BDX_OK) return bail(rc);
-            if (ok) {
-                ctx->tiered = 1;
-                ctx->pairs_tier = 1;
-            } else {
-                ctx->tier_cap_fixed = -1;
-                ctx->fs[1].bplan.enabled = 0;
-            }
-        }
-    }
-    ctx->path = ctx->F().bplan.enabled ? (ctx->F().splan.enabled ? (ctx->F().splan.diag ? "qgram2+bitpar+verify" : "qgram+bitpar+verify") : "bitpar+verify") : "generic";
-    if (ctx->tiered) ctx->path = "tier1:qgram+bitpar > " + ctx->path;
-    ctx->filter_used = ctx->F().bplan.enabled ? (ctx->F().splan.enabled ? BDX_FILTER_QGRAM : BDX_FILTER_BITPAR) : BDX_FILTER_OFF;
-    if (ctx->F().bplan.enabled) {
+    if (ctx->fs[0].bplan.enabled) {
         if (ctx->d_maxlen.ensure(1024) != hipSuccess) {
             ctx->err = "hipMalloc failed";
             return bail(BDX_E_DEVICE);
@@ -2553,11 +1426,11 @@ int64_t bdx_last_launches(const bdx_ctx *ctx, char *buf, int64_t cap) {
 
 int32_t bdx_launch_info(const bdx_ctx *ctx, bdx_launch_info_t *out) {
     if (!ctx || !out) return BDX_E_INVALID;
-    const bool f = ctx->filter_used != BDX_FILTER_OFF && ctx->F().bplan.reads_per_block > 0;
+    const bool f = ctx->filter_used != BDX_FILTER_OFF && ctx->fs[0].bplan.reads_per_block > 0;
     out->threads_per_block = f ? 256 : ctx->plan.threads;
-    out->lds_bytes_per_block = f ? (int32_t)bdx_bitpar_lds_bytes(ctx->dev, ctx->F().bplan, ctx->plan, &ctx->F().splan) : (int32_t)ctx->plan.lds_bytes;
+    out->lds_bytes_per_block = f ? (int32_t)bdx_bitpar_lds_bytes(ctx->dev, ctx->fs[0].bplan, ctx->plan, &ctx->fs[0].splan) : (int32_t)ctx->plan.lds_bytes;
     out->blocks = ctx->last_blocks;
-    out->reads_per_block = f ? ctx->F().bplan.reads_per_block : ctx->plan.threads;
+    out->reads_per_block = f ? ctx->fs[0].bplan.reads_per_block : ctx->plan.threads;
     out->filter_used = ctx->filter_used;
     out->max_m = ctx->dev.max_m;
     out->launches = ctx->launches;

@@ -5,7 +5,7 @@
 #include <string>
 #include <vector>
 
-#include "bdx_internal.h"
+#include "bdx_plan.h"  // BdxSetPlans, BdxPlanChoice and the planner's output (bdx_internal.h comes with it)
 
 #define BDX_FQ_SCRATCH 12  // scratch buffers of the device FASTQ pipeline (bdx_fastq.hip)
 #define BDX_DFL_SCRATCH 4  // scratch buffers of the device DEFLATE encoder (bdx_deflate.hip)
@@ -52,84 +52,30 @@ struct PinnedBuf {
     }
 };
 
-// Developer switches.  Read from the environment ONCE, in bdx_create; none of them
-// changes a result — they only select between kernel paths that must agree (the parity tests run them).
-struct BdxTuning {
-    int no_known = 0;     // BDX_NO_KNOWN: no reducer replay, every config runs split (filter -> exact kernel)
-    int no_seed = 0;      // BDX_NO_SEED: no q-gram seeds at all
-    int no_diag = 0;      // BDX_NO_DIAG: no two-intact-pieces variant
-    int no_windows = 0;   // BDX_NO_WINDOWS: split mode without column windows
-    int no_slot = 0;      // BDX_NO_SLOT: long reads use flat staging instead of window slots
-    int lds_dp = 0;       // BDX_LDS_DP: exact kernel with LDS columns instead of the register DP
-    int bitpar_r = 0;     // BDX_BITPAR_R: forced tile size of the fused kernel
-    long long grid = 0;   // BDX_GRID: forced persistent grid
-    int diag_min_b = 48;  // BDX_DIAG_MIN_B: barcode threshold of the diagonal filter
-    int no_window_upload = 0;  // BDX_NO_WINDOW_UPLOAD: the host entry point always uploads whole reads
-    int seed_hash_l2 = 0;  // BDX_SEED_HASH_L2: the piece hash table stays in global memory
-    int seed_bm_log2 = 0;  // BDX_SEED_BM_LOG2: size of the seed bitmap (log2 of its bits)
-    int no_clean = 0;     // BDX_NO_CLEAN: exact kernel's register DP always in its predicated by-construction form
-    int tier_q = 0;       // BDX_TIER_Q: piece length (5..8) the capped budgets of tier 1 are derived from (default: chosen per config)
-    int no_pipeline = 0;  // BDX_NO_PIPELINE: the host entry point uploads large batches in one piece
-    int no_dense = 0;     // BDX_NO_DENSE: plain-sweep kernels keep the 4-entry slots / window entries also for short barcodes
-    int no_band = 0;      // BDX_NO_BAND: the exact kernel never takes the diagonal-band DP
-    int poison = 0;       // BDX_POISON: every hand-over buffer is filled with 0xA5 before each classify call (tests: a consumer that reads what no producer wrote gets garbage on every run, not only when the allocator happens to hand back dirty memory)
-    int tier0_div = 0;    // BDX_TIER0_DIV: tier 0's list is planned for n_reads / this many reads (default 16; 1: the whole batch)
-    int no_kend = 0;      // BDX_NO_KEND: trim_side = 5 configs never take the known-end form of the wave kernel (filter + exact kernel instead)
-    int no_pairs = 0;     // BDX_NO_PAIRS: never the pairs-mode kernel (bdx_pairs.hip) between tier 1 and the general kernel
-    int no_win = 0;       // BDX_NO_WIN: never the window mode of the wave kernel (bdx_wave_win.hip): reads with a short column window stage whole tiles or stay on the general kernel
-    int no_wave = 0;      // BDX_NO_WAVE: never the wave-autonomous kernel (bdx_wave.hip): the general fused kernel answers every read
-    int wave_rw = 0;      // BDX_WAVE_RW / BDX_WAVE_WAVES: forced tile size / waves per workgroup of the wave kernel (tuning)
-    int wave_waves = 0;
-    int no_carry = 0;     // BDX_NO_CARRY: tier 1 of a dual config hands a listed read on without the pass it settled (the pairs mode evaluates both passes again)
-    int no_staged_download = 0;  // BDX_NO_STAGED_DOWNLOAD: large result vectors go back with the runtime's own pageable copies
-    int wave_maxres = 0;  // BDX_WAVE_MAXRES: resident waves per compute unit the wave kernel's geometry may plan for (default 16 = four per SIMD: the kernels need 114-128 VGPRs; tuning: the occupancy experiment of DESIGN §4)
-    int cu_count = 0;     // BDX_CU_COUNT: pretend the device has this many compute units (tests of the grid sizing)
-    int no_tier = 0;      // BDX_NO_TIER: no tiered budgets (every read filtered at the full budget)
-    int debug = 0;        // BDX_DEBUG: honoured only by builds with -DBDX_TUNING (phase skips: results are wrong)
-};
-
 struct bdx_comm_state;  // bdx_comm.cpp
 
 // One complete filter configuration of the fused kernel: sweep tables + seed tables + launch geometry.
 // A context holds two: fs[0] filters at the config's full operation budgets; fs[1] — "tier 1" — at budgets
-// capped so that single 8-base seeds stay selective (see bdx_abi.cpp, tiered budgets).
-struct BdxFilterSet {
-    BdxBitparPlan bplan{};
-    BdxSeedPlan splan{};
-    // weak single seeds kept beside a two-intact-pieces plan: taken when the latter's index does not fit the
-    // batch at hand (very many barcodes, reads beyond 312 bases); built at create, while the barcodes are there
-    BdxSeedPlan splan_alt{};
-    DevBuf bp_tables, seed_tables, seed_tables_alt;
-    BdxWavePlan wplan{};   // wave-autonomous kernel (bdx_wave.hip) for this set, when the config qualifies
-    DevBuf wave_tables;
-    BdxWavePlan wplan_k{};  // known-trim class (ScoreOnly conditions + trim sides): the same tables, the non-split kernel with position keys
-    BdxWavePlan wplan_a{};  // known-alignment class (... + summary statistics / per-pass positions wanted): kend = 3
-    BdxWavePlan pplan{};   // the same kernel in pairs mode (bdx_pairs.hip) at this set's full budgets, over listed reads
-    DevBuf pair_tables;
-    BdxWavePlan pplan_k{};  // ... in its known-end form (trim_side = 5 configs)
-    BdxWavePlan pplan_a{};  // ... in its known-alignment form (kend = 3)
+// capped so that single 8-base seeds stay selective (see bdx_plan.cpp, tiered budgets).  The plans come from the
+// planner; bdx_create uploads its blobs into these buffers and binds the plans' pointers.
+struct BdxFilterSet : BdxSetPlans {
+    DevBuf bp_tables, seed_tables, seed_tables_alt, wave_tables, pair_tables;
 };
 
-struct bdx_ctx {
+struct bdx_ctx : BdxPlanChoice {  // (tiered, tier_q, tier_cap_fixed, pairs_tier, pair_mmin, band_roll_off, filter_used, path)
     bdx_config_t cfg{};
     BdxDevCfg dev{};
     BdxGenericPlan plan{};
     BdxFilterSet fs[2];
-    int cur = 0;        // the set the table builders of bdx_create work on
-    int tiered = 0;     // fs[1] is usable: classify runs tier 1 first, tier 0 on the reads it cannot settle
-    BdxFilterSet &F() { return fs[cur]; }
-    const BdxFilterSet &F() const { return fs[cur]; }
     BdxTuning tune{};
     DevBuf d_maxlen;
     DevBuf d_tier;      // tiered budgets: reads handed from tier 1 to tier 0
     DevBuf d_carry;     // dual tiered known-class configs: the winning survivor of the pass tier 1 settled, per listed read (BdxWavePlan::d_carry)
     int user_len_hint = 0;  // 0 = measure every device batch
-    int filter_used = BDX_FILTER_OFF;
     int device = 0;
     int n_cu = 256;          // compute units of the device (hipDeviceAttributeMultiprocessorCount, read in bdx_create)
     int64_t wave_launches = 0;  // launches of the wave-autonomous kernel
     int64_t pair_launches = 0;  // launches of its pairs mode
-    int pair_mmin = 0;          // shortest barcode of the pairs plan
     DevBuf d_dbg;            // [0] hand-over windows the exact kernel refused (not a window: defence in depth; must stay 0)
     DevBuf d_wlist;          // reads the wave kernel hands to the general kernel (plain configs; tiered ones use d_tier)
     hipStream_t own_stream = nullptr;
@@ -147,11 +93,6 @@ struct bdx_ctx {
     // window upload (host entry point, long reads with short column windows): per-read true lengths / window starts
     DevBuf d_vlen, d_vlo;
     int virt_maxlen = 0;     // > 0 while a window-upload batch is being classified: its longest read
-    int tier_q = 8;          // piece length behind tier 1's capped budgets: cap(m) = m / tier_q - 1
-    int tier_cap_fixed = -1; // >= 0: the pairs tier — tier 1's budgets are capped at this many operations for every barcode and its
-                             // filter is the same-diagonal pairs mode over the whole batch (configs whose min_delta the seed tier cannot prove)
-    int pairs_tier = 0;
-    bool band_roll_off = false;      // bdx_create: the config has no filter (no hand-over windows) — the exact kernel keeps its by-construction LDS form
     int scratch_par = 0;             // which half of the scratch block the next classify call uses
     bool scratch_clean[2] = {false, false};  // that half is known to hold zeros (cleared by the previous call's last launch)
     bool scratch_zeroed = false;  // the small-batch copy kernel has already cleared the filter kernels' scratch words
@@ -184,7 +125,6 @@ struct bdx_ctx {
     DevBuf dfl[BDX_DFL_SCRATCH];  // scratch of the device DEFLATE encoder (bdx_deflate.hip): chunk table, member sizes / offsets, tokens, slots
     DevBuf inf[BDX_INF_SCRATCH];  // scratch of the device inflate (bdx_inflate.hip): member table, member status
     std::string err;
-    std::string path;
     std::string launch_log;      // the classify kernels the last classify call enqueued (bdx_last_launches)
     bool log_host_call = false;  // a bdx_classify_host call is in progress: its device calls add to one log
     int64_t launches = 0;

@@ -1,8 +1,9 @@
-// bdx_internal.h — structures shared between the C-ABI translation unit (bdx_abi.cpp) and the
-// gfx950 kernels (bdx_device.hip).  Not part of the public ABI.
+// bdx_internal.h — structures shared between the host side (the create-time planner bdx_plan.cpp, the C-ABI translation
+// unit bdx_abi.cpp) and the gfx950 kernels (bdx_device.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include "../../include/biodemux_hip.h"
@@ -18,6 +19,48 @@
 #define BDX_MAX_RATE 1.0e4
 #define BDX_WCAP 4       // column-window entries per read and pass handed from the filter to the exact kernel
 #define BDX_REG_ROWS 32  // barcodes up to this length run the register-resident exact DP
+
+// Developer switches.  Read from the environment ONCE, in bdx_create (read_tuning); none of them
+// changes a result — they only select between kernel paths that must agree (the parity tests run them).
+struct BdxTuning {
+    int no_known = 0;     // BDX_NO_KNOWN: no reducer replay, every config runs split (filter -> exact kernel)
+    int no_seed = 0;      // BDX_NO_SEED: no q-gram seeds at all
+    int no_diag = 0;      // BDX_NO_DIAG: no two-intact-pieces variant
+    int no_windows = 0;   // BDX_NO_WINDOWS: split mode without column windows
+    int no_slot = 0;      // BDX_NO_SLOT: long reads use flat staging instead of window slots
+    int lds_dp = 0;       // BDX_LDS_DP: exact kernel with LDS columns instead of the register DP
+    int bitpar_r = 0;     // BDX_BITPAR_R: forced tile size of the fused kernel
+    long long grid = 0;   // BDX_GRID: forced persistent grid
+    int diag_min_b = 48;  // BDX_DIAG_MIN_B: barcode threshold of the diagonal filter
+    int no_window_upload = 0;  // BDX_NO_WINDOW_UPLOAD: the host entry point always uploads whole reads
+    int seed_hash_l2 = 0;  // BDX_SEED_HASH_L2: the piece hash table stays in global memory
+    int seed_bm_log2 = 0;  // BDX_SEED_BM_LOG2: size of the seed bitmap (log2 of its bits)
+    int no_clean = 0;     // BDX_NO_CLEAN: exact kernel's register DP always in its predicated by-construction form
+    int tier_q = 0;       // BDX_TIER_Q: piece length (5..8) the capped budgets of tier 1 are derived from (default: chosen per config)
+    int no_pipeline = 0;  // BDX_NO_PIPELINE: the host entry point uploads large batches in one piece
+    int no_dense = 0;     // BDX_NO_DENSE: plain-sweep kernels keep the 4-entry slots / window entries also for short barcodes
+    int no_band = 0;      // BDX_NO_BAND: the exact kernel never takes the diagonal-band DP
+    int poison = 0;       // BDX_POISON: every hand-over buffer is filled with 0xA5 before each classify call (tests: a consumer that reads what no producer wrote gets garbage on every run, not only when the allocator happens to hand back dirty memory)
+    int tier0_div = 0;    // BDX_TIER0_DIV: tier 0's list is planned for n_reads / this many reads (default 16; 1: the whole batch)
+    int no_kend = 0;      // BDX_NO_KEND: trim_side = 5 configs never take the known-end form of the wave kernel (filter + exact kernel instead)
+    int no_pairs = 0;     // BDX_NO_PAIRS: never the pairs-mode kernel (bdx_pairs.hip) between tier 1 and the general kernel
+    int no_win = 0;       // BDX_NO_WIN: never the window mode of the wave kernel (bdx_wave_win.hip): reads with a short column window stage whole tiles or stay on the general kernel
+    int no_wave = 0;      // BDX_NO_WAVE: never the wave-autonomous kernel (bdx_wave.hip): the general fused kernel answers every read
+    int wave_rw = 0;      // BDX_WAVE_RW / BDX_WAVE_WAVES: forced tile size / waves per workgroup of the wave kernel (tuning)
+    int wave_waves = 0;
+    int no_carry = 0;     // BDX_NO_CARRY: tier 1 of a dual config hands a listed read on without the pass it settled (the pairs mode evaluates both passes again)
+    int no_staged_download = 0;  // BDX_NO_STAGED_DOWNLOAD: large result vectors go back with the runtime's own pageable copies
+    int wave_maxres = 0;  // BDX_WAVE_MAXRES: resident waves per compute unit the wave kernel's geometry may plan for (default 16 = four per SIMD: the kernels need 114-128 VGPRs; tuning: the occupancy experiment of DESIGN §4)
+    int cu_count = 0;     // BDX_CU_COUNT: pretend the device has this many compute units (tests of the grid sizing)
+    int no_tier = 0;      // BDX_NO_TIER: no tiered budgets (every read filtered at the full budget)
+    int debug = 0;        // BDX_DEBUG: honoured only by builds with -DBDX_TUNING (phase skips: results are wrong)
+    int no_band_roll = 0;    // BDX_NO_BAND_ROLL: barcodes beyond 32 rows never take the exact kernel's rolling diagonal band
+    int no_known_exact = 0;  // BDX_NO_KNOWN_EXACT: :exact configs stay outside the known classes
+    int no_kaln = 0;         // BDX_NO_KALN: never the known-alignment forms (kend = 3) of the wave kernel and its pairs mode
+    int trace_launch = 0;    // BDX_TRACE_LAUNCH: the planner says on stderr where it turned a filter set away from the wave kernel
+    double wave_chance = NAN;  // BDX_WAVE_CHANCE: chance seed hits per read up to which a set gets wave tables (default 6, tier 1: 3; tuning)
+    int pairs_nw = 0;        // BDX_PAIRS_NW: at least this many words per barcode mask in the pairs mode (tuning)
+};
 
 struct BdxDevRange {
     long long start_offset;
@@ -111,7 +154,7 @@ struct BdxGenericPlan {
     int n_cu;            // compute units of the device (list-mode grid: 4 workgroups per unit)
 };
 
-// Bit-parallel (Myers) pre-filter: tables built on the host in bdx_abi.cpp, used by
+// Bit-parallel (Myers) pre-filter: tables built on the host in bdx_plan.cpp, used by
 // bdx_bitpar.hip.  enabled == 0 -> the config is outside the filter's domain.
 struct BdxBitparPlan {
     int enabled;
@@ -146,7 +189,7 @@ struct BdxBitparPlan {
     const int32_t *d_kb[2];        // device, [B]: max unit edit operations of a recordable alignment
 };
 
-// q-gram seeding in front of the sweep (pigeonhole): tables built in bdx_abi.cpp.
+// q-gram seeding in front of the sweep (pigeonhole): tables built in bdx_plan.cpp.
 struct BdxSeedPlan {
     int enabled;
     int q;                 // seed length in bases (5..8); key = 2 bits per base
@@ -171,7 +214,7 @@ struct BdxSeedPlan {
 
 // Wave-autonomous seeded kernel (bdx_wave.hip): the single-seed filter + reducer replay of known-score configs whose
 // barcodes are plain A/C/G/T, every wave on a tile of its own (no workgroup barriers), bytes transcoded arithmetically.
-// Tables are built next to the seed tables of a filter set (bdx_abi.cpp, build_wave_tables); the geometry per batch.
+// Tables are built next to the seed tables of a filter set (bdx_plan.cpp, build_wave_tables); the geometry per batch.
 struct BdxWavePlan {
     int enabled;           // config-level eligibility of this filter set
     uint32_t *d_carry = nullptr;  // per launch (dual tiered known-class configs, min_delta = 0): tier 1 leaves the winning survivor of the ONE pass it settled
@@ -247,9 +290,22 @@ struct BdxWaveSplit {
 };
 
 // The wave-autonomous kernel (bdx_wave_kernel.h) is compiled in six translation units, one set of instantiations each.
-// Implemented in bdx_wave.hip (LDS sizing; the known-score and plain split-mode instantiations: whole ranges, one pass).
-size_t bdx_wave_table_bytes(const BdxWavePlan &wp, int hist_entries);
-size_t bdx_wave_area_bytes(int rw, int span_cap, bool pairs, int hq_cap, int sq_cap, int cand_words, bool winm = false);
+// Implemented in bdx_wave.hip (the known-score and plain split-mode instantiations: whole ranges, one pass).
+// LDS bytes of the shared tables / of one wave's work area (must mirror the kernel's carve-up); the planner (bdx_plan.cpp)
+// and the launchers share this one copy
+inline size_t bdx_wave_table_bytes(const BdxWavePlan &wp, int hist_entries) {
+    auto al = [](size_t x) { return (x + 31) & ~(size_t)31; };
+    return al((size_t)wp.bm_bytes) + al(wp.pairs_kb > 0 ? 0 : (size_t)wp.bm_bytes / 2) + al((size_t)wp.n_ent * 4) + al((size_t)wp.n_barcodes * 36) +
+           al(wp.kend >= 2 ? (size_t)wp.n_barcodes * 36 : 0) + 2 * al((size_t)wp.n_barcodes * 4) + al((size_t)hist_entries * 4);
+}
+inline size_t bdx_wave_area_bytes(int rw, int span_cap, bool pairs, int hq_cap, int sq_cap, int cand_words, bool winm = false) {
+    const size_t nvec = (size_t)span_cap >> 4;
+    const size_t recs = pairs ? 0 : 2 * (size_t)rw * 8 * 4;  // record tables
+    const size_t fixed = (size_t)(((rw + 1) * 4 + 15) / 16 * 16) + recs + (size_t)rw * 16 + 3 * (size_t)rw * 4 + 256 +
+                         ((pairs || winm) ? 2 * (size_t)rw * 4 + 16 + 2 * (size_t)rw * 20 : 0) + ((winm || pairs) ? (size_t)rw * 4 + 2 * (size_t)rw * 4 : 0);
+    const size_t o = fixed + ((nvec + 2 + 3) & ~(size_t)3) * 4 + ((2 * nvec + 6 + 3) & ~(size_t)3) * 4 + ((size_t)hq_cap + (pairs ? 0 : (size_t)sq_cap) + (size_t)rw * (size_t)cand_words) * 4;
+    return (o + 31) & ~(size_t)31;
+}
 hipError_t bdx_launch_wave(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
                            long long n_reads, const BdxDevOut &out, unsigned long long *d_counts, int tier1, double tier_slo, uint32_t *list,
                            unsigned int *list_count, hipStream_t stream, int dbg = 0, const BdxWaveSplit *sp = nullptr, double tier_slo1 = 0.0);

@@ -1,23 +1,7 @@
 // bdx_wave.hip — the wave-autonomous kernel (bdx_wave_kernel.h) for known-score configs (the headline form) and for plain split
-// mode, both with whole ranges and a single pass (GEN = false), its LDS sizing and their launcher.  Dual and ranged configs
+// mode, both with whole ranges and a single pass (GEN = false), and their launcher.  Dual and ranged configs
 // take the general forms, which bdx_wave_end.hip (non-split) and bdx_pairs.hip (split) hold.
 #include "bdx_wave_kernel.h"
-
-// LDS bytes of the shared tables / of one wave's work area (must mirror the kernel's carve-up)
-size_t bdx_wave_table_bytes(const BdxWavePlan &wp, int hist_entries) {
-    auto al = [](size_t x) { return (x + 31) & ~(size_t)31; };
-    return al((size_t)wp.bm_bytes) + al(wp.pairs_kb > 0 ? 0 : (size_t)wp.bm_bytes / 2) + al((size_t)wp.n_ent * 4) + al((size_t)wp.n_barcodes * 36) +
-           al(wp.kend >= 2 ? (size_t)wp.n_barcodes * 36 : 0) + 2 * al((size_t)wp.n_barcodes * 4) + al((size_t)hist_entries * 4);
-}
-
-size_t bdx_wave_area_bytes(int rw, int span_cap, bool pairs, int hq_cap, int sq_cap, int cand_words, bool winm) {
-    const size_t nvec = (size_t)span_cap >> 4;
-    const size_t recs = pairs ? 0 : 2 * (size_t)rw * 8 * 4;  // record tables
-    const size_t fixed = (size_t)(((rw + 1) * 4 + 15) / 16 * 16) + recs + (size_t)rw * 16 + 3 * (size_t)rw * 4 + 256 +
-                         ((pairs || winm) ? 2 * (size_t)rw * 4 + 16 + 2 * (size_t)rw * 20 : 0) + ((winm || pairs) ? (size_t)rw * 4 + 2 * (size_t)rw * 4 : 0);
-    const size_t o = fixed + ((nvec + 2 + 3) & ~(size_t)3) * 4 + ((2 * nvec + 6 + 3) & ~(size_t)3) * 4 + ((size_t)hq_cap + (pairs ? 0 : (size_t)sq_cap) + (size_t)rw * (size_t)cand_words) * 4;
-    return (o + 31) & ~(size_t)31;
-}
 
 hipError_t bdx_launch_wave(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
                            long long n_reads, const BdxDevOut &out, unsigned long long *d_counts, int tier1, double tier_slo, uint32_t *list,

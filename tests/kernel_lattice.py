@@ -110,9 +110,9 @@ def classify_kernels() -> list:
     return sorted(k for k in code_object_kernels() if parse(k) is not None)
 
 
-# ---- the wave planner, restated (bdx_abi.cpp: build_seed_tables, build_wave_tables, size_wave; bdx_wave_kernel.h: the
+# ---- the wave planner, restated (bdx_plan.cpp: build_seed_tables, build_wave_tables; bdx_abi.cpp: size_wave; bdx_wave_kernel.h: the
 # dispatch ladder seeded_ladder; bdx_wave.hip: bdx_wave_table_bytes, bdx_wave_area_bytes) ----
-LDS_MAX = 160 * 1024  # bdx_abi.cpp LDS_MAX
+LDS_MAX = 160 * 1024  # bdx_plan.cpp / bdx_abi.cpp LDS_MAX
 
 
 def wave_seed_plan(ms, rate: float) -> dict:
@@ -138,7 +138,7 @@ def wave_seed_plan(ms, rate: float) -> dict:
 
 def wave_table_bytes(sp: dict, kend: int) -> int:
     """bdx_wave_table_bytes of a non-pairs plan: seed bitmap, rank words, entries (one per piece), peq rows (stride 9), the
-    reversed rows of a KEND >= 2 plan, meta + settle words, the LDS histogram (4 + B counters: bdx_abi.cpp n_counts)."""
+    reversed rows of a KEND >= 2 plan, meta + settle words, the LDS histogram (4 + B counters: bdx_plan.cpp n_counts)."""
     al = lambda x: (x + 31) & ~31  # noqa: E731
     bm = (1 << (2 * sp["q"])) // 8
     b = sp["n_bc"]
@@ -209,7 +209,7 @@ def longest_in_cell(sp: dict, kend: int, cand_words: int, rw: int, nv: int) -> i
 # ---- recipes ----
 # wave form (the template arguments after RW, TF, NV, Q) -> the config switches that select it, single pass, whole ranges
 WAVE_FORMS = {
-    # known-score class: unit costs, no trim side, no summary (bdx_abi.cpp known_ok) -> the non-split kernel (bdx_launch_wave)
+    # known-score class: unit costs, no trim side, no summary (bdx_plan.cpp known_ok) -> the non-split kernel (bdx_launch_wave)
     "false, 0, 0, false, 0, false, false": dict(kw={}, want_pass=False),
     # weighted costs: not the known class (known_ok false, kclass false: no KEND plan) -> split mode (build_wave_tables)
     "true, 0, 0, false, 0, false, false": dict(kw={"indel": 2}, want_pass=False),
@@ -241,7 +241,7 @@ TILES = 40  # whole tiles of a batch (+ one ragged read): >= 2 x the 16 resident
 
 def wave_form_of(kw: dict, want_pass: bool) -> dict:
     """The wave form a single-pass config with whole ranges gets, from its switches `kw` (DemuxConfig fields) and whether
-    the caller wants per-pass outputs: known_ok = unit costs, no trim side, no summary (bdx_abi.cpp, build_bitpar_tables);
+    the caller wants per-pass outputs: known_ok = unit costs, no trim side, no summary (bdx_plan.cpp, build_bitpar_tables);
     split = not known_ok (build_wave_tables); with unit costs a split config also gets the known-trim plan (no summary:
     KEND 1, or 2 with a trim_side 3 pass) and the known-alignment plan (KEND 3); bdx_classify_device takes the known-trim
     plan unless the caller wants per-pass start positions or statistics (kend_ok), else the known-alignment one (p.aln).
