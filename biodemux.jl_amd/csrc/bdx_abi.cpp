@@ -1,6 +1,6 @@
 // bdx_abi.cpp — C-ABI of libbiodemux_hip.so (see include/biodemux_hip.h for the contract and
 // the reference lines each entry point replaces).  Host-side only: validation, upload of what the create-time planner
-// (bdx_plan.cpp) produced, per-call launch planning (the host entry point, bdx_classify_host, is bdx_host.cpp).  All arithmetic of the hot path runs in the gfx950
+// (bdx_plan.cpp) produced, reserve and enqueue of what the per-call planner (bdx_call.cpp) decided (the host entry point, bdx_classify_host, is bdx_host.cpp).  All arithmetic of the hot path runs in the gfx950
 // kernels of bdx_device.hip / bdx_filter.hip; there is NO CPU fallback — without a usable
 // HIP device every entry point fails with BDX_E_DEVICE.
 #include <cmath>
@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "bdx_call.h"
 #include "bdx_ctx.h"
 
 thread_local std::string g_create_error;
@@ -91,315 +92,6 @@ BdxTuning read_tuning() {
     if (const char *e = getenv("BDX_WAVE_CHANCE")) t.wave_chance = atof(e);
     if (const char *e = getenv("BDX_PAIRS_NW")) t.pairs_nw = atoi(e);
     return t;
-}
-
-const size_t LDS_MAX = 160 * 1024;
-
-// Geometry of the wave kernel for a batch: the tile size and workgroup shape that keep the most waves resident
-// per compute unit (tables once per workgroup + one work area per wave within 160 KiB, at most 16 waves: the
-// kernel is compiled for four waves per SIMD).  false: this batch runs the general kernel.
-bool size_wave(bdx_ctx *ctx, BdxWavePlan &wp, int read_len, long long n_reads);
-bool size_wave(bdx_ctx *ctx, int set, int read_len, long long n_reads) { return size_wave(ctx, ctx->fs[set].wplan, read_len, n_reads); }
-bool size_wave(bdx_ctx *ctx, BdxWavePlan &wp, int read_len, long long n_reads) {
-    wp.winm = 0;
-    if (!wp.enabled || ctx->dev.vlen) return false;  // (window uploads stage per-read slots: general kernel)
-    if (read_len < 1) read_len = 1;
-    const size_t tables = bdx_wave_table_bytes(wp, ctx->plan.hist_entries);
-    const int rws[3] = {32, 16, 8};
-    int best_waves = 0;
-    for (int rw : rws) {
-        if (ctx->tune.wave_rw && rw != ctx->tune.wave_rw) continue;
-        // small batches: at least one tile per resident wave before the tile grows
-        if (!ctx->tune.wave_rw && rw > 8 && n_reads / rw < (long long)ctx->n_cu * 16) continue;
-        const long long span = (((long long)rw * read_len + 64 + 15) & ~15LL);
-        if (span > 10 * 1024) continue;  // a tile's bytes wait in registers: at most ten 16-byte vectors per lane
-        // queues: the planted barcode's pieces (up to kb + 1 = 3 hits, one or two records) + the chance hits, with slack
-        const int hq_cap = rw * (int)std::ceil(std::max(6.0, 4.0 + 2.5 * wp.chance));
-        const int sq_cap = rw * (int)std::ceil(std::max(3.0, 1.8 + 1.6 * wp.chance));
-        const size_t area = bdx_wave_area_bytes(rw, (int)span, false, hq_cap, sq_cap, wp.cand_words + (wp.ranged ? 4 : 0));
-        const int maxres = ctx->tune.wave_maxres > 0 ? ctx->tune.wave_maxres : 16;
-        const int shapes[4] = {8, 16, 4, ctx->tune.wave_waves};  // (a forced shape may be any wave count up to 16)
-        for (int w : shapes) {
-            if (w < 1 || w > 16 || (ctx->tune.wave_waves && w != ctx->tune.wave_waves)) continue;
-            const size_t lds = tables + (size_t)w * area;
-            if (lds > LDS_MAX) continue;
-            int per_cu = (int)(LDS_MAX / (((lds + 1279) / 1280) * 1280));  // 1280-byte LDS granules
-            if (per_cu * w > maxres) per_cu = maxres / w;
-            if (per_cu < 1) continue;
-            const int resident = per_cu * w;
-            if (resident > best_waves) {
-                best_waves = resident;
-                wp.rw = rw;
-                wp.waves = w;
-                wp.blocks = per_cu * ctx->n_cu;
-                wp.span_cap = (int)span;
-                wp.hq_cap = hq_cap;
-                wp.sq_cap = sq_cap;
-            }
-        }
-        if (best_waves >= 12) break;  // a larger tile at (nearly) full residency beats a smaller one
-    }
-    if (best_waves < 4) return false;
-    wp.read_len_hint = read_len;
-    // ranged single-pass configs: the seed scan only walks the groups of sixteen positions that overlap a read's window when
-    // the window (resolved at the planned read length, classification.jl:795-800) is much shorter than the read
-    wp.scan_gpr = 0;
-    if (wp.ranged) {
-        const int npw = ctx->dev.is_dual ? 2 : 1;
-        long long gpr = 0;
-        for (int k = 0; k < npw; ++k) {
-            const BdxDevRange &dr = ctx->dev.pass[k].ref_search;
-            long long f = dr.start_from_end ? read_len + dr.start_offset : dr.start_offset;
-            long long l = dr.end_from_end ? read_len + dr.end_offset : dr.end_offset;
-            if (f < 1) f = 1;
-            if (l > read_len) l = read_len;
-            const long long wlen = l >= f ? l - f + 1 : 0;
-            const long long g = (wlen + 15) / 16 + 1;
-            if (g > gpr) gpr = g;
-        }
-        if (gpr * npw * 16 * 10 <= (long long)read_len * 7 && (long long)wp.rw * npw * gpr < 2048) wp.scan_gpr = (int)gpr;
-    }
-    return true;
-}
-
-// Window mode of the wave kernel (bdx_wave_win.hip) for a batch: single-pass known-score configs whose ref_search_range
-// window — resolved at the planned read length (classification.jl:795-800) — is at most half the read: the tiles are
-// scattered, every read's slot holds just its window (+ up to 15 positions in front: the loads are aligned 16-byte vectors).
-// This is what lets 10 kbp reads with a 200-column window (BASELINE config 5) take the wave kernel at all: a tile's bytes
-// wait in registers, which bounds a contiguous tile at 10 KB.
-bool size_wave_win(bdx_ctx *ctx, BdxWavePlan &wp, int read_len, long long n_reads) {
-    wp.winm = 0;
-    if (!wp.enabled || ctx->dev.vlen || !wp.ranged || wp.split || wp.kend || ctx->dev.is_dual || ctx->tune.no_wave || ctx->tune.no_win) return false;
-    if (read_len < 1) read_len = 1;
-    const BdxDevRange &dr = ctx->dev.pass[0].ref_search;
-    {
-        const long long LIM = 1LL << 28;  // (the kernel resolves the windows in 32-bit arithmetic)
-        if (dr.start_offset < -LIM || dr.start_offset > LIM || dr.end_offset < -LIM || dr.end_offset > LIM) return false;
-    }
-    long long f = dr.start_from_end ? read_len + dr.start_offset : dr.start_offset;
-    long long l = dr.end_from_end ? read_len + dr.end_offset : dr.end_offset;
-    if (f < 1) f = 1;
-    if (l > read_len) l = read_len;
-    const long long wlen = l >= f ? l - f + 1 : 0;
-    if (wlen < 1 || wlen * 2 > read_len) return false;
-    const int slot = (int)((wlen + 15 + 15) & ~15LL);
-    const size_t tables = bdx_wave_table_bytes(wp, ctx->plan.hist_entries);
-    const double chance = wp.chance * (double)wlen / 150.0;
-    int best_waves = 0;
-    const int rws[2] = {32, 16};
-    for (int rw : rws) {
-        if (ctx->tune.wave_rw && rw != ctx->tune.wave_rw) continue;
-        if (!ctx->tune.wave_rw && rw > 16 && n_reads / rw < (long long)ctx->n_cu * 16) continue;  // small batches: a tile per resident wave first
-        const int vecs = rw * (slot >> 4);
-        if (!((rw == 32 && vecs <= 64 * 7) || (rw == 16 && vecs <= 64 * 4))) continue;  // (instantiated register budgets)
-        const int span = rw * slot + 16;
-        const int hq_cap = rw * (int)std::ceil(std::max(6.0, 4.0 + 2.5 * chance));
-        const int sq_cap = rw * (int)std::ceil(std::max(3.0, 1.8 + 1.6 * chance));
-        const size_t area = bdx_wave_area_bytes(rw, span, false, hq_cap, sq_cap, 0, true);
-        const int shapes[3] = {16, 8, 4};  // (tried: 32-read tiles on 12 waves per CU — C5 0.329 vs 0.314 ms with 16-read tiles on 16 waves)
-        for (int w : shapes) {
-            if (ctx->tune.wave_waves && w != ctx->tune.wave_waves) continue;
-            const size_t lds = tables + (size_t)w * area;
-            if (lds > LDS_MAX) continue;
-            int per_cu = (int)(LDS_MAX / (((lds + 1279) / 1280) * 1280));
-            if (per_cu * w > 16) per_cu = 16 / w;
-            if (per_cu * w > best_waves) {
-                best_waves = per_cu * w;
-                wp.rw = rw;
-                wp.waves = w;
-                wp.blocks = per_cu * ctx->n_cu;
-                wp.span_cap = span;
-                wp.hq_cap = hq_cap;
-                wp.sq_cap = sq_cap;
-            }
-        }
-        if (best_waves >= 12) break;
-    }
-    if (best_waves < 4) return false;
-    wp.slot = slot;
-    wp.read_len_hint = read_len;
-    wp.scan_gpr = 0;
-    wp.winm = 1;
-    return true;
-}
-
-// Geometry of the pairs mode for a batch: 16-read tiles of slots of `read_len` rounded up to 16 bytes.
-bool size_pairs(bdx_ctx *ctx, BdxWavePlan &wp, int read_len);
-bool size_pairs(bdx_ctx *ctx, int read_len) { return size_pairs(ctx, ctx->fs[0].pplan, read_len); }
-bool size_pairs(bdx_ctx *ctx, BdxWavePlan &wp, int read_len) {
-    if (!wp.enabled || ctx->dev.vlen) return false;
-    if (read_len < 1) read_len = 1;
-    // a read's slot in the tile's images: its bytes are fetched as aligned 16-byte vectors, so it starts up to 15 positions in
-    const int slot = (read_len + 15 + 15) & ~15;
-    const int rw = 16;
-    const int span = rw * slot + 16;
-    if (span > 6 * 1024 + 16) return false;  // (instantiated: three and six 16-byte vectors per lane)
-    int cpr = ((15 + read_len - ctx->pair_mmin + wp.pairs_spread + 8) >> 4) + 1;  // (diagonals are counted from the slot's start)
-    if (read_len < ctx->pair_mmin) cpr = 1;
-    if (cpr > slot / 16) cpr = slot / 16;
-    if (cpr < 1) cpr = 1;
-    const size_t tables = bdx_wave_table_bytes(wp, ctx->plan.hist_entries);
-    // (31 chance flags per read at 96 barcodes and kb = 4: the queue holds a 16-read tile's worth; with more barcodes it is
-    // drained several times per tile; a tile whose queue runs over between two drains is handed on / swept whole)
-    // (same-diagonal variants: ~80 chance flags per read at 96 barcodes of eight 3-base pieces — the queue is drained inside the scan)
-    wp.hq_cap = wp.groups > 1 ? 1024 : wp.pairs_kb >= 8 ? 1280 : 56 * rw;
-    wp.sq_cap = 0;
-    const size_t area = bdx_wave_area_bytes(rw, span, true, wp.hq_cap, 0, wp.cand_words + (wp.ranged ? 4 : 0));
-    int best = 0;
-    const int shapes[3] = {16, 8, 4};
-    for (int w : shapes) {
-        if (ctx->tune.wave_waves && w != ctx->tune.wave_waves) continue;
-        const size_t lds = tables + (size_t)w * area;
-        if (lds > LDS_MAX) continue;
-        int per_cu = (int)(LDS_MAX / (((lds + 1279) / 1280) * 1280));
-        if (per_cu * w > 16) per_cu = 16 / w;
-        if (per_cu * w > best) {
-            best = per_cu * w;
-            wp.waves = w;
-            wp.blocks = per_cu * ctx->n_cu;
-        }
-    }
-    if (best < 4) return false;
-    wp.rw = rw;
-    wp.span_cap = span;
-    wp.slot = slot;
-    wp.cpr = cpr;
-    wp.read_len_hint = read_len;
-    return true;
-}
-
-// Geometry of the fused kernel for a given typical read length: the largest R whose LDS
-// footprint still lets two workgroups share a CU (8 waves/CU), else whatever fits.
-// set: the filter set planned (0: full budgets, 1: tier 1).
-// force_slot: list mode (tier 0 of the tiered budgets) — the reads are scattered, every read is staged into a slot
-bool size_bitpar(bdx_ctx *ctx, int set, int read_len, long long n_reads, bool force_slot = false) {
-    BdxFilterSet &F = ctx->fs[set];
-    BdxBitparPlan &bp = F.bplan;
-    if (!bp.enabled) return false;
-    if (read_len < 1) read_len = 1;
-    if (ctx->dev.vlen) force_slot = true;  // window upload: only each read's window is there
-    // small batches: keep >= ~1024 tiles in flight (4 per CU) before growing the tile
-    int r_cap = 256;
-    while (r_cap > 16 && n_reads / r_cap < 4LL * ctx->n_cu) r_cap >>= 1;
-    if (bp.read_len_hint == read_len && bp.r_cap == r_cap && bp.reads_per_block > 0 && (bp.slot_bytes > 0 || !force_slot)) return true;
-    bp.r_cap = r_cap;
-    const int forced = ctx->tune.bitpar_r;
-    // Pick the R that keeps the most waves resident per CU (the sweep is latency-bound):
-    // workgroups/CU = min(8, floor(160 KiB / LDS(R))) with 4 waves each; ties -> larger R
-    // (fewer table reloads).  R = 16 is only taken when nothing larger fits.
-    // Column-window bound for this read length: the union over the passes of
-    // final_search_range (classification.jl:799-800), resolved exactly like the device does.
-    // Window lengths are non-decreasing in n, so the bound at the hint covers shorter reads.
-    int wmax = read_len;
-    {
-        long long ulo = (1LL << 40), uhi = 0;
-        const int npass = ctx->dev.is_dual ? 2 : 1;
-        for (int k = 0; k < npass; ++k) {
-            const BdxDevPass &P = ctx->dev.pass[k];
-            long long f, l;
-            if (P.explicit_window) {
-                f = P.win_first;
-                l = P.win_last;
-            } else {
-                auto res = [&](const BdxDevRange &dr, long long &a, long long &b) {
-                    long long s = dr.start_from_end ? read_len + dr.start_offset : dr.start_offset;
-                    long long e = dr.end_from_end ? read_len + dr.end_offset : dr.end_offset;
-                    a = s > 1 ? s : 1;
-                    b = e < read_len ? e : read_len;
-                    if (b < a) b = a - 1;
-                };
-                long long rf, rl, bf, bl, ef, el;
-                res(P.ref_search, rf, rl);
-                res(P.bc_start, bf, bl);
-                res(P.bc_end, ef, el);
-                f = rf > bf ? rf : bf;
-                l = rl < el ? rl : el;
-            }
-            if (f < 1) f = 1;
-            if (l > read_len) l = read_len;
-            if (l < f) continue;
-            long long h = ctx->dev.algorithm == BDX_ALG_SEMIGLOBAL ? l : l + ctx->dev.max_m - 1;
-            if (h > read_len) h = read_len;
-            if (f - 1 < ulo) ulo = f - 1;
-            if (h > uhi) uhi = h;
-        }
-        if (uhi > ulo) wmax = (int)(uhi - ulo);
-        else wmax = 16;
-    }
-    const bool slot_mode = force_slot || ((long long)wmax * 2 + 96 <= (long long)read_len && !ctx->tune.no_slot);
-    const int slot = slot_mode ? ((wmax + 15 + 16 + 15) & ~15) : 0;
-    bp.slot_bytes = slot;
-    bp.seed_span = slot_mode ? wmax : read_len;
-    if (F.splan.enabled && F.splan.diag) {
-        // index width for this read length, and the sweep queue for the expected number of flagged pairs
-        if (bp.seed_span > 312) {  // the widest index holds 320 positions: weak single seeds if they apply, else the plain sweep
-            F.splan = F.splan_alt;  // (disabled if weak seeds do not apply either)
-            F.splan_alt = BdxSeedPlan{};
-            return size_bitpar(ctx, set, read_len, n_reads, force_slot);
-        }
-        bp.diag_nw = bp.seed_span <= 152 ? 5 : 10;
-        const double L = (double)(bp.seed_span < 32 ? 32 : bp.seed_span);
-        const double flagged = F.splan.diag_flag_coef * ((L - 3.0) / 256.0) * ((L - 3.0) / 256.0) / (L + 24.0) +
-                               (double)(F.splan.n_always[0] + F.splan.n_always[1]);
-        bp.diag_qcap = (int)(flagged * 1.3) + 12;  // per read (a sub-batch shares 4..8 reads' worth)
-    }
-    const bool diag = F.splan.enabled && F.splan.diag;
-    const int tries[7] = {256, 128, 64, 32, 16, 8, 4};
-    int best_R = 0, best_blocks = 0, best_stage = 0;
-    for (int R : tries) {
-        if (diag ? R > 32 : R < 16) continue;  // the diagonal variant indexes 8 reads at a time (40 KiB): small tiles
-        if (forced && R != forced) continue;
-        if (!forced && R > r_cap) continue;
-        if (bp.word_bytes == 16 && (R > 64 || R < 16)) continue;  // (128-bit sweep words: instantiated for tiles of 64 / 32 / 16 reads)
-        if (!forced && !F.splan.enabled && R > 64 && read_len <= 1024) continue;  // sweep-all: 64-read tiles measured best
-        size_t st = slot_mode ? (size_t)R * (size_t)slot : (size_t)R * (size_t)read_len + 64;
-        st = (st + 15) & ~(size_t)15;
-        if (st > (size_t)1 << 20) continue;
-        bp.reads_per_block = R;
-        bp.stage_bytes = (int)st;
-        bp.read_len_hint_for_lds = read_len;
-        const size_t lds = bdx_bitpar_lds_bytes(ctx->dev, bp, ctx->plan, &F.splan);
-        if (lds > LDS_MAX) continue;
-        int blocks = (int)(LDS_MAX / (((lds + 1279) / 1280) * 1280));  // LDS is allocated in 1280-byte granules (measured: 54128 B -> 2 per CU, 51872 B -> 3)
-        // Measured on MI355X (tools/probe.py): tile size matters more than residency once 3
-        // workgroups (12 waves) share a CU — larger tiles fill the 256 lanes of the sparse
-        // sweep / exact stages better.  Rank: >= 3 resident (largest R wins), then 2, then 1.
-        const int rank = blocks >= 3 ? 3 : blocks;
-        if (!diag && R == 16 && best_R) continue;
-        if (rank > best_blocks) {
-            best_blocks = rank;
-            best_R = R;
-            best_stage = (int)st;
-        }
-    }
-    if (best_R && diag && best_blocks < 2) {
-        // the index leaves room for one workgroup per CU only (very many barcodes): weak single seeds if they
-        // apply, else the plain sweep
-        F.splan = F.splan_alt;  // (disabled if weak seeds do not apply either)
-        F.splan_alt = BdxSeedPlan{};
-        return size_bitpar(ctx, set, read_len, n_reads, force_slot);
-    }
-    if (best_R) {
-        bp.reads_per_block = best_R;
-        bp.stage_bytes = best_stage;
-        bp.read_len_hint = read_len;
-        bp.read_len_hint_for_lds = read_len;
-        return true;
-    }
-    if (F.splan.enabled) {
-        // the seed tables do not fit next to everything else (very many barcodes): the two-intact-pieces index
-        // gives way to the weak single seeds kept beside it; those give way to the plain sweep; plan again
-        if (F.splan.diag && F.splan_alt.enabled) {
-            F.splan = F.splan_alt;
-            F.splan_alt = BdxSeedPlan{};
-        } else {
-            F.splan.enabled = 0;
-        }
-        return size_bitpar(ctx, set, read_len, n_reads, force_slot);
-    }
-    bp.reads_per_block = 0;
-    bp.read_len_hint = 0;
-    return false;
 }
 
 int validate(const bdx_config_t *c) {
@@ -503,7 +195,7 @@ void bind(BdxWavePlan &wp, const DevBuf &t, const BdxWaveOff &o) {
 }
 
 // Everything the planner produced goes to the device here: the barcode arrays, the counters, and per filter set every
-// table a plan left enabled refers to (also one a rejected tier attempt left behind: plan_call walks both sets); then
+// table a plan left enabled refers to (also one a rejected tier attempt left behind: the call planner walks both sets); then
 // the plans' pointers are bound from base + offset.
 int upload_plan(bdx_ctx *ctx, const bdx_config_t &c, const BdxPlanOut &po) {
     ctx->dev = po.dev;
@@ -732,7 +424,7 @@ int32_t bdx_create(const bdx_config_t *config, bdx_ctx **out) {
         ctx->cfg.pass[k].bc_off = nullptr;
         ctx->cfg.pass[k].bc_len_no_N = nullptr;
     }
-    if (bdx_generic_set_lds_limit(LDS_MAX) != hipSuccess) {
+    if (bdx_generic_set_lds_limit(BDX_LDS_MAX) != hipSuccess) {
         ctx->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
         return bail(BDX_E_DEVICE);
     }
@@ -831,162 +523,11 @@ int32_t bdx_sync(bdx_ctx *ctx) {
     return BDX_OK;
 }
 
-// ---- one filtered classify call: plan (every size_* call), reserve (buffers, poison, scratch), enqueue ----------------
-// The fused kernel filters; the exact DP runs at full width in the generic kernel:
-//  * split (trimming / summary / weighted costs / N-scoring / Hamming / exact): every read's candidate mask (+ column
-//    windows) goes through HBM, the generic kernel gives every verdict;
-//  * known-score configs: the fused kernel also gives the verdict of (nearly) every read by replaying the reducer; the few
-//    it cannot settle are listed and evaluated by the generic kernel in list mode;
-//  * tiered budgets (known-score configs whose full budget is too large for selective single seeds): tier 1 — capped
-//    budgets, single seeds — runs over the whole batch and settles every read whose verdict cannot depend on a barcode
-//    beyond the cap; tier 0 — the full budget — then runs in list mode over the rest.
-// A call runs up to five stages in this order: front, tier 1's exact launch, middle, full-budget filter, exact.
-
-// Front stage.  Tiered: tier 1 over every read of the batch — bitpar (the fused kernel), wave / wave_win / wave_end (the wave
-// kernel answers what it can settle and lists the rest), wave_split (the wave kernel as a filter: tier 1's exact launch settles
-// and lists), pairs (the same-diagonal pairs mode as a filter).  Plain configs: wave, wave_win or wave_end in front of the same
-// filter set in list mode.
-enum class Front { none, bitpar, wave, wave_win, wave_split, wave_end, pairs };
-// Middle stage: the pairs mode of the wave kernel (bdx_pairs.hip).  end: known-end / known-alignment form over tier 1's
-// list; list: known-score form over it; split: tier 0's filter over it; all: the only filter, over every read.
-enum class Middle { none, end, list, split, all };
-enum class Full { none, wave_split, bitpar };  // the full-budget filter (none: the pairs mode already filtered)
-enum class Exact { known, split, split_list };  // the generic kernel: over the fused kernel's hand-over list / dense / over a list
-
-struct CallPlan {
-    int npass = 1, tier_len = 0, batch_len = 0;  // tier_len > 0: tiered; batch_len: the read length the launches were planned for
-    bool split = false, windows = false, dense_w = false;
-    int short_lb[2] = {0, 0};
-    Front front = Front::none;
-    bool t1_exact = false;  // tier 1's exact launch
-    Middle middle = Middle::none;
-    Full full = Full::bitpar;
-    Exact exact = Exact::known;
-    bool carry = false, aln = false;  // carried passes (d_carry); the known-end forms run as the known-alignment class
-    BdxWavePlan *wfront = nullptr, *wmid = nullptr;  // the wave plans the front / middle stage launch
-};
-
-static int plan_call(bdx_ctx *ctx, const BdxDevOut &o, bool stats, long long n_reads, int batch_len, int tier_len, CallPlan &p) {
-    if (n_reads > 0xFFFFFFF0LL) return fail(ctx, BDX_E_INVALID, "more than 2^32 reads in one batch");
-    const BdxDevCfg &dev = ctx->dev;
-    BdxFilterSet &f0 = ctx->fs[0], &f1 = ctx->fs[1];
-    const bool tiered = tier_len > 0;
-    p.npass = dev.is_dual ? 2 : 1;
-    p.tier_len = tier_len;
-    p.batch_len = batch_len;
-    for (int k = 0; k < p.npass; ++k) p.split |= !f0.bplan.known_ok[k];
-    // (:exact returns the occurrence's start and end whatever the output policy: a caller that wants them gets the launch in
-    // its split form — known-alignment class first, exact kernel for what that lists)
-    if (dev.algorithm == BDX_ALG_EXACT && (o.pass_start != nullptr || o.pass_end != nullptr)) p.split = true;
-    p.windows = p.split && !ctx->tune.no_windows;
-    // dense window table of the plain-sweep kernel (few barcodes, many genuine candidates per read; columns fit 16 bits)
-    p.dense_w = p.windows && f0.bplan.dense_d && !f0.splan.enabled && batch_len <= 60000 && !ctx->tune.no_dense;
-    // restricted runs of passes that only report score (+ end) through the clean-class DP start m + kb columns before
-    // the first end column (orc_selftest_clean_short_lookback); everything else keeps 2 (m + kb) + 1
-    for (int k = 0; k < p.npass; ++k) {
-        const int ts = dev.pass[k].trim_side;
-        p.short_lb[k] = (ctx->plan.clean || ctx->plan.band_roll) && dev.algorithm == BDX_ALG_SEMIGLOBAL && !dev.need_traceback &&
-                        (ts == 0 || (ts == 5 && o.pass_start == nullptr));
-    }
-    for (BdxFilterSet &f : ctx->fs) {
-        f.bplan.short_lb[0] = p.short_lb[0];
-        f.bplan.short_lb[1] = p.short_lb[1];
-        f.bplan.n_cu = ctx->n_cu;
-    }
-    // Wave-autonomous kernel (bdx_wave.hip) in front of the general one: it answers the reads of the known-score
-    // class and lists the rest — as tier 1 of a tiered config, or (plain configs) ahead of the same filter set
-    // in list mode.  The list-mode plan is made first: if it cannot be made, the general kernel runs alone.
-    // (window mode first: reads much longer than their column window — only the windows are fetched)
-    if (!p.split && !dev.vlen) {
-        BdxWavePlan &wp = tiered ? f1.wplan : f0.wplan;
-        if ((size_wave_win(ctx, wp, batch_len, n_reads) || size_wave(ctx, wp, batch_len, n_reads)) &&
-            (tiered || size_bitpar(ctx, 0, batch_len, n_reads, true))) {
-            p.front = wp.winm ? Front::wave_win : Front::wave;
-            p.wfront = &wp;
-        }
-        if (!tiered && p.front == Front::none) (void)size_bitpar(ctx, 0, batch_len, n_reads);  // (restore the dense plan)
-    }
-    // Known-end class (trim_side = 5, single pass, no start positions or statistics wanted): the same kernel in its
-    // known-end form answers the reads it can settle, trimmed keep range included; the listed rest goes through the
-    // split path (filter in list mode -> exact kernel in list mode).
-    bool trim3 = false;  // (a trim_side = 3 pass of the known-trim class knows its start only)
-    for (int k = 0; k < p.npass; ++k) trim3 |= dev.pass[k].trim_side == 3;
-    const bool kend_ok = p.split && p.windows && !dev.vlen && !p.dense_w && o.pass_start == nullptr && !stats && !(trim3 && o.pass_end != nullptr);
-    // known-alignment class: the caller wants positions the known-trim class does not know, or the statistics tables
-    p.aln = p.split && p.windows && !dev.vlen && !p.dense_w && !kend_ok && ctx->fs[tiered ? 1 : 0].wplan_a.enabled;
-    if (kend_ok || p.aln) {
-        BdxWavePlan &wk = tiered ? (p.aln ? f1.wplan_a : f1.wplan_k) : (p.aln ? f0.wplan_a : f0.wplan_k);
-        if (size_wave(ctx, wk, batch_len, n_reads)) {
-            if (tiered || size_bitpar(ctx, 0, batch_len, n_reads, true)) {
-                p.front = Front::wave_end;
-                p.wfront = &wk;
-            } else {
-                (void)size_bitpar(ctx, 0, batch_len, n_reads);  // (restore the dense plan)
-            }
-        }
-    }
-    // split configs (trimming, summary, weighted costs): the wave kernel as the FILTER of a dense launch — candidate
-    // masks and column windows in the formats of the general kernel's split mode, every verdict from the exact
-    // kernel as before.  Tiered: tier 1 (all reads); plain: the only filter launch.
-    bool wsplit0 = false;
-    if (p.split && p.windows && !dev.vlen && p.front == Front::none) {
-        if (tiered && f1.wplan.split && size_wave(ctx, 1, batch_len, n_reads)) p.front = Front::wave_split;
-        if (!tiered) wsplit0 = f0.wplan.split && !p.dense_w && size_wave(ctx, 0, batch_len, n_reads);
-    }
-    // the pairs tier: tier 1's filter is the same-diagonal pairs mode over every read of the batch
-    if (tiered && p.front != Front::wave_end && ctx->pairs_tier && p.split && p.windows && !p.dense_w && !dev.vlen &&
-        size_pairs(ctx, f1.pplan, batch_len))
-        p.front = Front::pairs;
-    if (tiered && p.front == Front::none) p.front = Front::bitpar;
-    p.t1_exact = tiered && p.split && p.front != Front::wave_end;
-    // Carried passes: tier 1 of a dual known-class config lists a read when ONE of its passes is open; the pass it settled goes
-    // along (two state bits on the list entry + the pass's winning survivor in d_carry[read]) and the pairs mode only looks for
-    // the other pass's barcodes — about half of its sweeps for C4.  Only when the pairs mode in its known form is what reads
-    // tier 1's list (nothing else understands the state bits), reads fit 30 bits and min_delta = 0 (a lone carried winner
-    // then IS the pass's result).
-    // (the known-trim / known-alignment forms and the plain known-score form of a dual config without trimming)
-    if (tiered && (p.front == Front::wave_end || p.front == Front::wave) && dev.is_dual && dev.min_delta == 0.0 && !ctx->tune.no_carry &&
-        n_reads < (1LL << 30) && o.pass_start == nullptr && o.pass_end == nullptr && o.pass_raw == nullptr && o.pass_bc == nullptr &&
-        o.pass_score == nullptr && o.pass_delta == nullptr) {
-        BdxWavePlan &pp = p.front == Front::wave_end ? (p.aln ? f0.pplan_a : f0.pplan_k) : f0.pplan;
-        p.carry = size_pairs(ctx, pp, tier_len) && pp.groups <= 1 && pp.pairs_kb <= 4 && !pp.split;
-    }
-    if (tiered) {
-        // tier 0 walks the list: scattered reads -> slot staging
-        // (tier 0 sees a fraction of the batch — 10..25 % in the bench configs: its tile size is planned for a sixteenth of
-        // the batch, so that the list of a small batch still spreads over the device — C5, 400 k reads: tiles of 16 instead
-        // of 128 reads, 0.42 -> 0.38 ms; batches of millions of reads keep their tiles)
-        long long n_list_est = n_reads / (ctx->tune.tier0_div > 0 ? ctx->tune.tier0_div : 16);
-        if (n_list_est < 1) n_list_est = 1;
-        if (!size_bitpar(ctx, 0, tier_len, n_list_est, true)) return fail(ctx, BDX_E_DEVICE, "internal: tier 0 cannot be planned in list mode");
-    }
-    // Pairs mode of the wave kernel between tier 1 and the general kernel: the listed reads are gathered into slots and
-    // filtered at the full budgets by the two-intact-pieces lemma.  Known-score configs: it answers them (what it cannot
-    // answer goes on to the general kernel in list mode); split configs: it is tier 0's filter (masks + windows of the
-    // listed reads for the exact kernel).  Known-end class: the pairs mode answers the listed reads itself (verdict +
-    // trimmed keep range); what it cannot answer goes on to the split path in list mode.
-    // Same-diagonal pairs mode as the ONLY filter of a split config without tiers (weighted costs whose full budget is beyond
-    // every seeded variant — the reference's demo2 options): every read of the batch is laid out in slots and scanned;
-    // masks + windows of all reads go to the exact kernel's dense launch.
-    BdxWavePlan &pk = p.aln ? f0.pplan_a : f0.pplan_k;
-    p.wmid = &f0.pplan;
-    if (tiered && (kend_ok || p.aln) && size_pairs(ctx, pk, tier_len)) {
-        p.middle = Middle::end;
-        p.wmid = &pk;
-    } else if (tiered && (!p.split || p.windows) && !p.dense_w && size_pairs(ctx, tier_len)) {
-        p.middle = p.split ? Middle::split : Middle::list;
-    } else if (!tiered && p.split && p.windows && !p.dense_w && !wsplit0 && p.front != Front::wave_end && !dev.vlen && f0.pplan.enabled &&
-               f0.pplan.pairs_kb >= 8 && f0.pplan.split && size_pairs(ctx, batch_len)) {
-        p.middle = Middle::all;
-    }
-    p.full = (p.middle == Middle::split || p.middle == Middle::all) ? Full::none : wsplit0 ? Full::wave_split : Full::bitpar;
-    p.exact = !p.split ? Exact::known : p.front != Front::none ? Exact::split_list : Exact::split;
-    return BDX_OK;
-}
+// ---- one filtered classify call: plan (bdx_plan_call, bdx_call.cpp), reserve (buffers, poison, scratch), enqueue ----------------
 
 // Buffers of the plan's hand-overs, the test switch's fills, this call's half of the scratch block and the per-launch
 // fields of the plans.
-static int reserve(bdx_ctx *ctx, const CallPlan &p, long long n_reads) {
+static int reserve(bdx_ctx *ctx, CallPlan &p, long long n_reads) {
     const bool tiered = p.tier_len > 0;
     const size_t list_bytes = (size_t)n_reads * 4 + 64;
     for (int k = 0; k < p.npass; ++k) {
@@ -1001,11 +542,9 @@ static int reserve(bdx_ctx *ctx, const CallPlan &p, long long n_reads) {
     if (!p.split) HIP_TRY(ctx, ctx->d_exc.ensure(list_bytes));
     if (tiered) HIP_TRY(ctx, ctx->d_tier.ensure(list_bytes));
     if ((!tiered && p.front != Front::none) || p.middle == Middle::end || p.middle == Middle::list) HIP_TRY(ctx, ctx->d_wlist.ensure(list_bytes));
-    for (BdxFilterSet &f : ctx->fs)
-        f.wplan.d_carry = f.pplan.d_carry = f.wplan_k.d_carry = f.wplan_a.d_carry = f.pplan_k.d_carry = f.pplan_a.d_carry = nullptr;
     if (p.carry) {
         HIP_TRY(ctx, ctx->d_carry.ensure(list_bytes));
-        p.wfront->d_carry = p.wmid->d_carry = (uint32_t *)ctx->d_carry.p;
+        p.wfront.d_carry = p.wmid.d_carry = (uint32_t *)ctx->d_carry.p;
     }
     if (ctx->tune.poison) {
         // test switch: whatever a consumer reads without a producer having written it is garbage on EVERY run
@@ -1027,7 +566,7 @@ static int reserve(bdx_ctx *ctx, const CallPlan &p, long long n_reads) {
     ctx->scratch_zeroed = false;
     ctx->scratch_clean[spar] = false;  // (a call that fails half-way leaves it that way: the next one clears it itself)
     for (int set = tiered ? 1 : 0; set >= 0; --set) {
-        BdxBitparPlan &b = ctx->fs[set].bplan;
+        BdxBitparPlan &b = set ? p.t1 : p.fused;
         b.d_tile_counter = (int *)(scratch + (set ? 256 : 64));
         b.dense_w = set ? 0 : p.dense_w;
         b.grid_override = ctx->tune.grid;
@@ -1097,8 +636,8 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const uint8_t *seq, const lo
     // one launcher per kernel family; `filter`: the split form (masks + windows into wsp, no verdicts, no list)
     const auto counted = [](hipError_t e, int64_t &launches) { if (e == hipSuccess) launches += 1; return e; };
     const int he = ctx->plan.hist_entries, dbg = ctx->tune.debug;
-    const auto bitpar = [&](const BdxFilterSet &f, const BdxTierArgs *t) {
-        return bdx_launch_bitpar(ctx->dev, ctx->plan, f.bplan, f.splan, seq, off, n_reads, o, ctx->counts, c0, c1, ctx->stream, w0, w1, n0, n1,
+    const auto bitpar = [&](int set, const BdxTierArgs *t) {
+        return bdx_launch_bitpar(ctx->dev, ctx->plan, set ? p.t1 : p.fused, bdx_seed_plan(ctx->fs[set], p.seed[set]), seq, off, n_reads, o, ctx->counts, c0, c1, ctx->stream, w0, w1, n0, n1,
                                  p.split ? 1 : 0, exc_list, exc_count, t);
     };
     const auto wave = [&](const BdxWavePlan &wp, int tier1, bool filter) {
@@ -1133,12 +672,12 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const uint8_t *seq, const lo
     // 1. front stage
     switch (p.front) {
         case Front::none: break;
-        case Front::bitpar: HIP_TRY(ctx, bitpar(f1, &t1)); break;
-        case Front::wave: HIP_TRY(ctx, wave(*p.wfront, tiered, false)); break;
-        case Front::wave_win: HIP_TRY(ctx, wave_win(*p.wfront, tiered)); break;
-        case Front::wave_split: HIP_TRY(ctx, wave(f1.wplan, 0, true)); break;  // (the exact kernel settles and lists)
-        case Front::wave_end: HIP_TRY(ctx, wave_end(*p.wfront, tiered)); break;  // verdicts + trimmed keep range of what it settles
-        case Front::pairs: HIP_TRY(ctx, pairs(f1.pplan, nullptr, nullptr, true, nullptr)); break;
+        case Front::bitpar: HIP_TRY(ctx, bitpar(1, &t1)); break;
+        case Front::wave: HIP_TRY(ctx, wave(p.wfront, tiered, false)); break;
+        case Front::wave_win: HIP_TRY(ctx, wave_win(p.wfront, tiered)); break;
+        case Front::wave_split: HIP_TRY(ctx, wave(p.wfront, 0, true)); break;  // (the exact kernel settles and lists)
+        case Front::wave_end: HIP_TRY(ctx, wave_end(p.wfront, tiered)); break;  // verdicts + trimmed keep range of what it settles
+        case Front::pairs: HIP_TRY(ctx, pairs(p.wfront, nullptr, nullptr, true, nullptr)); break;
     }
     // 2. tier 1's exact launch: it answers what tier 1 settles and lists the rest (known-score / known-end configs: the filter kernel did)
     if (p.t1_exact) {
@@ -1153,10 +692,10 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const uint8_t *seq, const lo
     // 3. middle stage
     switch (p.middle) {
         case Middle::none: break;
-        case Middle::end: HIP_TRY(ctx, pairs(*p.wmid, t0.in_list, t0.in_count, false, p.aln ? stp : nullptr)); break;
-        case Middle::list: HIP_TRY(ctx, pairs(*p.wmid, t0.in_list, t0.in_count, false, nullptr)); break;
-        case Middle::split: HIP_TRY(ctx, pairs(*p.wmid, t0.in_list, t0.in_count, true, nullptr)); break;
-        case Middle::all: HIP_TRY(ctx, pairs(*p.wmid, nullptr, nullptr, true, nullptr)); break;
+        case Middle::end: HIP_TRY(ctx, pairs(p.wmid, t0.in_list, t0.in_count, false, p.aln ? stp : nullptr)); break;
+        case Middle::list: HIP_TRY(ctx, pairs(p.wmid, t0.in_list, t0.in_count, false, nullptr)); break;
+        case Middle::split: HIP_TRY(ctx, pairs(p.wmid, t0.in_list, t0.in_count, true, nullptr)); break;
+        case Middle::all: HIP_TRY(ctx, pairs(p.wmid, nullptr, nullptr, true, nullptr)); break;
     }
     if (p.middle == Middle::end || p.middle == Middle::list) {  // what the pairs mode cannot answer goes on in list mode
         t0.in_list = mid_list;
@@ -1166,8 +705,8 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const uint8_t *seq, const lo
     // 4. full-budget filter
     switch (p.full) {
         case Full::none: break;  // (the pairs mode already wrote the masks and windows)
-        case Full::wave_split: HIP_TRY(ctx, wave(f0.wplan, 0, true)); break;
-        case Full::bitpar: HIP_TRY(ctx, bitpar(f0, p.front != Front::none ? &t0 : nullptr)); break;
+        case Full::wave_split: HIP_TRY(ctx, wave(p.wfull, 0, true)); break;
+        case Full::bitpar: HIP_TRY(ctx, bitpar(0, p.front != Front::none ? &t0 : nullptr)); break;
     }
     // 5. exact stage (its last launch clears the other scratch half for the next call)
     switch (p.exact) {
@@ -1198,23 +737,6 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const uint8_t *seq, const lo
     }
 #endif
     return BDX_OK;
-}
-
-// ctx->path of a filtered call: its stages, front first
-static std::string call_path(const bdx_ctx *ctx, const CallPlan &p) {
-    const BdxSeedPlan &sp = ctx->fs[0].splan;
-    std::string s = sp.enabled ? (sp.diag ? "qgram2+bitpar+verify" : "qgram+bitpar+verify") : "bitpar+verify";
-    if (p.full == Full::wave_split) s = "wave+verify";
-    switch (p.middle) {
-        case Middle::none: break;
-        case Middle::end: s = (p.aln ? "pairs(aln) > " : "pairs(end) > ") + s; break;
-        case Middle::list: s = "pairs > " + s; break;
-        case Middle::split: s = "pairs+verify"; break;
-        case Middle::all: s = "pairs(diag)+verify"; break;
-    }
-    static const char *const front[] = {"", "qgram+bitpar", "wave", "wave(win)", "wave", "wave(end)", "pairs(diag)"};
-    if (p.front == Front::none) return s;
-    return std::string(p.tier_len > 0 ? "tier1:" : "") + (p.front == Front::wave_end && p.aln ? "wave(aln)" : front[(int)p.front]) + " > " + s;
 }
 
 int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int64_t *d_seq_off, int64_t n_reads,
@@ -1264,11 +786,9 @@ int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int6
         st.overflow = (unsigned int *)ctx->st_flag.p;
         stp = &st;
     }
-    bool filtered = false;
-    int tier_len = 0;  // > 0: tiered budgets apply to this batch (the read length both tiers were planned for)
-    int batch_len = 0;  // the read length the filtered launches were planned for
+    int len = 0;  // the read length the filtered launches are planned for
     if (ctx->fs[0].bplan.enabled) {
-        int len = ctx->virt_maxlen > 0 ? ctx->virt_maxlen : ctx->user_len_hint;
+        len = ctx->virt_maxlen > 0 ? ctx->virt_maxlen : ctx->user_len_hint;
         if (len <= 0 && measured_len >= 0) len = measured_len > 0 ? measured_len : 1;
         if (len <= 0) {  // measure the batch: one tiny kernel + a 4-byte copy
             int host_len = 0;
@@ -1277,20 +797,26 @@ int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int6
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             len = host_len;
         }
-        batch_len = len;
-        filtered = size_bitpar(ctx, 0, len, n_reads);
-        // both tiers must be plannable for this batch, else the full budget alone
-        if (filtered && ctx->tiered && size_bitpar(ctx, 1, len, n_reads)) tier_len = len;
     }
-    if (filtered) {
-        CallPlan p;
-        int rc = plan_call(ctx, o, stp != nullptr, n_reads, batch_len, tier_len, p);
-        if (rc == BDX_OK) rc = reserve(ctx, p, n_reads);
+    const BdxCallEnv env{ctx->dev, ctx->plan, ctx->fs[0], ctx->fs[1], *ctx, ctx->tune, ctx->n_cu};
+    BdxCallArgs args;
+    args.n_reads = n_reads;
+    args.read_len = len;
+    args.window_upload = ctx->dev.vlen != nullptr;
+    void *const vectors[10] = {o.bc1, o.bc2, o.keep_start, o.keep_end, o.pass_start, o.pass_end, o.pass_raw, o.pass_bc, o.pass_score, o.pass_delta};
+    for (int i = 0; i < 10; ++i) args.wanted |= vectors[i] ? 1u << i : 0u;
+    args.stats = stp != nullptr;
+    CallPlan &p = ctx->last;
+    std::string why;
+    int rc = bdx_plan_call(env, args, ctx->seed, p, why);
+    if (rc != BDX_OK) return fail(ctx, rc, "%s", why.c_str());
+    if (p.filtered) {
+        rc = reserve(ctx, p, n_reads);
         if (rc == BDX_OK) rc = enqueue(ctx, p, d_seq_bytes, (const long long *)d_seq_off, n_reads, o, stp);
         if (rc != BDX_OK) return rc;
-        ctx->last_blocks = (n_reads + ctx->fs[0].bplan.reads_per_block - 1) / ctx->fs[0].bplan.reads_per_block;
-        ctx->path = call_path(ctx, p);
-        ctx->filter_used = ctx->fs[0].splan.enabled ? BDX_FILTER_QGRAM : BDX_FILTER_BITPAR;
+        ctx->last_blocks = (n_reads + p.fused.reads_per_block - 1) / p.fused.reads_per_block;
+        ctx->path = p.path;
+        ctx->filter_used = bdx_seed_plan(ctx->fs[0], p.seed[0]).enabled ? BDX_FILTER_QGRAM : BDX_FILTER_BITPAR;
     } else {
         HIP_TRY(ctx, bdx_launch_generic(ctx->dev, ctx->plan, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
                                         ctx->counts, nullptr, nullptr, ctx->stream, nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -1426,11 +952,12 @@ int64_t bdx_last_launches(const bdx_ctx *ctx, char *buf, int64_t cap) {
 
 int32_t bdx_launch_info(const bdx_ctx *ctx, bdx_launch_info_t *out) {
     if (!ctx || !out) return BDX_E_INVALID;
-    const bool f = ctx->filter_used != BDX_FILTER_OFF && ctx->fs[0].bplan.reads_per_block > 0;
+    const CallPlan &p = ctx->last;  // (filtered: the last call ran the fused kernel's path)
+    const bool f = ctx->filter_used != BDX_FILTER_OFF && p.filtered;
     out->threads_per_block = f ? 256 : ctx->plan.threads;
-    out->lds_bytes_per_block = f ? (int32_t)bdx_bitpar_lds_bytes(ctx->dev, ctx->fs[0].bplan, ctx->plan, &ctx->fs[0].splan) : (int32_t)ctx->plan.lds_bytes;
+    out->lds_bytes_per_block = f ? (int32_t)p.lds_bytes : (int32_t)ctx->plan.lds_bytes;
     out->blocks = ctx->last_blocks;
-    out->reads_per_block = f ? ctx->fs[0].bplan.reads_per_block : ctx->plan.threads;
+    out->reads_per_block = f ? p.fused.reads_per_block : ctx->plan.threads;
     out->filter_used = ctx->filter_used;
     out->max_m = ctx->dev.max_m;
     out->launches = ctx->launches;

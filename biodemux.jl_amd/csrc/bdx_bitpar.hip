@@ -93,9 +93,7 @@ struct BitparArgs {
 // The product library has no phase-skip switches: BDX_DBG folds to 0 and the branches disappear.
 // reads indexed at a time by the two-intact-pieces variant (5 KiB of index each).  4 instead of 8 gives a fourth
 // workgroup per CU in list mode: measured +3 % on C2d, +6 % at 384 barcodes, -3.5 % at 96 barcodes on small batches
-#ifndef BDX_DIAG_SB_NARROW
-#define BDX_DIAG_SB_NARROW 8
-#endif
+// (BDX_DIAG_SB_NARROW, 8 unless the build says otherwise: bdx_internal.h)
 #ifdef BDX_TUNING
 #define BDX_DBG(bit) (a.dbg & (bit))
 #else
@@ -126,6 +124,7 @@ __global__ __launch_bounds__(BS, 4) void bdx_bitpar_kernel(const BitparArgs a) {
     // NW (DIAG): position words per 4-mer key: 5 for reads of <= 152 staged bases, 10 for <= 312
     constexpr int SBMAX = NW <= 5 ? BDX_DIAG_SB_NARROW : 4;  // index sub-batch: SBMAX x 5 KiB (NW = 5) or x 10 KiB
     constexpr int SB = DIAG ? (R < SBMAX ? R : SBMAX) : R;  // DIAG: reads indexed at a time (5 KiB of index each); larger tiles are walked in sub-batches
+    // (the carve-up below is what bdx_bitpar_lds_bytes, bdx_call.cpp, adds up on the host: change both together)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     LDS unsigned char *smem = (LDS unsigned char *)smem_raw;
     const BdxDevCfg &cfg = a.cfg;
@@ -1215,14 +1214,14 @@ hipError_t launch_one(const BitparArgs &a, size_t lds, long long n_reads, hipStr
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
     if (dev < 0 || !attr_set[dev].load(std::memory_order_acquire)) {
         hipError_t e = hipFuncSetAttribute((const void *)bdx_bitpar_kernel<BS, R, SEED, DIAG, NW, WL>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, BDX_LDS_MAX);
         if (e != hipSuccess) return e;
         if (dev >= 0) attr_set[dev].store(true, std::memory_order_release);
     }
     // persistent grid: enough workgroups to fill every CU at the LDS-limited residency,
     // never more than there are tiles
     const long long tiles = (n_reads + R - 1) / R;
-    long long per_cu = (long long)((160 * 1024) / (lds ? ((lds + 1279) / 1280) * 1280 : 1));  // 1280-byte LDS granules
+    long long per_cu = bdx_lds_residency(lds);
     if (per_cu < 1) per_cu = 1;
     if (per_cu > 8) per_cu = 8;
     long long blocks = (long long)(n_cu > 0 ? n_cu : 256) * per_cu;  // exactly the resident set; the tile queue balances it
@@ -1239,42 +1238,6 @@ hipError_t launch_one(const BitparArgs &a, size_t lds, long long n_reads, hipStr
 }
 
 }  // namespace
-
-size_t bdx_bitpar_lds_bytes(const BdxDevCfg &cfg, const BdxBitparPlan &bp, const BdxGenericPlan &gp,
-                            const BdxSeedPlan *sp) {
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const int R = bp.reads_per_block;
-    const int B0 = cfg.pass[0].n_barcodes, B1 = cfg.is_dual ? cfg.pass[1].n_barcodes : 0;
-    const int cw0 = cfg.pass[0].cand_words, cw1 = cfg.is_dual ? cfg.pass[1].cand_words : 0;
-    size_t o = 0;
-    o += al((size_t)gp.hist_entries * 4) + al(256);
-    const size_t wb = bp.word_bytes >= 8 ? (size_t)bp.word_bytes : 4;
-    o += al((size_t)bp.ncodes * bp.bpad[0] * wb) + al(cfg.is_dual ? (size_t)bp.ncodes * bp.bpad[1] * wb : 0);
-    o += al((size_t)B0 * wb) + al((size_t)B1 * wb) + al((size_t)B0 * 4) + al((size_t)B1 * 4);
-    o += al((size_t)R * (cw0 + cw1) * 4) + al((size_t)(R + 1) * 4) + 4 * al((size_t)R * 4) + al((size_t)R * 16);
-    const bool seeded = sp && sp->enabled;
-    const int sc = (!seeded && bp.dense_d) ? 4 : (bp.slot_cap > 4 ? bp.slot_cap : 4);
-    o += al((size_t)2 * R * sc * 4) + al((size_t)2 * R * 4) + al((size_t)2 * R);
-    o += al((size_t)bp.stage_bytes + 16);
-    if (sp && sp->enabled && sp->diag) {
-        const int nw = bp.diag_nw > 0 ? bp.diag_nw : 5;
-        const int sbmax = nw <= 5 ? BDX_DIAG_SB_NARROW : 4;
-        const int SBh = R < sbmax ? R : sbmax;  // index sub-batch (see the kernel)
-        o += al((size_t)(bp.stage_bytes >> 2) + 32) + al((size_t)2 * (bp.diag_qcap > 0 ? bp.diag_qcap : 64) * SBh * 4);
-        o += al((size_t)R) + 2 * al((size_t)R * 4);
-        o += al((size_t)SBh * 256 * nw * 4) + al((size_t)B0 * 4) + al((size_t)B1 * 4) + al((size_t)B0 * 8) + al((size_t)B1 * 8);
-    } else if (sp && sp->enabled) {
-        o += al((size_t)sp->bm_words * 4) + al((size_t)(bp.stage_bytes >> 2) + 32);
-        if (sp->hash_in_lds) o += al((size_t)4 << sp->hash_log2) + al((size_t)1 << sp->hash_log2);
-        const size_t sq = (size_t)2 * (sp->qmul >= 4 ? sp->qmul : 4) * R;  // hit-queue entries
-        o += al(sq * 4) + al(sq) + 3 * al((size_t)R * sp->rcap * 4);
-        o += al((size_t)R) + 2 * al((size_t)R * 4);
-    }
-    o += al(32);
-    if (!(sp && sp->enabled) && cfg.is_dual) o += al((size_t)R);  // act[]
-    if (!(sp && sp->enabled) && bp.dense_d) o += al((size_t)R * (B0 + B1));  // dtab[]
-    return o;
-}
 
 hipError_t bdx_launch_bitpar(const BdxDevCfg &cfg, const BdxGenericPlan &gp, const BdxBitparPlan &bp,
                              const BdxSeedPlan &sp, const uint8_t *d_seq, const long long *d_off, long long n_reads, const BdxDevOut &out,

@@ -38,17 +38,10 @@ struct Bytes<false> {
     __device__ __forceinline__ Bytes<false> at(long long o) const { return Bytes<false>{p + o}; }
 };
 
-// resolve(), classification.jl:96-100, with Julia's UnitRange normalisation (empty a:b has
-// last == a-1; the callers use last(range), :800-801).
+// resolve(), classification.jl:96-100: the one copy the host planners share (bdx_internal.h)
 __device__ __forceinline__ void resolve_range(const BdxDevRange &dr, long long len, long long &first,
                                               long long &last) {
-    long long s = dr.start_from_end ? len + dr.start_offset : dr.start_offset;
-    long long e = dr.end_from_end ? len + dr.end_offset : dr.end_offset;
-    long long a = s > 1 ? s : 1;
-    long long b = e < len ? e : len;
-    if (b < a) b = a - 1;
-    first = a;
-    last = b;
+    bdx_resolve_range(dr, len, first, last);
 }
 
 // semiglobal_alignment_core, classification.jl:238-445, one (read, barcode) pair per lane.

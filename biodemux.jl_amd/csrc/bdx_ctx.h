@@ -5,7 +5,7 @@
 #include <string>
 #include <vector>
 
-#include "bdx_plan.h"  // BdxSetPlans, BdxPlanChoice and the planner's output (bdx_internal.h comes with it)
+#include "bdx_call.h"  // CallPlan, BdxSeedChoice; with it bdx_plan.h: BdxSetPlans, BdxPlanChoice and the planner's output (and bdx_internal.h)
 
 #define BDX_FQ_SCRATCH 12  // scratch buffers of the device FASTQ pipeline (bdx_fastq.hip)
 #define BDX_DFL_SCRATCH 4  // scratch buffers of the device DEFLATE encoder (bdx_deflate.hip)
@@ -67,6 +67,8 @@ struct bdx_ctx : BdxPlanChoice {  // (tiered, tier_q, tier_cap_fixed, pairs_tier
     BdxDevCfg dev{};
     BdxGenericPlan plan{};
     BdxFilterSet fs[2];
+    BdxSeedChoice seed[2] = {BDX_SEED_MAIN, BDX_SEED_MAIN};  // per set: the seed plan in effect — the planning state that outlives a call
+    CallPlan last;           // the last classify call's plan (bdx_launch_info reports from it)
     BdxTuning tune{};
     DevBuf d_maxlen;
     DevBuf d_tier;      // tiered budgets: reads handed from tier 1 to tier 0

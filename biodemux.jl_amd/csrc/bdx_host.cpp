@@ -245,15 +245,7 @@ void scan_offsets(const int64_t *seq_off, int64_t n_reads, int64_t &mx_out, bool
 // position for :hamming / :exact.
 void host_union_window(const BdxDevCfg &cfg, long long n_ll, long long &ulo, long long &uhi) {
     const long long n = n_ll > (1LL << 30) ? (1LL << 30) : n_ll;
-    const auto resolve = [&](const BdxDevRange &dr, long long &first, long long &last) {
-        const long long s = dr.start_from_end ? n + dr.start_offset : dr.start_offset;
-        const long long e = dr.end_from_end ? n + dr.end_offset : dr.end_offset;
-        const long long a = s > 1 ? s : 1;
-        long long b = e < n ? e : n;
-        if (b < a) b = a - 1;
-        first = a;
-        last = b;
-    };
+    const auto resolve = [&](const BdxDevRange &dr, long long &first, long long &last) { bdx_resolve_range(dr, n, first, last); };
     ulo = (1LL << 40);
     uhi = 0;
     const bool sgm = cfg.algorithm == BDX_ALG_SEMIGLOBAL;
@@ -348,7 +340,6 @@ int classify_host_windows(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t 
     ctx->dev.vlo = (const int32_t *)ctx->d_vlo.p;
     ctx->virt_maxlen = (int)(maxlen > (1LL << 30) ? (1LL << 30) : (maxlen < 1 ? 1 : maxlen));
     const int rc = run_and_download(ctx, (const uint8_t *)ctx->d_seq.p, (const int64_t *)ctx->d_off.p, n_reads, out);
-    for (BdxFilterSet &f : ctx->fs) f.bplan.read_len_hint = 0;  // the slot geometry was forced: plan afresh for ordinary batches
     if (rc == BDX_OK) ctx->window_uploads += 1;
     return rc == BDX_OK ? 0 : rc;
 }

@@ -1,5 +1,5 @@
-// bdx_internal.h — structures shared between the host side (the create-time planner bdx_plan.cpp, the C-ABI translation
-// unit bdx_abi.cpp) and the gfx950 kernels (bdx_device.hip).  Not part of the public ABI.
+// bdx_internal.h — structures shared between the host side (the create-time planner bdx_plan.cpp, the per-call planner
+// bdx_call.cpp, the C-ABI translation unit bdx_abi.cpp) and the gfx950 kernels (bdx_device.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -68,6 +68,23 @@ struct BdxDevRange {
     int start_from_end;
     int end_from_end;
 };
+
+// resolve(), classification.jl:96-100, with Julia's UnitRange normalisation (empty a:b has
+// last == a-1; the callers use last(range), :800-801).
+__host__ __device__ __forceinline__ void bdx_resolve_range(const BdxDevRange &dr, long long len, long long &first, long long &last) {
+    long long s = dr.start_from_end ? len + dr.start_offset : dr.start_offset;
+    long long e = dr.end_from_end ? len + dr.end_offset : dr.end_offset;
+    long long a = s > 1 ? s : 1;
+    long long b = e < len ? e : len;
+    if (b < a) b = a - 1;
+    first = a;
+    last = b;
+}
+
+// LDS of a compute unit, and how many workgroups of `lds` bytes share it: LDS is allocated in 1280-byte granules
+// (measured: 54128 B -> 2 per CU, 51872 B -> 3)
+#define BDX_LDS_MAX ((size_t)160 * 1024)
+inline int bdx_lds_residency(size_t lds) { return lds ? (int)(BDX_LDS_MAX / (((lds + 1279) / 1280) * 1280)) : (int)BDX_LDS_MAX; }
 
 struct BdxDevPass {
     BdxDevRange ref_search, bc_start, bc_end;
@@ -268,9 +285,14 @@ struct BdxTierArgs {
     const unsigned int *in_count;
 };
 
-// Implemented in bdx_bitpar.hip.
+// index sub-batch of the fused kernel's diagonal variant at the narrow index width (bdx_bitpar.hip)
+#ifndef BDX_DIAG_SB_NARROW
+#define BDX_DIAG_SB_NARROW 8
+#endif
+// LDS bytes of a workgroup of the fused kernel (bdx_call.cpp; mirrors the carve-up at the head of bdx_bitpar_kernel)
 size_t bdx_bitpar_lds_bytes(const BdxDevCfg &cfg, const BdxBitparPlan &bp, const BdxGenericPlan &gp,
                             const BdxSeedPlan *sp = nullptr);
+// Implemented in bdx_bitpar.hip.
 hipError_t bdx_launch_bitpar(const BdxDevCfg &cfg, const BdxGenericPlan &gp, const BdxBitparPlan &bp,
                              const BdxSeedPlan &sp, const uint8_t *d_seq, const long long *d_off, long long n_reads, const BdxDevOut &out,
                              unsigned long long *d_counts, uint32_t *cand_out0, uint32_t *cand_out1, hipStream_t stream,

@@ -11,7 +11,7 @@
 
 namespace {
 
-const size_t LDS_MAX = 160 * 1024;
+const size_t LDS_MAX = BDX_LDS_MAX;
 
 bool whole(const bdx_range_t &r) { return !r.start_from_end && r.start_offset <= 1 && r.end_from_end && r.end_offset >= 0; }
 

@@ -110,9 +110,9 @@ def classify_kernels() -> list:
     return sorted(k for k in code_object_kernels() if parse(k) is not None)
 
 
-# ---- the wave planner, restated (bdx_plan.cpp: build_seed_tables, build_wave_tables; bdx_abi.cpp: size_wave; bdx_wave_kernel.h: the
+# ---- the wave planner, restated (bdx_plan.cpp: build_seed_tables, build_wave_tables; bdx_call.cpp: size_wave; bdx_wave_kernel.h: the
 # dispatch ladder seeded_ladder; bdx_wave.hip: bdx_wave_table_bytes, bdx_wave_area_bytes) ----
-LDS_MAX = 160 * 1024  # bdx_plan.cpp / bdx_abi.cpp LDS_MAX
+LDS_MAX = 160 * 1024  # bdx_internal.h BDX_LDS_MAX
 
 
 def wave_seed_plan(ms, rate: float) -> dict:

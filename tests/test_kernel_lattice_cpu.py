@@ -45,7 +45,7 @@ def test_every_instantiation_is_accounted_for():
             assert n in ks, f"PENDING ({why}) names {n}, which the code object does not hold"
     for n, why in KL.UNREACHABLE.items():
         assert n in ks, f"UNREACHABLE names {n}, which the code object does not hold"
-        assert "bdx_plan.cpp" in why or "bdx_abi.cpp" in why or ".hip" in why, f"{n}: the reason must cite the planner condition: {why}"
+        assert "bdx_plan.cpp" in why or "bdx_call.cpp" in why or "bdx_abi.cpp" in why or ".hip" in why, f"{n}: the reason must cite the planner condition: {why}"
 
 
 def test_the_headline_cell_has_a_recipe():
@@ -54,7 +54,7 @@ def test_the_headline_cell_has_a_recipe():
 
 @pytest.mark.parametrize("name", [n for n in KL.classify_kernels() if KL.recipe(n) is not None])
 def test_recipe_lands_in_its_cell(name):
-    """The rules (form from the config, geometry from size_wave) put both batches of the recipe in the target cell; the
+    """The rules (form from the config, geometry from size_wave of bdx_call.cpp) put both batches of the recipe in the target cell; the
     edge batch's longest read is the longest that stays there and the main batch's the shortest that holds a barcode with
     flanks; both batches end in a ragged tile and walk at least two tiles per resident wave of the one CU.  BDX_WAVE_RW is
     forced only where no read length reaches the cell with the planner's own choice."""
@@ -82,3 +82,45 @@ def test_recipe_lands_in_its_cell(name):
     lens = off[1:] - off[:-1]
     assert len(lens) == rc.n_edge and int(lens.max()) == rc.edge_len == longest
     assert (lens == 0).any() and (lens < rc.m).any() and (seq == ord("N")).any()
+
+
+def test_size_wave_restated_equals_the_call_planner(tmp_path):
+    """Over the lattice's own grid — every recipe's config, both batch sizes, one CU, the forced tile size where the recipe
+    forces one, the read lengths at and beside both ends of its cell — kernel_lattice.size_wave returns what the per-call
+    planner (csrc/bdx_call.cpp, through tests/call_host.cpp) returns: tile, workgroup shape, grid and span, or no wave plan."""
+    import call_cases as CC
+    import plan_cases as PC
+
+    grid = {}
+    for name in KL.classify_kernels():
+        rc = KL.recipe(name)
+        if rc is not None:
+            key = (tuple(sorted(rc.form["kw"].items())), rc.want_pass, rc.m, rc.n_bc, rc.env.get("BDX_WAVE_RW", "0"))
+            grid.setdefault(key, (rc, set()))[1].update((n, L) for n in (rc.n_main, rc.n_edge)
+                                                        for L in (max(rc.low - 1, 1), rc.low, rc.main_len, rc.edge_len, rc.edge_len + 1))
+    assert len(grid) >= 20
+    cases, expect = [], {}
+    for i, (key, (rc, shapes)) in enumerate(sorted(grid.items(), key=lambda kv: kv[0])):
+        kw = dict(key[0])
+        costs = (kw.get("match", 0), kw.get("mismatch", 1), kw.get("indel", 1))
+        tune = dict(n_cu=1, **({"wave_rw": int(key[4])} if key[4] != "0" else {}))
+        shapes = sorted(shapes)
+        cases.append(CC.CallCase("lattice%d" % i, None, [CC.call(n, L, wanted=CC.PASS_START if rc.want_pass else 0) for n, L in shapes],
+                                 passes=[PC.one_pass(rc.barcodes(), trim=kw.get("trim_side") or 0)], rate=KL.RATE, costs=costs, tune=tune))
+        sp = KL.wave_seed_plan([rc.m] * rc.n_bc, KL.RATE)
+        expect["lattice%d" % i] = [KL.size_wave(sp, rc.derived["kend"], rc.cand_words, L, n, 1, int(key[4])) for n, L in shapes]
+    got = CC.run_driver(CC.build_driver(tmp_path), tmp_path, cases=cases)
+    checked = 0
+    for name, want in expect.items():
+        r = got[name]
+        for c, g in enumerate(want):
+            p = r.plan(c)
+            which = "wfull" if p["full"] == "wave_split" else "wfront" if p["front"] in ("wave", "wave_end") else None
+            if g is None:
+                assert which is None, (name, c)
+                continue
+            assert which is not None, (name, c, g)
+            t = r.tiles(which, c)
+            assert dict(rw=t["rw"], waves=t["waves"], blocks=t["blocks"], span=t["span_cap"]) == g, (name, c)
+            checked += 1
+    assert checked >= 100
