@@ -1,6 +1,7 @@
 """The member decoder of the device inflate (csrc/bdx_inflate_core.h as plain C++) under AddressSanitizer and
-UndefinedBehaviorSanitizer: a stand-alone driver with exact-size heap buffers runs every member of tests/inflate_cases.py,
-every prefix of one and a few thousand corrupted ones.  This is where the out-of-bounds handling of bad members is
+UndefinedBehaviorSanitizer: a stand-alone driver with exact-size heap buffers runs every member of tests/inflate_cases.py
+and of tests/inflate_edge_cases.py (the streams zlib's encoder never writes, good and bad), every prefix of the small ones
+and some ten thousand corrupted ones.  This is where the out-of-bounds handling of bad members is
 proven: a read one byte outside a member or a write one byte outside its slot is the sanitizer's to report."""
 import os
 import subprocess
@@ -9,6 +10,7 @@ import numpy as np
 
 import helpers as H
 import inflate_cases as IC
+import inflate_edge_cases as EC
 from test_sanitizers import ENV, SAN
 
 INFLATE_DRIVER = r'''
@@ -85,7 +87,8 @@ int main(int argc, char** argv) {
 
 
 def test_inflate_decoder_under_asan_ubsan(tmp_path):
-    members = list(IC.good_members()) + list(IC.bad_members())
+    edge_bad = [m for m, _ in EC.bad_edge_members()]
+    members = list(IC.good_members()) + list(IC.bad_members()) + list(EC.good_edge_members()) + edge_bad
     for k, m in enumerate(members):
         (tmp_path / ("member_%d.gz" % k)).write_bytes(m.comp)
         (tmp_path / ("member_%d.plain" % k)).write_bytes(m.plain or b"")
@@ -96,5 +99,6 @@ def test_inflate_decoder_under_asan_ubsan(tmp_path):
     subprocess.check_call(["g++", *SAN, "-std=c++17", "-I", os.path.join(H.ROOT, "biodemux.jl_amd", "csrc"), "-o", exe, str(src)])
     out = subprocess.run([exe, str(tmp_path), str(len(members))], env=ENV, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
-    assert "inflate driver ok: %d good, %d bad" % (len(IC.good_members()), len(IC.bad_members())) in out.stdout
+    assert "inflate driver ok: %d good, %d bad" % (len(IC.good_members()) + len(EC.good_edge_members()),
+                                                   len(IC.bad_members()) + len(edge_bad)) in out.stdout
     assert int(out.stdout.split()[-2]) >= 400 * sum(len(m.comp) <= 4000 for m in members)
