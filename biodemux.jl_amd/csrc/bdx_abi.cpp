@@ -556,49 +556,45 @@ static int reserve(bdx_ctx *ctx, CallPlan &p, long long n_reads) {
         for (DevBuf *b : bufs)
             if (b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0xA5, b->cap, ctx->stream));
     }
-    // scratch words (d_maxlen, 1 KiB): +64 tile queue, +128 hand-over count (+132.. tuning statistics),
-    // +192 tier-0 list length, +256 tile queue of the second launch, +320 the pairs mode's list length; one memset clears them all
-    // (the block's two halves alternate between calls: this call's last launch clears the other half for the next call,
-    // which then needs no memset of its own — 5 us of fill + a launch gap per call, 1 % of a 10 M-read C2 step)
+    // this call's half of the scratch block (BdxScratch): one memset clears its words — unless the last call's final launch
+    // already did: the halves alternate, so a call needs no memset of its own (5 us of fill + a launch gap per call, 1 % of a
+    // 10 M-read C2 step)
+    BdxScratch *const scratch = ctx->scratch();
     const int spar = ctx->scratch_par & 1;
-    char *scratch = (char *)ctx->d_maxlen.p + 512 * spar;
-    if (!ctx->scratch_zeroed && !ctx->scratch_clean[spar]) HIP_TRY(ctx, hipMemsetAsync(scratch + 64, 0, 4 * BDX_SCRATCH_WORDS, ctx->stream));
+    if (!ctx->scratch_zeroed && !ctx->scratch_clean[spar]) HIP_TRY(ctx, hipMemsetAsync(scratch->tile_queue, 0, 4 * BDX_SCRATCH_WORDS, ctx->stream));
     ctx->scratch_zeroed = false;
     ctx->scratch_clean[spar] = false;  // (a call that fails half-way leaves it that way: the next one clears it itself)
     for (int set = tiered ? 1 : 0; set >= 0; --set) {
         BdxBitparPlan &b = set ? p.t1 : p.fused;
-        b.d_tile_counter = (int *)(scratch + (set ? 256 : 64));
+        b.d_tile_counter = set ? scratch->tile_queue_t1 : scratch->tile_queue;
         b.dense_w = set ? 0 : p.dense_w;
-        b.grid_override = ctx->tune.grid;
         b.dbg = ctx->tune.debug;
     }
     return BDX_OK;
 }
 
-static int enqueue(bdx_ctx *ctx, const CallPlan &p, const uint8_t *seq, const long long *off, long long n_reads, const BdxDevOut &o,
-                   const BdxDevStats *stp) {
+static int enqueue(bdx_ctx *ctx, const CallPlan &p, const BdxBatch &b, const BdxDevStats *stp) {
     const BdxFilterSet &f0 = ctx->fs[0], &f1 = ctx->fs[1];
-    const bool tiered = p.tier_len > 0, two = p.npass > 1;
-    const int spar = ctx->scratch_par & 1;
-    char *scratch = (char *)ctx->d_maxlen.p + 512 * spar;
-    uint32_t *zero_next = (uint32_t *)((char *)ctx->d_maxlen.p + 512 * (1 - spar) + 64);
-    uint32_t *c0 = (uint32_t *)ctx->d_cand[0].p, *c1 = two ? (uint32_t *)ctx->d_cand[1].p : c0;
-    uint32_t *w0 = p.windows ? (uint32_t *)ctx->d_wins[0].p : nullptr, *w1 = p.windows && two ? (uint32_t *)ctx->d_wins[1].p : w0;
-    uint8_t *n0 = p.windows ? (uint8_t *)ctx->d_wcnt[0].p : nullptr, *n1 = p.windows && two ? (uint8_t *)ctx->d_wcnt[1].p : n0;
-    uint32_t *exc_list = p.split ? nullptr : (uint32_t *)ctx->d_exc.p;
-    unsigned int *exc_count = (unsigned int *)(scratch + 128);
-    // what the front stage cannot settle: tier 1 lists into d_tier, a plain front stage into d_wlist; the pairs mode into d_wlist
-    uint32_t *front_list = (uint32_t *)(tiered ? ctx->d_tier.p : ctx->d_wlist.p), *mid_list = (uint32_t *)ctx->d_wlist.p;
-    unsigned int *front_count = (unsigned int *)(scratch + 192), *mid_count = (unsigned int *)(scratch + 320);
-    const double *slo = f1.bplan.tier_slo;
-    BdxWaveSplit wsp{};
+    const bool tiered = p.tier_len > 0;
+    BdxScratch *const scratch = ctx->scratch();
+    // the hand-over buffers: a single-pass call names pass 0's twice, windows only when the call runs with them
+    BdxHandOver ho{};
     for (int k = 0; k < 2; ++k) {
-        wsp.cw[k] = k < p.npass ? ctx->dev.pass[k].cand_words : 0;
-        wsp.cand_out[k] = k ? c1 : c0;
-        wsp.wins_out[k] = k ? w1 : w0;
-        wsp.wcnt_out[k] = k ? n1 : n0;
-        wsp.short_lb[k] = p.short_lb[k];
+        const int buf = k < p.npass ? k : 0;
+        ho.cand_words[k] = k < p.npass ? ctx->dev.pass[k].cand_words : 0;
+        ho.cand[k] = (uint32_t *)ctx->d_cand[buf].p;
+        ho.wins[k] = p.windows ? (uint32_t *)ctx->d_wins[buf].p : nullptr;
+        ho.wcnt[k] = p.windows ? (uint8_t *)ctx->d_wcnt[buf].p : nullptr;
+        ho.short_lb[k] = p.short_lb[k];
     }
+    // what the known-score fused kernel hands to the exact kernel; what the front stage cannot settle: tier 1 lists into d_tier,
+    // a plain front stage into d_wlist; the pairs mode into d_wlist
+    const BdxDevList none{}, exc{p.split ? nullptr : (uint32_t *)ctx->d_exc.p, &scratch->exc_count};
+    const BdxDevList front{(uint32_t *)(tiered ? ctx->d_tier.p : ctx->d_wlist.p), &scratch->front_count}, mid{(uint32_t *)ctx->d_wlist.p, &scratch->mid_count};
+    const double *slo = f1.bplan.tier_slo;
+    const BdxTierArgs no_lists{}, tier1{none, front, 1, {slo[0], slo[1]}};
+    const BdxTierArgs front_out = tiered ? tier1 : BdxTierArgs{none, front, 0, {0.0, 0.0}};  // a front stage that settles and lists
+    const auto over = [&](const BdxDevList &in, const BdxDevList &out) { return BdxTierArgs{in, out, 0, {0.0, 0.0}}; };
     // diagonal-band DP of the exact kernel (sg_core_band): clean class, every barcode of the config with the same
     // number of rows and of the pass with the same budget, column windows handed over by tracked sweeps
     const auto band_cfg = [&](const BdxFilterSet &f) {
@@ -620,109 +616,91 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const uint8_t *seq, const lo
     };
     // test switch BDX_POISON: between a producer and its consumer, every element the consumer will read must have
     // been written (bdx_poison_check_kernel); `with_windows`: also the window hand-over of both passes for these reads
-    const auto poison_check = [&](const uint32_t *list, const unsigned int *count, bool check_list, bool with_windows, bool packed = false) -> hipError_t {
+    const auto poison_check = [&](const BdxDevList &list, bool check_list, bool with_windows, bool packed = false) -> hipError_t {
         if (!ctx->tune.poison) return hipSuccess;
         unsigned int *dbg = (unsigned int *)ctx->d_dbg.p;
-        uint32_t *l = (uint32_t *)list;
-        if (!with_windows || !p.windows)
-            return l ? bdx_launch_poison_check(l, count, n_reads, nullptr, nullptr, nullptr, 0, 0, (check_list ? 1 : 0) | (packed ? 2 : 0), dbg, ctx->stream) : hipSuccess;
+        if (!with_windows || !p.windows) return list.ids ? bdx_launch_poison_check(b, list, ho, -1, 0, (check_list ? 1 : 0) | (packed ? 2 : 0), dbg) : hipSuccess;
         for (int k = 0; k < p.npass; ++k) {
-            hipError_t e = bdx_launch_poison_check(l, count, n_reads, k ? w1 : w0, k ? n1 : n0, k ? c1 : c0, ctx->dev.pass[k].cand_words,
-                                                   ctx->dev.pass[k].n_barcodes, (check_list && k == 0) ? 1 : 0, dbg, ctx->stream);
+            hipError_t e = bdx_launch_poison_check(b, list, ho, k, ctx->dev.pass[k].n_barcodes, (check_list && k == 0) ? 1 : 0, dbg);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
     };
-    // one launcher per kernel family; `filter`: the split form (masks + windows into wsp, no verdicts, no list)
+    // `filter`: a wave / pairs launch in its split form (masks + windows into the hand-over, no verdicts, no counts, no list)
     const auto counted = [](hipError_t e, int64_t &launches) { if (e == hipSuccess) launches += 1; return e; };
-    const int he = ctx->plan.hist_entries, dbg = ctx->tune.debug;
-    const auto bitpar = [&](int set, const BdxTierArgs *t) {
-        return bdx_launch_bitpar(ctx->dev, ctx->plan, set ? p.t1 : p.fused, bdx_seed_plan(ctx->fs[set], p.seed[set]), seq, off, n_reads, o, ctx->counts, c0, c1, ctx->stream, w0, w1, n0, n1,
-                                 p.split ? 1 : 0, exc_list, exc_count, t);
+    const int he = ctx->plan.hist_entries;
+    const auto wave = [&](const BdxWavePlan &wp, bool filter) {
+        return counted(filter ? bdx_launch_wave(ctx->dev, wp, he, b.uncounted(), ho, no_lists) : bdx_launch_wave(ctx->dev, wp, he, b, BdxHandOver{}, front_out), ctx->wave_launches);
     };
-    const auto wave = [&](const BdxWavePlan &wp, int tier1, bool filter) {
-        return counted(bdx_launch_wave(ctx->dev, wp, he, seq, off, n_reads, o, filter ? nullptr : ctx->counts, tier1,
-                                       tier1 ? slo[0] : 0.0, filter ? nullptr : front_list, filter ? nullptr : front_count, ctx->stream, dbg,
-                                       filter ? &wsp : nullptr, tier1 ? slo[1] : 0.0),
-                       ctx->wave_launches);
-    };
-    const auto wave_win = [&](const BdxWavePlan &wp, int tier1) {
-        return counted(bdx_launch_wave_win(ctx->dev, wp, he, seq, off, n_reads, o, ctx->counts, tier1, tier1 ? slo[0] : 0.0, front_list,
-                                           front_count, ctx->stream, dbg),
-                       ctx->wave_launches);
-    };
-    const auto wave_end = [&](const BdxWavePlan &wp, int tier1) {
-        return counted(bdx_launch_wave_end(ctx->dev, wp, he, seq, off, n_reads, o, ctx->counts, tier1, tier1 ? slo[0] : 0.0, front_list,
-                                           front_count, ctx->stream, dbg, tier1 ? slo[1] : 0.0, p.aln ? stp : nullptr),
-                       ctx->wave_launches);
-    };
-    const auto pairs = [&](const BdxWavePlan &wp, const uint32_t *in_list, const unsigned int *in_count, bool filter, const BdxDevStats *st) {
-        return counted(bdx_launch_pairs(ctx->dev, wp, he, seq, off, n_reads, in_list, in_count, o, filter ? nullptr : ctx->counts,
-                                        filter ? nullptr : mid_list, filter ? nullptr : mid_count, ctx->stream, dbg >> 8, filter ? &wsp : nullptr, st),
+    const auto pairs = [&](const BdxWavePlan &wp, const BdxDevList &in, bool filter, const BdxDevStats *st) {
+        return counted(filter ? bdx_launch_pairs(ctx->dev, wp, he, b.uncounted(), ho, over(in, none), st) : bdx_launch_pairs(ctx->dev, wp, he, b, BdxHandOver{}, over(in, mid), st),
                        ctx->pair_launches);
     };
-    const auto generic = [&](const BdxDevCfg &dv, const uint32_t *list, const unsigned int *count, const BdxTierArgs *t, const double *t_slo,
-                             uint32_t *zero) {
-        return bdx_launch_generic(dv, ctx->plan, seq, off, n_reads, o, ctx->counts, c0, two ? c1 : nullptr, ctx->stream, w0, two ? w1 : nullptr, n0,
-                                  two ? n1 : nullptr, list, count, stp, t, t_slo, zero);
+    const auto generic = [&](const BdxDevCfg &dv, const BdxTierArgs &t, long long blocks, bool last) {
+        // (the call's last launch clears the other scratch half for the next call)
+        return bdx_launch_generic(dv, ctx->plan, b, ho, t, stp, blocks, last ? (uint32_t *)ctx->scratch(true)->tile_queue : nullptr);
     };
 
-    BdxTierArgs t1{1, (uint32_t *)ctx->d_tier.p, front_count, nullptr, nullptr};
-    BdxTierArgs t0{0, nullptr, nullptr, nullptr, nullptr};
+    BdxDevList todo = none;  // the list the next stage walks (none: every read of the batch)
     // 1. front stage
     switch (p.front) {
         case Front::none: break;
-        case Front::bitpar: HIP_TRY(ctx, bitpar(1, &t1)); break;
-        case Front::wave: HIP_TRY(ctx, wave(p.wfront, tiered, false)); break;
-        case Front::wave_win: HIP_TRY(ctx, wave_win(p.wfront, tiered)); break;
-        case Front::wave_split: HIP_TRY(ctx, wave(p.wfront, 0, true)); break;  // (the exact kernel settles and lists)
-        case Front::wave_end: HIP_TRY(ctx, wave_end(p.wfront, tiered)); break;  // verdicts + trimmed keep range of what it settles
-        case Front::pairs: HIP_TRY(ctx, pairs(p.wfront, nullptr, nullptr, true, nullptr)); break;
+        case Front::bitpar: HIP_TRY(ctx, bdx_launch_bitpar(ctx->dev, ctx->plan, p.t1, bdx_seed_plan(f1, p.seed[1]), b, ho, exc, tier1)); break;
+        case Front::wave: HIP_TRY(ctx, wave(p.wfront, false)); break;
+        case Front::wave_win: HIP_TRY(ctx, counted(bdx_launch_wave_win(ctx->dev, p.wfront, he, b, front_out), ctx->wave_launches)); break;
+        case Front::wave_split: HIP_TRY(ctx, wave(p.wfront, true)); break;  // (the exact kernel settles and lists)
+        case Front::wave_end:  // verdicts + trimmed keep range of what it settles
+            HIP_TRY(ctx, counted(bdx_launch_wave_end(ctx->dev, p.wfront, he, b, front_out, p.aln ? stp : nullptr), ctx->wave_launches));
+            break;
+        case Front::pairs: HIP_TRY(ctx, pairs(p.wfront, none, true, nullptr)); break;
     }
     // 2. tier 1's exact launch: it answers what tier 1 settles and lists the rest (known-score / known-end configs: the filter kernel did)
     if (p.t1_exact) {
-        HIP_TRY(ctx, poison_check(nullptr, nullptr, false, true));
-        HIP_TRY(ctx, generic(band_cfg(f1), nullptr, nullptr, &t1, f1.bplan.tier_slo, nullptr));
+        HIP_TRY(ctx, poison_check(none, false, true));
+        HIP_TRY(ctx, generic(band_cfg(f1), tier1, p.t1_exact_blocks, false));
     }
     if (p.front != Front::none) {  // tier 0 / the plain front stage's filter set walks the list
-        t0.in_list = front_list;
-        t0.in_count = front_count;
-        HIP_TRY(ctx, poison_check(t0.in_list, t0.in_count, true, false, p.carry));
+        todo = front;
+        HIP_TRY(ctx, poison_check(todo, true, false, p.carry));
     }
     // 3. middle stage
     switch (p.middle) {
         case Middle::none: break;
-        case Middle::end: HIP_TRY(ctx, pairs(p.wmid, t0.in_list, t0.in_count, false, p.aln ? stp : nullptr)); break;
-        case Middle::list: HIP_TRY(ctx, pairs(p.wmid, t0.in_list, t0.in_count, false, nullptr)); break;
-        case Middle::split: HIP_TRY(ctx, pairs(p.wmid, t0.in_list, t0.in_count, true, nullptr)); break;
-        case Middle::all: HIP_TRY(ctx, pairs(p.wmid, nullptr, nullptr, true, nullptr)); break;
+        case Middle::end: HIP_TRY(ctx, pairs(p.wmid, todo, false, p.aln ? stp : nullptr)); break;
+        case Middle::list: HIP_TRY(ctx, pairs(p.wmid, todo, false, nullptr)); break;
+        case Middle::split: HIP_TRY(ctx, pairs(p.wmid, todo, true, nullptr)); break;
+        case Middle::all: HIP_TRY(ctx, pairs(p.wmid, none, true, nullptr)); break;
     }
     if (p.middle == Middle::end || p.middle == Middle::list) {  // what the pairs mode cannot answer goes on in list mode
-        t0.in_list = mid_list;
-        t0.in_count = mid_count;
-        HIP_TRY(ctx, poison_check(mid_list, mid_count, true, false));
+        todo = mid;
+        HIP_TRY(ctx, poison_check(todo, true, false));
     }
-    // 4. full-budget filter
+    // 4. full-budget filter (in list mode it runs with its own set's thresholds: nothing lies beyond a full budget)
     switch (p.full) {
         case Full::none: break;  // (the pairs mode already wrote the masks and windows)
-        case Full::wave_split: HIP_TRY(ctx, wave(p.wfull, 0, true)); break;
-        case Full::bitpar: HIP_TRY(ctx, bitpar(0, p.front != Front::none ? &t0 : nullptr)); break;
+        case Full::wave_split: HIP_TRY(ctx, wave(p.wfull, true)); break;
+        case Full::bitpar: {
+            const BdxTierArgs listed{todo, none, 0, {p.fused.tier_slo[0], p.fused.tier_slo[1]}};
+            HIP_TRY(ctx, bdx_launch_bitpar(ctx->dev, ctx->plan, p.fused, bdx_seed_plan(f0, p.seed[0]), b, ho, exc, p.front != Front::none ? listed : no_lists));
+            break;
+        }
     }
-    // 5. exact stage (its last launch clears the other scratch half for the next call)
+    // 5. exact stage
     switch (p.exact) {
         case Exact::known:
-            HIP_TRY(ctx, poison_check(exc_list, exc_count, true, false));
-            HIP_TRY(ctx, generic(ctx->dev, exc_list, exc_count, nullptr, nullptr, zero_next));
+            HIP_TRY(ctx, poison_check(exc, true, false));
+            HIP_TRY(ctx, generic(ctx->dev, over(exc, none), p.exact_blocks, true));
             break;
         case Exact::split:
-            HIP_TRY(ctx, poison_check(nullptr, nullptr, false, true));
-            HIP_TRY(ctx, generic(band_cfg(f0), nullptr, nullptr, nullptr, nullptr, zero_next));
+            HIP_TRY(ctx, poison_check(none, false, true));
+            HIP_TRY(ctx, generic(band_cfg(f0), no_lists, p.exact_blocks, true));
             break;
         case Exact::split_list:  // (tiered: list mode over the reads tier 1 handed on)
-            HIP_TRY(ctx, poison_check(t0.in_list, t0.in_count, false, true));
-            HIP_TRY(ctx, generic(band_cfg(f0), t0.in_list, t0.in_count, nullptr, nullptr, zero_next));
+            HIP_TRY(ctx, poison_check(todo, false, true));
+            HIP_TRY(ctx, generic(band_cfg(f0), over(todo, none), p.exact_blocks, true));
             break;
     }
+    const int spar = ctx->scratch_par & 1;
     // (the call's last launch is enqueued: the other half will hold zeros when the next call's kernels start)
     ctx->scratch_clean[1 - spar] = true;
     ctx->scratch_par = 1 - spar;
@@ -730,10 +708,10 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const uint8_t *seq, const lo
     if (ctx->tune.debug & 128) {  // tuning statistics of the fused kernel (see bdx_bitpar.hip)
             unsigned int st[4] = {0, 0, 0, 0}, tl = 0;
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(st, exc_count, sizeof(st), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(&tl, scratch + 192, sizeof(tl), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(st, &scratch->exc_count, sizeof(st), hipMemcpyDeviceToHost));  // (with the three statistics words behind it)
+            HIP_TRY(ctx, hipMemcpy(&tl, &scratch->front_count, sizeof(tl), hipMemcpyDeviceToHost));
             fprintf(stderr, "[bdx] handed over %u reads; %u windowed sweeps, %u columns, %u tiles with a fallback read; tier 0 list %u (of %lld reads)\n",
-                    st[0], st[1], st[2], st[3], tl, (long long)n_reads);
+                    st[0], st[1], st[2], st[3], tl, b.n_reads);
     }
 #endif
     return BDX_OK;
@@ -810,18 +788,17 @@ int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int6
     std::string why;
     int rc = bdx_plan_call(env, args, ctx->seed, p, why);
     if (rc != BDX_OK) return fail(ctx, rc, "%s", why.c_str());
+    const BdxBatch batch{d_seq_bytes, (const long long *)d_seq_off, n_reads, o, ctx->counts, ctx->stream};
     if (p.filtered) {
         rc = reserve(ctx, p, n_reads);
-        if (rc == BDX_OK) rc = enqueue(ctx, p, d_seq_bytes, (const long long *)d_seq_off, n_reads, o, stp);
+        if (rc == BDX_OK) rc = enqueue(ctx, p, batch, stp);
         if (rc != BDX_OK) return rc;
         ctx->last_blocks = (n_reads + p.fused.reads_per_block - 1) / p.fused.reads_per_block;
         ctx->path = p.path;
         ctx->filter_used = bdx_seed_plan(ctx->fs[0], p.seed[0]).enabled ? BDX_FILTER_QGRAM : BDX_FILTER_BITPAR;
     } else {
-        HIP_TRY(ctx, bdx_launch_generic(ctx->dev, ctx->plan, d_seq_bytes, (const long long *)d_seq_off, n_reads, o,
-                                        ctx->counts, nullptr, nullptr, ctx->stream, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                        nullptr, stp));
-        ctx->last_blocks = (n_reads + ctx->plan.threads - 1) / ctx->plan.threads;
+        HIP_TRY(ctx, bdx_launch_generic(ctx->dev, ctx->plan, batch, BdxHandOver{}, BdxTierArgs{}, stp, p.exact_blocks, nullptr));
+        ctx->last_blocks = p.exact_blocks;
         ctx->path = "generic";
         ctx->filter_used = BDX_FILTER_OFF;
     }
@@ -923,8 +900,7 @@ int64_t bdx_last_list_reads(bdx_ctx *ctx) {
     if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return -1;
     unsigned int v = 0;
     // (the scratch half of the LAST call: the halves alternate, the last launch of a call clears the other one)
-    const char *last = (const char *)ctx->d_maxlen.p + 512 * (1 - (ctx->scratch_par & 1)) + 192;
-    if (hipMemcpy(&v, last, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(&v, &ctx->scratch(true)->front_count, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return (int64_t)v;
 }
 

@@ -1206,7 +1206,7 @@ __global__ __launch_bounds__(BS, 4) void bdx_bitpar_kernel(const BitparArgs a) {
 }
 
 template <int BS, int R, bool SEED, bool DIAG = false, int NW = 5, int WL = 0>
-hipError_t launch_one(const BitparArgs &a, size_t lds, long long n_reads, hipStream_t stream, long long grid_override, int n_cu) {
+hipError_t launch_one(const BitparArgs &a, size_t lds, long long blocks, hipStream_t stream) {
     // the attribute is per device: one flag per device of this process.  Contexts of several OS threads may
     // launch concurrently: setting the attribute twice is harmless, the flag itself must not be a data race.
     static std::atomic<bool> attr_set[64];
@@ -1218,56 +1218,35 @@ hipError_t launch_one(const BitparArgs &a, size_t lds, long long n_reads, hipStr
         if (e != hipSuccess) return e;
         if (dev >= 0) attr_set[dev].store(true, std::memory_order_release);
     }
-    // persistent grid: enough workgroups to fill every CU at the LDS-limited residency,
-    // never more than there are tiles
-    const long long tiles = (n_reads + R - 1) / R;
-    long long per_cu = bdx_lds_residency(lds);
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu > 8) per_cu = 8;
-    long long blocks = (long long)(n_cu > 0 ? n_cu : 256) * per_cu;  // exactly the resident set; the tile queue balances it
-    if (grid_override > 0) blocks = grid_override;
-    if (blocks > tiles) blocks = tiles;
-    if (blocks < 1) blocks = 1;
+    // (a persistent grid: the tile queue balances it)
     hipLaunchKernelGGL((bdx_bitpar_kernel<BS, R, SEED, DIAG, NW, WL>), dim3((unsigned)blocks), dim3(BS), lds, stream, a);
     if (bdx_launch_logging()) {
         char name[96];
         snprintf(name, sizeof name, "bdx_bitpar_kernel<%d, %d, %s, %s, %d, %d>", BS, R, SEED ? "true" : "false", DIAG ? "true" : "false", NW, WL);
-        bdx_note_launch("bitpar", name, blocks, BS, R, blocks, n_reads, a.in_list != nullptr ? 1 : 0);
+        bdx_note_launch("bitpar", name, blocks, BS, R, blocks, a.n_reads, a.in_list != nullptr ? 1 : 0);
     }
     return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t bdx_launch_bitpar(const BdxDevCfg &cfg, const BdxGenericPlan &gp, const BdxBitparPlan &bp,
-                             const BdxSeedPlan &sp, const uint8_t *d_seq, const long long *d_off, long long n_reads, const BdxDevOut &out,
-                             unsigned long long *d_counts, uint32_t *cand_out0, uint32_t *cand_out1,
-                             hipStream_t stream, uint32_t *wins_out0, uint32_t *wins_out1, uint8_t *wcnt_out0,
-                             uint8_t *wcnt_out1, int split, uint32_t *exc_list, unsigned int *exc_count,
-                             const BdxTierArgs *tier) {
-    if (n_reads <= 0) return hipSuccess;
+hipError_t bdx_launch_bitpar(const BdxDevCfg &cfg, const BdxGenericPlan &gp, const BdxBitparPlan &bp, const BdxSeedPlan &sp, const BdxBatch &b,
+                             const BdxHandOver &ho, const BdxDevList &exc, const BdxTierArgs &t) {
+    if (b.n_reads <= 0) return hipSuccess;
     BitparArgs a;
-    a.tier = 0;
-    a.tier_slo[0] = a.tier_slo[1] = 0.0;
-    a.tier_list = nullptr;
-    a.tier_count = nullptr;
-    a.in_list = nullptr;
-    a.in_count = nullptr;
-    if (tier) {
-        a.tier = tier->tier1;
-        a.tier_slo[0] = bp.tier_slo[0];
-        a.tier_slo[1] = bp.tier_slo[1];
-        a.tier_list = tier->out_list;
-        a.tier_count = tier->out_count;
-        a.in_list = tier->in_list;
-        a.in_count = tier->in_count;
-    }
+    a.tier = t.tier1;
+    a.tier_slo[0] = t.slo[0];
+    a.tier_slo[1] = t.slo[1];
+    a.tier_list = t.out.ids;
+    a.tier_count = t.out.count;
+    a.in_list = t.in.ids;
+    a.in_count = t.in.count;
     a.cfg = cfg;
-    a.seq = d_seq;
-    a.off = d_off;
-    a.n_reads = n_reads;
-    a.out = out;
-    a.counts = d_counts;
+    a.seq = b.seq;
+    a.off = b.off;
+    a.n_reads = b.n_reads;
+    a.out = b.out;
+    a.counts = b.counts;
     a.stage_bytes = bp.stage_bytes;
     a.hist_entries = gp.hist_entries;
     a.lut = bp.d_lut;
@@ -1288,15 +1267,14 @@ hipError_t bdx_launch_bitpar(const BdxDevCfg &cfg, const BdxGenericPlan &gp, con
     a.short_lb[0] = bp.short_lb[0];
     a.short_lb[1] = bp.short_lb[1];
     a.ncode = bp.ncode_N;
-    a.split = split;
-    a.exc_list = exc_list;
-    a.exc_count = exc_count;
-    a.cand_out[0] = cand_out0;
-    a.cand_out[1] = cand_out1;
-    a.wins_out[0] = wins_out0;
-    a.wins_out[1] = wins_out1;
-    a.wcnt_out[0] = wcnt_out0;
-    a.wcnt_out[1] = wcnt_out1;
+    a.split = exc.ids == nullptr ? 1 : 0;
+    a.exc_list = exc.ids;
+    a.exc_count = exc.count;
+    for (int k = 0; k < 2; ++k) {
+        a.cand_out[k] = ho.cand[k];
+        a.wins_out[k] = ho.wins[k];
+        a.wcnt_out[k] = ho.wcnt[k];
+    }
     a.tile_counter = bp.d_tile_counter;
     a.known_ok[0] = bp.known_ok[0];
     a.known_ok[1] = bp.known_ok[1];
@@ -1321,10 +1299,9 @@ hipError_t bdx_launch_bitpar(const BdxDevCfg &cfg, const BdxGenericPlan &gp, con
         a.seed_n_always[k] = sp.n_always[k];
         a.seed_always[k] = sp.d_always[k];
     }
-    const size_t lds = bdx_bitpar_lds_bytes(cfg, bp, gp, &sp);
     const bool seed = sp.enabled != 0;
     if (seed && sp.diag) {
-#define BDX_LAUNCH_D(RR) return bp.diag_nw > 5 ? launch_one<256, RR, true, true, 10>(a, lds, n_reads, stream, bp.grid_override, bp.n_cu) : launch_one<256, RR, true, true, 5>(a, lds, n_reads, stream, bp.grid_override, bp.n_cu)
+#define BDX_LAUNCH_D(RR) return bp.diag_nw > 5 ? launch_one<256, RR, true, true, 10>(a, bp.lds_bytes, bp.grid, b.stream) : launch_one<256, RR, true, true, 5>(a, bp.lds_bytes, bp.grid, b.stream)
         switch (bp.reads_per_block) {
             case 32:
                 BDX_LAUNCH_D(32);
@@ -1340,13 +1317,13 @@ hipError_t bdx_launch_bitpar(const BdxDevCfg &cfg, const BdxGenericPlan &gp, con
 #undef BDX_LAUNCH_D
     }
 #define BDX_LAUNCH_R(RR)                                                                                                  \
-    return bp.word_bytes == 8 ? (seed ? launch_one<256, RR, true, false, 5, 1>(a, lds, n_reads, stream, bp.grid_override, bp.n_cu)    \
-                                      : launch_one<256, RR, false, false, 5, 1>(a, lds, n_reads, stream, bp.grid_override, bp.n_cu)) \
-                              : (seed ? launch_one<256, RR, true>(a, lds, n_reads, stream, bp.grid_override, bp.n_cu)                    \
-                                      : launch_one<256, RR, false>(a, lds, n_reads, stream, bp.grid_override, bp.n_cu))
+    return bp.word_bytes == 8 ? (seed ? launch_one<256, RR, true, false, 5, 1>(a, bp.lds_bytes, bp.grid, b.stream)    \
+                                      : launch_one<256, RR, false, false, 5, 1>(a, bp.lds_bytes, bp.grid, b.stream)) \
+                              : (seed ? launch_one<256, RR, true>(a, bp.lds_bytes, bp.grid, b.stream)                    \
+                                      : launch_one<256, RR, false>(a, bp.lds_bytes, bp.grid, b.stream))
 #define BDX_LAUNCH_Q(RR)                                                                                                  \
-    return seed ? launch_one<256, RR, true, false, 5, 2>(a, lds, n_reads, stream, bp.grid_override, bp.n_cu)                \
-                : launch_one<256, RR, false, false, 5, 2>(a, lds, n_reads, stream, bp.grid_override, bp.n_cu)
+    return seed ? launch_one<256, RR, true, false, 5, 2>(a, bp.lds_bytes, bp.grid, b.stream)                \
+                : launch_one<256, RR, false, false, 5, 2>(a, bp.lds_bytes, bp.grid, b.stream)
     if (bp.word_bytes == 16) {  // barcodes of 65..128 nt: tiles of 64 / 32 / 16 reads (size_bitpar)
         switch (bp.reads_per_block) {
             case 64:

@@ -262,6 +262,34 @@ bool size_bitpar(const Batch &b, int set, BdxSeedChoice &choice, int read_len, l
     }
 }
 
+// ---- the grid and LDS bytes of a launch ----
+// Fused kernel, a persistent grid: enough workgroups to fill every compute unit at the LDS-limited residency (the tile queue
+// balances it), or what BDX_GRID forces; never more than there are tiles.
+void grid_bitpar(const BdxCallEnv &env, const BdxSeedPlan &sp, long long n_reads, BdxBitparPlan &bp) {
+    bp.lds_bytes = bdx_bitpar_lds_bytes(env.dev, bp, env.plan, &sp);
+    const long long tiles = (n_reads + bp.reads_per_block - 1) / bp.reads_per_block;
+    const long long per_cu = std::min(std::max(bdx_lds_residency(bp.lds_bytes), 1), 8);
+    const long long blocks = env.tune.grid > 0 ? env.tune.grid : (long long)(env.n_cu > 0 ? env.n_cu : 256) * per_cu;
+    bp.grid = std::max(std::min(blocks, tiles), 1LL);
+}
+
+// Wave kernel over contiguous tiles: the plan's workgroups, but no more than give every wave one tile; the pairs mode (its
+// reads are a list of unknown length): the plan's.  At least one.
+void grid_wave(const BdxCallEnv &env, long long n_reads, BdxWavePlan &wp) {
+    wp.lds_bytes = bdx_wave_table_bytes(wp, env.plan.hist_entries) + (size_t)wp.waves * bdx_wave_area_bytes(wp);
+    const long long tiles = (n_reads + wp.rw - 1) / wp.rw, useful = (tiles + wp.waves - 1) / wp.waves;
+    wp.grid = std::max(wp.pairs_kb > 0 ? (long long)wp.blocks : std::min<long long>(wp.blocks, useful), 1LL);
+}
+
+// Generic kernel: a thread per read; over a list the grid strides, four workgroups per compute unit.  false: more workgroups
+// than a grid holds.
+bool grid_generic(const BdxGenericPlan &gp, long long n_reads, bool list, long long &blocks) {
+    blocks = (n_reads + gp.threads - 1) / gp.threads;
+    if (blocks > 0x7FFFFFFFLL) return false;
+    if (list) blocks = std::min(blocks, 4LL * (gp.n_cu > 0 ? gp.n_cu : 256));
+    return true;
+}
+
 // the stages of a filtered call, front first
 std::string call_path(const BdxSeedPlan &sp, const CallPlan &p) {
     std::string s = sp.enabled ? (sp.diag ? "qgram2+bitpar+verify" : "qgram+bitpar+verify") : "bitpar+verify";
@@ -335,8 +363,9 @@ int bdx_plan_call(const BdxCallEnv &env, const BdxCallArgs &args, BdxSeedChoice 
         err = msg;
         return code;
     };
+    const char *const too_many = "more reads than one launch of the exact kernel takes";
     p.filtered = size_bitpar(b, 0, seed[0], len, n_reads, false, p.fused);
-    if (!p.filtered) return BDX_OK;
+    if (!p.filtered) return grid_generic(env.plan, n_reads, false, p.exact_blocks) ? BDX_OK : fail(BDX_E_DEVICE, too_many);
     // both tiers must be plannable for this batch, else the full budget alone (a batch of empty reads is never tiered)
     const bool tiered = env.choice.tiered && size_bitpar(b, 1, seed[1], len, n_reads, false, p.t1) && args.read_len > 0;
     if (n_reads > 0xFFFFFFF0LL) return fail(BDX_E_INVALID, "more than 2^32 reads in one batch");
@@ -454,7 +483,20 @@ int bdx_plan_call(const BdxCallEnv &env, const BdxCallArgs &args, BdxSeedChoice 
     p.seed[0] = seed[0];
     p.seed[1] = seed[1];
     const BdxSeedPlan sp = bdx_seed_plan(f0, seed[0]);
-    p.lds_bytes = bdx_bitpar_lds_bytes(dev, p.fused, env.plan, &sp);
+    // every launch's grid and LDS bytes; the developer switches' word as the wave kernels read it
+    grid_bitpar(env, sp, n_reads, p.fused);
+    p.lds_bytes = p.fused.lds_bytes;
+    if (p.front == Front::bitpar) grid_bitpar(env, bdx_seed_plan(f1, seed[1]), n_reads, p.t1);
+    const auto wave_launch = [&](bool launched, BdxWavePlan &wp) {
+        if (!launched) return;
+        grid_wave(env, n_reads, wp);
+        wp.dbg = wp.pairs_kb > 0 ? env.tune.debug >> 8 : env.tune.debug;
+    };
+    wave_launch(p.front != Front::none && p.front != Front::bitpar, p.wfront);
+    wave_launch(p.middle != Middle::none, p.wmid);
+    wave_launch(p.full == Full::wave_split, p.wfull);
+    if (!grid_generic(env.plan, n_reads, false, p.t1_exact_blocks) || !grid_generic(env.plan, n_reads, p.exact != Exact::split, p.exact_blocks))
+        return fail(BDX_E_DEVICE, too_many);
     p.path = call_path(sp, p);
     return BDX_OK;
 }

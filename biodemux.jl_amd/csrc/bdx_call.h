@@ -1,6 +1,7 @@
 // bdx_call.h — the per-call planner (bdx_call.cpp): which kernels one batch runs on and with which tile, queue and LDS
-// geometry.  Host-only like bdx_plan.cpp: no HIP runtime call, no device buffer, no context.  bdx_classify_device
-// (bdx_abi.cpp) runs it once per call and launches from the CallPlan it returns; tests/call_host.cpp runs it on a CPU.
+// geometry, and the grid and LDS bytes of every launch (the launchers decide neither).  Host-only like bdx_plan.cpp: no HIP
+// runtime call, no device buffer, no context.  bdx_classify_device (bdx_abi.cpp) runs it once per call and launches from
+// the CallPlan it returns; tests/call_host.cpp runs it on a CPU.
 #pragma once
 #include <string>
 
@@ -54,7 +55,7 @@ inline BdxSeedPlan bdx_seed_plan(const BdxSetPlans &f, BdxSeedChoice c) {
 }
 
 struct CallPlan {
-    bool filtered = false;  // false: the generic kernel alone (nothing else below is set)
+    bool filtered = false;  // false: the generic kernel alone (of what is below only exact_blocks is set)
     int npass = 1, tier_len = 0, batch_len = 0;  // tier_len > 0: tiered; batch_len: the read length the launches were planned for
     bool split = false, windows = false, dense_w = false;
     int short_lb[2] = {0, 0};
@@ -64,11 +65,13 @@ struct CallPlan {
     Full full = Full::bitpar;
     Exact exact = Exact::known;
     bool carry = false, aln = false;  // carried passes (d_carry); the known-end forms run as the known-alignment class
-    // sized copies of the plans the stages launch; reserve (bdx_abi.cpp) adds the per-launch device pointers
+    // sized copies of the plans the stages launch, each with its launch's grid and LDS bytes (BDX_GRID applied); reserve
+    // (bdx_abi.cpp) adds the per-launch device pointers
     BdxWavePlan wfront{}, wmid{}, wfull{};  // the wave-kernel front stage, the pairs mode, the wave kernel as the full-budget filter
     BdxBitparPlan t1{}, fused{};            // the fused kernel: tier 1 over the batch; at the full budgets (dense, or over the list)
     BdxSeedChoice seed[2] = {BDX_SEED_MAIN, BDX_SEED_MAIN};  // the seed plans t1 (seed[1]) and fused (seed[0]) were sized with
-    size_t lds_bytes = 0;  // LDS of a `fused` workgroup
+    long long t1_exact_blocks = 0, exact_blocks = 0;  // grids of the generic kernel: tier 1's exact launch, the exact stage
+    size_t lds_bytes = 0;  // LDS of a `fused` workgroup (fused.lds_bytes: what bdx_launch_info reports)
     std::string path;      // the stages, front first (bdx_kernel_path)
 };
 

@@ -70,7 +70,7 @@ struct bdx_ctx : BdxPlanChoice {  // (tiered, tier_q, tier_cap_fixed, pairs_tier
     BdxSeedChoice seed[2] = {BDX_SEED_MAIN, BDX_SEED_MAIN};  // per set: the seed plan in effect — the planning state that outlives a call
     CallPlan last;           // the last classify call's plan (bdx_launch_info reports from it)
     BdxTuning tune{};
-    DevBuf d_maxlen;
+    DevBuf d_maxlen;    // the scratch block: two BdxScratch halves (word 0: bdx_launch_maxlen's result)
     DevBuf d_tier;      // tiered budgets: reads handed from tier 1 to tier 0
     DevBuf d_carry;     // dual tiered known-class configs: the winning survivor of the pass tier 1 settled, per listed read (BdxWavePlan::d_carry)
     int user_len_hint = 0;  // 0 = measure every device batch
@@ -98,6 +98,8 @@ struct bdx_ctx : BdxPlanChoice {  // (tiered, tier_q, tier_cap_fixed, pairs_tier
     int scratch_par = 0;             // which half of the scratch block the next classify call uses
     bool scratch_clean[2] = {false, false};  // that half is known to hold zeros (cleared by the previous call's last launch)
     bool scratch_zeroed = false;  // the small-batch copy kernel has already cleared the filter kernels' scratch words
+    // the half the next classify call uses (while it runs: this call's) / other: the half the last call used, which this call's last launch clears
+    BdxScratch *scratch(bool other = false) const { return (BdxScratch *)d_maxlen.p + ((scratch_par & 1) ^ (other ? 1 : 0)); }
     int host_maxlen = 0;     // > 0 while bdx_classify_host runs an ordinary batch: its longest read (seen on the host)
     PinnedBuf h_stage;  // page-locked staging for the verdict vectors of small batches
     PinnedBuf h_in;     // page-locked staging for the bytes + offsets of small batches

@@ -375,13 +375,14 @@ __global__ void bdx_poison_check_kernel(uint32_t *list, const unsigned int *list
 }
 }  // namespace
 
-hipError_t bdx_launch_poison_check(uint32_t *list, const unsigned int *list_count, long long n_reads, const uint32_t *wins, uint8_t *wcnt,
-                                   const uint32_t *cand, int cand_words, int n_barcodes, int check_list, unsigned int *dbg, hipStream_t stream) {
-    if (n_reads <= 0 || !dbg) return hipSuccess;
-    long long blocks = (n_reads + 255) / 256;
+hipError_t bdx_launch_poison_check(const BdxBatch &b, const BdxDevList &list, const BdxHandOver &ho, int pass, int n_barcodes, int check_list, unsigned int *dbg) {
+    if (b.n_reads <= 0 || !dbg) return hipSuccess;
+    long long blocks = (b.n_reads + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(bdx_poison_check_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, list, list_count, n_reads, wins, wcnt, cand, cand_words,
-                       n_barcodes, check_list, dbg);
+    const bool w = pass >= 0;
+    hipLaunchKernelGGL(bdx_poison_check_kernel, dim3((unsigned)blocks), dim3(256), 0, b.stream, list.ids, (const unsigned int *)list.count, b.n_reads,
+                       w ? (const uint32_t *)ho.wins[pass] : nullptr, w ? ho.wcnt[pass] : nullptr, w ? (const uint32_t *)ho.cand[pass] : nullptr,
+                       w ? ho.cand_words[pass] : 0, n_barcodes, check_list, dbg);
     return hipGetLastError();
 }
 
@@ -438,48 +439,41 @@ static void launch_generic_one(dim3 grid, dim3 block, size_t lds, hipStream_t st
     }
 }
 
-hipError_t bdx_launch_generic(const BdxDevCfg &cfg, const BdxGenericPlan &plan, const uint8_t *d_seq,
-                              const long long *d_off, long long n_reads, const BdxDevOut &out,
-                              unsigned long long *d_counts, const uint32_t *d_cand0, const uint32_t *d_cand1,
-                              hipStream_t stream, const uint32_t *d_wins0, const uint32_t *d_wins1,
-                              const uint8_t *d_wcnt0, const uint8_t *d_wcnt1, const uint32_t *d_list,
-                              const unsigned int *d_list_count, const BdxDevStats *stats, const BdxTierArgs *tier,
-                              const double *tier_slo, uint32_t *zero_words) {
-    if (n_reads <= 0) return hipSuccess;
+hipError_t bdx_launch_generic(const BdxDevCfg &cfg, const BdxGenericPlan &plan, const BdxBatch &b, const BdxHandOver &ho, const BdxTierArgs &t,
+                              const BdxDevStats *stats, long long blocks, uint32_t *zero_words) {
+    if (b.n_reads <= 0) return hipSuccess;
+    const bool two = ho.cand_words[1] > 0;  // (a single-pass hand-over names pass 0's buffers twice: this kernel wants none)
+    const hipStream_t stream = b.stream;
     GenericArgs a;
     a.zero_words = zero_words;
     a.cfg = cfg;
-    a.seq = d_seq;
-    a.off = d_off;
-    a.n_reads = n_reads;
-    a.out = out;
-    a.counts = d_counts;
-    a.cand0 = d_cand0;
-    a.cand1 = d_cand1;
-    a.wins[0] = d_wins0;
-    a.wins[1] = d_wins1;
-    a.wcnt[0] = d_wcnt0;
-    a.wcnt[1] = d_wcnt1;
-    a.list = d_list;
-    a.list_count = d_list_count;
+    a.seq = b.seq;
+    a.off = b.off;
+    a.n_reads = b.n_reads;
+    a.out = b.out;
+    a.counts = b.counts;
+    a.cand0 = ho.cand[0];
+    a.cand1 = two ? ho.cand[1] : nullptr;
+    a.wins[0] = ho.wins[0];
+    a.wins[1] = two ? ho.wins[1] : nullptr;
+    a.wcnt[0] = ho.wcnt[0];
+    a.wcnt[1] = two ? ho.wcnt[1] : nullptr;
+    a.list = t.in.ids;
+    a.list_count = t.in.count;
     if (stats)
         a.stats = *stats;
     else
         a.stats = BdxDevStats{};
-    a.tier1 = tier && tier->tier1 ? 1 : 0;
-    a.tier_slo[0] = tier_slo ? tier_slo[0] : 0.0;
-    a.tier_slo[1] = tier_slo ? tier_slo[1] : 0.0;
-    a.tier_list = tier ? tier->out_list : nullptr;
-    a.tier_count = tier ? tier->out_count : nullptr;
-    a.cfg.end_only_ok = out.pass_start == nullptr ? 1 : 0;
+    a.tier1 = t.tier1 ? 1 : 0;
+    a.tier_slo[0] = t.slo[0];
+    a.tier_slo[1] = t.slo[1];
+    a.tier_list = t.out.ids;
+    a.tier_count = t.out.count;
+    a.cfg.end_only_ok = b.out.pass_start == nullptr ? 1 : 0;
     a.dp_rows = plan.dp_rows;
     a.stage_bytes = plan.stage_bytes;
     a.bc_stage_bytes = plan.bc_stage_bytes;
     a.hist_entries = plan.hist_entries;
-    long long blocks = (n_reads + plan.threads - 1) / plan.threads;
-    if (blocks > 0x7FFFFFFFLL) return hipErrorInvalidValue;
-    const long long list_grid = 4LL * (plan.n_cu > 0 ? plan.n_cu : 256);
-    if (d_list && blocks > list_grid) blocks = list_grid;  // list mode: the hand-overs are few; the grid strides
     const dim3 grid((unsigned)blocks), block((unsigned)plan.threads);
     if (plan.reg_rows == 24 && plan.threads == 256 && plan.clean) {
         if (plan.uniform_m)

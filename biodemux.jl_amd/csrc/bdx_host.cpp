@@ -401,7 +401,7 @@ int32_t bdx_classify_host(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t 
         void *h_in_dev = nullptr;  // the staging buffer as the device sees it
         HIP_TRY(ctx, hipHostGetDevicePointer(&h_in_dev, ctx->h_in.p, 0));
         const bool zero_scratch = ctx->d_maxlen.p != nullptr;  // (allocated at bdx_create when a filter is in use)
-        HIP_TRY(ctx, bdx_launch_copy(ctx->d_seq.p, h_in_dev, bytes, ctx->stream, zero_scratch ? (char *)ctx->d_maxlen.p + 512 * (ctx->scratch_par & 1) + 64 : nullptr, 4 * BDX_SCRATCH_WORDS));
+        HIP_TRY(ctx, bdx_launch_copy(ctx->d_seq.p, h_in_dev, bytes, ctx->stream, zero_scratch ? ctx->scratch()->tile_queue : nullptr, 4 * BDX_SCRATCH_WORDS));
         ctx->scratch_zeroed = zero_scratch;
         const int rcs = run_and_download(ctx, (const uint8_t *)ctx->d_seq.p - base, (const int64_t *)((const char *)ctx->d_seq.p + o_off),
                                          n_reads, out, /*mapped_outputs=*/true);

@@ -1,9 +1,13 @@
 // bdx_internal.h — structures shared between the host side (the create-time planner bdx_plan.cpp, the per-call planner
 // bdx_call.cpp, the C-ABI translation unit bdx_abi.cpp) and the gfx950 kernels (bdx_device.hip).  Not part of the public ABI.
+// The seam between bdx_abi.cpp's enqueue and the classify launchers is at the end: what one call hands every launcher
+// (BdxBatch, BdxHandOver, BdxDevList / BdxTierArgs), the launchers, and the layout of the call's scratch words (BdxScratch).
+// A launcher decides no grid and no LDS size: both stand in the sized plan it is given (bdx_call.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/biodemux_hip.h"
@@ -189,7 +193,7 @@ struct BdxBitparPlan {
     int seed_span;         // bases per read the seed scan covers (read length, or the window in slot mode)
     int ncode_N;           // symbol code of 'N' (255 if no barcode contains it)
     int ncodes;            // symbol codes incl. the trailing "other" code (<= 16)
-    long long grid_override;  // > 0: forced persistent grid (tuning, BdxTuning::grid)
+    long long grid_override;  // (unused: BdxTuning::grid is applied where the grid is decided, bdx_call.cpp)
     int n_cu;              // compute units of the device: the persistent grid is n_cu x the LDS-limited residency
     int short_lb[2];       // per launch and pass: short lookback of the restricted runs (score / end-only clean-class passes)
     int dbg;               // BdxTuning::debug (only builds with -DBDX_TUNING look at it)
@@ -204,6 +208,8 @@ struct BdxBitparPlan {
     const void *d_peq[2];          // device, [ncodes][bpad] sweep words
     const void *d_pvinit[2];       // device, [B]: top-aligned mask of the barcode's rows
     const int32_t *d_kb[2];        // device, [B]: max unit edit operations of a recordable alignment
+    long long grid;                // per launch (bdx_call.cpp): workgroups
+    size_t lds_bytes;              //   ... and LDS bytes of each
 };
 
 // q-gram seeding in front of the sweep (pigeonhole): tables built in bdx_plan.cpp.
@@ -273,16 +279,48 @@ struct BdxWavePlan {
     int groups;            // groups of 128 barcodes (more than 128 barcodes: one set of piece tables per group, nw = 4)
     int slot;              // pairs mode: flat positions per read of a (scattered) tile: the read length + 15 (its address mod 16), rounded up to 16
     int cpr;               // 16-diagonal chunks scanned per read
+    // per launch (bdx_call.cpp)
+    long long grid;        // workgroups: `blocks`, but no more than give every wave a tile
+    size_t lds_bytes;      // the tables + one work area per wave
+    int dbg;               // BdxTuning::debug as this kernel reads it (the pairs mode: shifted down by eight bits)
 };
 
-// Tiered budgets: tier 1 (tier1 = 1) appends the reads it cannot settle to out_list / *out_count; tier 0 then
-// runs over in_list[0 .. *in_count) only (list mode).
+// ---- what one classify call hands its launchers ----
+// The batch: one per bdx_classify_device call.  A launch that must not count (a filter in split form) gets uncounted().
+struct BdxBatch {
+    const uint8_t *seq;
+    const long long *off;
+    long long n_reads;
+    BdxDevOut out;
+    unsigned long long *counts;
+    hipStream_t stream;
+    BdxBatch uncounted() const { return BdxBatch{seq, off, n_reads, out, nullptr, stream}; }
+};
+
+// The split-mode hand-over from a filter (fused kernel, wave kernel, pairs mode) to the exact kernel, per pass: candidate
+// masks [read][cand_words], column windows with their entry counts (null: the call runs without windows), and whether the
+// restricted runs take the short lookback.  A single-pass call has cand_words[1] = 0 and pass 0's buffers in both places.
+// A launch that is no part of a hand-over gets an empty one (BdxHandOver{}).
+struct BdxHandOver {
+    int cand_words[2];
+    uint32_t *cand[2];
+    uint32_t *wins[2];
+    uint8_t *wcnt[2];
+    int short_lb[2];
+};
+
+// A list of read numbers on the device with its length.  ids == nullptr: no list (an input: every read of the batch).
+struct BdxDevList {
+    uint32_t *ids;
+    unsigned int *count;
+};
+
+// The lists of a launch: it runs over in.ids[0 .. *in.count) (list mode) and appends the reads it cannot settle to out.
+// tier1: the launch is tier 1 of the tiered budgets; slo: per pass the smallest score a barcode beyond its capped budget can have.
 struct BdxTierArgs {
+    BdxDevList in, out;
     int tier1;
-    uint32_t *out_list;
-    unsigned int *out_count;
-    const uint32_t *in_list;
-    const unsigned int *in_count;
+    double slo[2];
 };
 
 // index sub-batch of the fused kernel's diagonal variant at the narrow index width (bdx_bitpar.hip)
@@ -292,24 +330,13 @@ struct BdxTierArgs {
 // LDS bytes of a workgroup of the fused kernel (bdx_call.cpp; mirrors the carve-up at the head of bdx_bitpar_kernel)
 size_t bdx_bitpar_lds_bytes(const BdxDevCfg &cfg, const BdxBitparPlan &bp, const BdxGenericPlan &gp,
                             const BdxSeedPlan *sp = nullptr);
-// Implemented in bdx_bitpar.hip.
-hipError_t bdx_launch_bitpar(const BdxDevCfg &cfg, const BdxGenericPlan &gp, const BdxBitparPlan &bp,
-                             const BdxSeedPlan &sp, const uint8_t *d_seq, const long long *d_off, long long n_reads, const BdxDevOut &out,
-                             unsigned long long *d_counts, uint32_t *cand_out0, uint32_t *cand_out1, hipStream_t stream,
-                             uint32_t *wins_out0, uint32_t *wins_out1, uint8_t *wcnt_out0, uint8_t *wcnt_out1, int split,
-                             uint32_t *exc_list, unsigned int *exc_count, const BdxTierArgs *tier = nullptr);
+// Implemented in bdx_bitpar.hip.  exc: the known-score form lists the reads it hands to the exact kernel after all
+// (no list: split form — masks and windows of every read into `ho`, no verdicts).
+hipError_t bdx_launch_bitpar(const BdxDevCfg &cfg, const BdxGenericPlan &gp, const BdxBitparPlan &bp, const BdxSeedPlan &sp, const BdxBatch &b,
+                             const BdxHandOver &ho, const BdxDevList &exc, const BdxTierArgs &t);
 // max read length of a device-resident batch (one tiny kernel; result written to *d_out)
 hipError_t bdx_launch_maxlen(const long long *d_off, long long n_reads, int *d_out, hipStream_t stream);
 hipError_t bdx_launch_copy(void *d_dst, const void *src_mapped, size_t bytes, hipStream_t stream, void *d_zero = nullptr, int zero_bytes = 0);
-
-// split-mode outputs of the wave kernel (same buffers and formats as bdx_bitpar.hip's split mode)
-struct BdxWaveSplit {
-    int cw[2];
-    uint32_t *cand_out[2];
-    uint32_t *wins_out[2];
-    uint8_t *wcnt_out[2];
-    int short_lb[2];
-};
 
 // The wave-autonomous kernel (bdx_wave_kernel.h) is compiled in six translation units, one set of instantiations each.
 // Implemented in bdx_wave.hip (the known-score and plain split-mode instantiations: whole ranges, one pass).
@@ -328,46 +355,55 @@ inline size_t bdx_wave_area_bytes(int rw, int span_cap, bool pairs, int hq_cap, 
     const size_t o = fixed + ((nvec + 2 + 3) & ~(size_t)3) * 4 + ((2 * nvec + 6 + 3) & ~(size_t)3) * 4 + ((size_t)hq_cap + (pairs ? 0 : (size_t)sq_cap) + (size_t)rw * (size_t)cand_words) * 4;
     return (o + 31) & ~(size_t)31;
 }
-hipError_t bdx_launch_wave(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
-                           long long n_reads, const BdxDevOut &out, unsigned long long *d_counts, int tier1, double tier_slo, uint32_t *list,
-                           unsigned int *list_count, hipStream_t stream, int dbg = 0, const BdxWaveSplit *sp = nullptr, double tier_slo1 = 0.0);
+// ... of the plan `wp` (window mode keeps no candidate words)
+inline size_t bdx_wave_area_bytes(const BdxWavePlan &wp) {
+    return wp.winm ? bdx_wave_area_bytes(wp.rw, wp.span_cap, false, wp.hq_cap, wp.sq_cap, 0, true)
+                   : bdx_wave_area_bytes(wp.rw, wp.span_cap, wp.pairs_kb > 0, wp.hq_cap, wp.sq_cap, wp.cand_words + (wp.ranged ? 4 : 0));
+}
+// (ho: the split form's outputs, else empty; t.out: the reads the kernel does not answer)
+hipError_t bdx_launch_wave(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const BdxBatch &b, const BdxHandOver &ho, const BdxTierArgs &t);
 // Implemented in bdx_wave_end.hip (the known-end class: its forward-sweep instantiations are there, the reversed ones in
-// bdx_wave_rev.hip, the known-alignment ones in bdx_wave_aln.hip).
-hipError_t bdx_launch_wave_end(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
-                               long long n_reads, const BdxDevOut &out, unsigned long long *d_counts, int tier1, double tier_slo, uint32_t *list,
-                               unsigned int *list_count, hipStream_t stream, int dbg = 0, double tier_slo1 = 0.0,
-                               const BdxDevStats *stats = nullptr);  // (stats / pass_start: the known-alignment class only, kend = 3)
+// bdx_wave_rev.hip, the known-alignment ones in bdx_wave_aln.hip).  (stats / pass_start: the known-alignment class only, kend = 3)
+hipError_t bdx_launch_wave_end(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const BdxBatch &b, const BdxTierArgs &t, const BdxDevStats *stats);
 // Implemented in bdx_wave_win.hip (the window-mode instantiations: single-pass known-score configs whose column window is much
 // shorter than their reads — only the windows are fetched).
-hipError_t bdx_launch_wave_win(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
-                               long long n_reads, const BdxDevOut &out, unsigned long long *d_counts, int tier1, double tier_slo, uint32_t *list,
-                               unsigned int *list_count, hipStream_t stream, int dbg = 0);
+hipError_t bdx_launch_wave_win(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const BdxBatch &b, const BdxTierArgs &t);
 // Implemented in bdx_pairs.hip (the pairs-mode instantiations; those of the known-end class with reversed sweeps are in
 // bdx_wave_rev.hip, the known-alignment ones in bdx_wave_aln.hip).
-// (the listed reads d_idmap[0 .. *d_count) are fetched straight from the batch; d_idmap == NULL: every read of the batch)
-hipError_t bdx_launch_pairs(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
-                            long long n_reads, const uint32_t *d_idmap, const unsigned int *d_count, const BdxDevOut &out,
-                            unsigned long long *d_counts, uint32_t *list, unsigned int *list_count, hipStream_t stream, int dbg = 0,
-                            const BdxWaveSplit *sp = nullptr, const BdxDevStats *stats = nullptr);
+// (the listed reads t.in are fetched straight from the batch; no input list: every read of the batch)
+hipError_t bdx_launch_pairs(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const BdxBatch &b, const BdxHandOver &ho, const BdxTierArgs &t,
+                            const BdxDevStats *stats);
 
-// Implemented in bdx_device.hip.
-hipError_t bdx_launch_generic(const BdxDevCfg &cfg, const BdxGenericPlan &plan, const uint8_t *d_seq,
-                              const long long *d_off, long long n_reads, const BdxDevOut &out,
-                              unsigned long long *d_counts, const uint32_t *d_cand0,
-                              const uint32_t *d_cand1, hipStream_t stream, const uint32_t *d_wins0 = nullptr,
-                              const uint32_t *d_wins1 = nullptr, const uint8_t *d_wcnt0 = nullptr,
-                              const uint8_t *d_wcnt1 = nullptr, const uint32_t *d_list = nullptr,
-                              const unsigned int *d_list_count = nullptr, const BdxDevStats *stats = nullptr,
-                              const BdxTierArgs *tier = nullptr, const double *tier_slo = nullptr, uint32_t *zero_words = nullptr);
+// Implemented in bdx_device.hip.  blocks: the grid (CallPlan); zero_words: the call's last launch clears these scratch words.
+hipError_t bdx_launch_generic(const BdxDevCfg &cfg, const BdxGenericPlan &plan, const BdxBatch &b, const BdxHandOver &ho, const BdxTierArgs &t,
+                              const BdxDevStats *stats, long long blocks, uint32_t *zero_words);
 // Launch log of the classify call in progress on this thread (bdx_last_launches; bdx_abi.cpp): the launchers note every
 // classify kernel they enqueue while bdx_launch_logging() holds.  tile: reads per tile; units: what the tiles are dealt
 // over (0: no tile loop); list: `reads` is the capacity of a device-side list.
 bool bdx_launch_logging();
 void bdx_note_launch(const char *family, const char *kernel, long long blocks, int threads, int tile, long long units, long long reads, int list);
-// scratch words of a classify call (tile queues, hand-over / tier list lengths): bytes [64, 512) of one half of the context's
-// 1 KiB scratch block; the halves alternate between calls and a call's last launch clears the other one (bdx_abi.cpp)
-#define BDX_SCRATCH_WORDS 112
+// One 512-byte half of the context's 1 KiB scratch block (bdx_ctx::d_maxlen).  The halves alternate between calls and a
+// call's last launch clears the other one's words behind `head` (bdx_abi.cpp), which then needs no memset of its own.
+struct BdxScratch {
+    int head[16];                 // word 0 of half 0 receives bdx_launch_maxlen's result; never cleared by a launch
+    int tile_queue[16];           // tile queue of the call's full-budget fused launch
+    unsigned int exc_count;       // reads the known-score fused kernel hands to the exact kernel ...
+    unsigned int tune_stats[3];   //   ... and its tuning statistics (builds with -DBDX_TUNING)
+    unsigned int pad0[12];
+    unsigned int front_count;     // length of the front stage's / tier 1's list
+    unsigned int pad1[15];
+    int tile_queue_t1[16];        // tile queue of tier 1's fused launch
+    unsigned int mid_count;       // length of the pairs mode's list
+    unsigned int pad2[47];
+};
+static_assert(offsetof(BdxScratch, tile_queue) == 64 && offsetof(BdxScratch, exc_count) == 128 && offsetof(BdxScratch, tune_stats) == 132 &&
+                  offsetof(BdxScratch, front_count) == 192 && offsetof(BdxScratch, tile_queue_t1) == 256 && offsetof(BdxScratch, mid_count) == 320 &&
+                  sizeof(BdxScratch) == 512,
+              "the kernels and bdx_last_list_reads find the scratch words at these offsets");
+// the words a launch clears: everything behind `head`
+constexpr int BDX_SCRATCH_WORDS = (int)((sizeof(BdxScratch) - offsetof(BdxScratch, tile_queue)) / 4);
+static_assert(BDX_SCRATCH_WORDS == 112, "bytes [64, 512) of a half");
 hipError_t bdx_generic_set_lds_limit(size_t bytes);
 // test switch BDX_POISON: checks (and sanitises) one hand-over between a producer and its consumer (bdx_device.hip)
-hipError_t bdx_launch_poison_check(uint32_t *list, const unsigned int *list_count, long long n_reads, const uint32_t *wins, uint8_t *wcnt,
-                                   const uint32_t *cand, int cand_words, int n_barcodes, int check_list, unsigned int *dbg, hipStream_t stream);
+// (list: checked when given; pass >= 0: also that pass's windows and masks in `ho` for these reads)
+hipError_t bdx_launch_poison_check(const BdxBatch &b, const BdxDevList &list, const BdxHandOver &ho, int pass, int n_barcodes, int check_list, unsigned int *dbg);

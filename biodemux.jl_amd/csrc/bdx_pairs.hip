@@ -4,23 +4,18 @@
 // by side.
 #include "bdx_wave_kernel.h"
 
-// Pairs mode over the reads of a list (d_idmap[0 .. *d_count), fetched straight from the batch; d_idmap == NULL: every read of
-// the batch): final verdicts at the full budgets for the known-score class (what it cannot answer goes to `list`), candidate
-// masks + windows in split mode.
-hipError_t bdx_launch_pairs(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const uint8_t *d_seq, const long long *d_off,
-                            long long n_reads, const uint32_t *d_idmap, const unsigned int *d_count, const BdxDevOut &out,
-                            unsigned long long *d_counts, uint32_t *list, unsigned int *list_count, hipStream_t stream, int dbg,
-                            const BdxWaveSplit *sp, const BdxDevStats *stats) {
-    if (wp.pairs_kb <= 0 || !d_seq || !d_off || n_reads <= 0 || (d_idmap && !d_count)) return BDX_BAD_PLAN();
+// Pairs mode over the reads of a list (t.in, fetched straight from the batch; no input list: every read of the batch): final
+// verdicts at the full budgets for the known-score class (what it cannot answer goes to t.out), candidate masks + windows in
+// split mode.  (never a tier 1 with a settle rule: t.tier1 / t.slo are not looked at)
+hipError_t bdx_launch_pairs(const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const BdxBatch &b, const BdxHandOver &ho, const BdxTierArgs &t,
+                            const BdxDevStats *stats) {
+    if (wp.pairs_kb <= 0 || !b.seq || !b.off || b.n_reads <= 0 || (t.in.ids && !t.in.count)) return BDX_BAD_PLAN();
     WaveArgs a;
-    fill_args(a, cfg, wp, hist_entries, out, d_counts, list, list_count, dbg, sp);
+    fill_args(a, cfg, wp, hist_entries, b, ho, t);
     if (stats) {
         if (wp.kend != 3) return BDX_BAD_PLAN();
         a.stats = *stats;
     }
-    a.seq = d_seq;
-    a.off = d_off;
-    a.n_reads = n_reads;
     a.tier = 0;
     a.tier_slo = 0.0;
     a.slot = wp.slot;
@@ -29,40 +24,38 @@ hipError_t bdx_launch_pairs(const BdxDevCfg &cfg, const BdxWavePlan &wp, int his
     a.max_len = wp.read_len_hint;
     a.cpr = wp.cpr;
     a.cpr_inv = (65536 + wp.cpr - 1) / wp.cpr;
-    a.idmap = d_idmap;
-    a.n_dev = d_idmap ? d_count : nullptr;
+    a.idmap = t.in.ids;
+    a.n_dev = t.in.ids ? t.in.count : nullptr;
     a.dual = (!wp.split && cfg.is_dual) ? 1 : 0;
     if (a.dual && wp.cand_words != 4) return BDX_BAD_PLAN();
-    if (wp.split && (!sp || !a.cand_out[0] || !a.wins_out[0] || !a.wcnt_out[0])) return BDX_BAD_PLAN();
+    if (wp.split && (!a.cand_out[0] || !a.wins_out[0] || !a.wcnt_out[0])) return BDX_BAD_PLAN();
     if (wp.rw * wp.cpr > 32 * 40 || (wp.slot & 15) || wp.slot < 16 || wp.rw * wp.slot + 16 > wp.span_cap) return BDX_BAD_PLAN();
-    const size_t lds = bdx_wave_table_bytes(wp, hist_entries) + (size_t)wp.waves * (size_t)a.per_wave;
-    const long long blocks = wp.blocks < 1 ? 1 : wp.blocks;
     // (4 (kb + 2) <= m makes m - kb - 1 >= 16: the first twelve columns of a sweep never need the score)
     if ((wp.pairs_kb > 4 && wp.pairs_kb != 8 && wp.pairs_kb != 9) || wp.nw > 4 || wp.track_from < 12 || wp.n_barcodes > 512 || (wp.groups > 1 && (wp.nw != 4 || wp.split || wp.kend))) return BDX_BAD_PLAN();
     if (wp.pairs_kb >= 8 && (!wp.split || wp.groups > 1)) return BDX_BAD_PLAN();
     if (wp.kend && !wp.d_peq8r) return BDX_BAD_PLAN();
     if (wp.kend == 3) {
         if (wp.pairs_kb > 4 || wp.groups > 1 || wp.split) return BDX_BAD_PLAN();
-        return bdx_launch_pairs_aln(&a, wp, lds, blocks, stream);  // (bdx_wave_aln.hip)
+        return bdx_launch_pairs_aln(&a, wp, b.stream);  // (bdx_wave_aln.hip)
     }
-    if (wp.kend && out.pass_start != nullptr) return BDX_BAD_PLAN();
-    if (wp.kend && out.pass_end != nullptr && (a.trim0 == 3 || a.trim1 == 3)) return BDX_BAD_PLAN();
+    if (wp.kend && b.out.pass_start != nullptr) return BDX_BAD_PLAN();
+    if (wp.kend && b.out.pass_end != nullptr && (a.trim0 == 3 || a.trim1 == 3)) return BDX_BAD_PLAN();
     if ((wp.kend == 2) != (wp.kend && (a.trim0 == 3 || a.trim1 == 3))) return BDX_BAD_PLAN();
-    if (wp.kend == 2) return bdx_launch_pairs_rev(&a, wp, lds, blocks, stream);  // (bdx_wave_rev.hip)
+    if (wp.kend == 2) return bdx_launch_pairs_rev(&a, wp, b.stream);  // (bdx_wave_rev.hip)
     return pairs_ladder<true>(wp, [&](auto c) {
         using C = decltype(c);
         // (same-diagonal variants 8 / 9: weighted costs, i.e. always split mode)
         if constexpr (C::KB >= 8)
-            return launch_wave<16, 12, C::NV, 4, true, C::KB, C::NW>(a, lds, wp.waves, blocks, stream);
+            return launch_wave<16, 12, C::NV, 4, true, C::KB, C::NW>(a, wp, b.stream);
         else  // (many groups, MG: always four mask words, which the checks above made sure of)
-            return wp.groups > 1 ? launch_wave<16, 12, C::NV, 4, false, C::KB, 4, true>(a, lds, wp.waves, blocks, stream)
-                   : wp.split    ? launch_wave<16, 12, C::NV, 4, true, C::KB, C::NW>(a, lds, wp.waves, blocks, stream)
-                   : wp.kend     ? launch_wave<16, 12, C::NV, 4, false, C::KB, C::NW, false, 1>(a, lds, wp.waves, blocks, stream)
-                                 : launch_wave<16, 12, C::NV, 4, false, C::KB, C::NW>(a, lds, wp.waves, blocks, stream);
+            return wp.groups > 1 ? launch_wave<16, 12, C::NV, 4, false, C::KB, 4, true>(a, wp, b.stream)
+                   : wp.split    ? launch_wave<16, 12, C::NV, 4, true, C::KB, C::NW>(a, wp, b.stream)
+                   : wp.kend     ? launch_wave<16, 12, C::NV, 4, false, C::KB, C::NW, false, 1>(a, wp, b.stream)
+                                 : launch_wave<16, 12, C::NV, 4, false, C::KB, C::NW>(a, wp, b.stream);
     });
 }
 
 // The split-mode kernel with per-read column windows (ref_search_range), for bdx_launch_wave.
-hipError_t bdx_launch_wave_split_gen(const void *wave_args, const BdxWavePlan &wp, size_t lds, long long blocks, hipStream_t stream) {
-    return launch_seeded<true, 0, true>(*(const WaveArgs *)wave_args, wp, lds, blocks, stream);
+hipError_t bdx_launch_wave_split_gen(const void *wave_args, const BdxWavePlan &wp, hipStream_t stream) {
+    return launch_seeded<true, 0, true>(*(const WaveArgs *)wave_args, wp, stream);
 }

@@ -4,12 +4,12 @@
 // the sets of instantiations compile side by side.
 #include "bdx_wave_kernel.h"
 
-hipError_t bdx_launch_wave_end_aln(const void *wave_args, const BdxWavePlan &wp, size_t lds, long long blocks, hipStream_t stream) {
+hipError_t bdx_launch_wave_end_aln(const void *wave_args, const BdxWavePlan &wp, hipStream_t stream) {
     if (wp.kend != 3) return BDX_BAD_PLAN();
-    return launch_seeded<false, 3, true>(*(const WaveArgs *)wave_args, wp, lds, blocks, stream);
+    return launch_seeded<false, 3, true>(*(const WaveArgs *)wave_args, wp, stream);
 }
 
-hipError_t bdx_launch_pairs_aln(const void *wave_args, const BdxWavePlan &wp, size_t lds, long long blocks, hipStream_t stream) {
+hipError_t bdx_launch_pairs_aln(const void *wave_args, const BdxWavePlan &wp, hipStream_t stream) {
     if (wp.pairs_kb > 4 || wp.nw > 4 || wp.track_from < 12 || wp.groups > 1 || wp.split || wp.kend != 3) return BDX_BAD_PLAN();
-    return launch_pairs_form<false, 3>(*(const WaveArgs *)wave_args, wp, lds, blocks, stream);
+    return launch_pairs_form<false, 3>(*(const WaveArgs *)wave_args, wp, stream);
 }

@@ -1859,7 +1859,7 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
 }
 
 template <int RW, int TF, int NV, int Q, bool SPLIT, int KB, int NW, bool MG = false, int KEND = 0, bool GEN = true, bool WINM = false>
-hipError_t launch_wave(const WaveArgs &a0, size_t lds, int waves, long long blocks, hipStream_t stream) {
+hipError_t launch_wave(const WaveArgs &a0, const BdxWavePlan &wp, hipStream_t stream) {
     WaveArgs a = a0;
     a.req = (a.out.bc1 ? REQ_BC1 : 0u) | (a.out.bc2 ? REQ_BC2 : 0u) | (a.out.keep_start ? REQ_KS : 0u) | (a.out.keep_end ? REQ_KE : 0u) |
             (a.out.pass_start ? REQ_PSTART : 0u) | (a.out.pass_end ? REQ_PEND : 0u) | (a.out.pass_raw ? REQ_PRAW : 0u) | (a.out.pass_bc ? REQ_PBC : 0u) |
@@ -1873,24 +1873,30 @@ hipError_t launch_wave(const WaveArgs &a0, size_t lds, int waves, long long bloc
         if (e != hipSuccess) return e;
         if (dev >= 0) attr_set[dev].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL((bdx_wave_kernel<RW, TF, NV, Q, SPLIT, KB, NW, MG, KEND, GEN, WINM>), dim3((unsigned)blocks), dim3(64 * waves), lds, stream, a);
+    hipLaunchKernelGGL((bdx_wave_kernel<RW, TF, NV, Q, SPLIT, KB, NW, MG, KEND, GEN, WINM>), dim3((unsigned)wp.grid), dim3(64 * wp.waves), wp.lds_bytes, stream, a);
     if (bdx_launch_logging()) {
         const auto tf = [](bool b) { return b ? "true" : "false"; };
         char name[128];
         snprintf(name, sizeof name, "bdx_wave_kernel<%d, %d, %d, %d, %s, %d, %d, %s, %d, %s, %s>", RW, TF, NV, Q, tf(SPLIT), KB, NW, tf(MG), KEND,
                  tf(GEN), tf(WINM));
-        bdx_note_launch(KB > 0 ? "pairs" : "wave", name, blocks, 64 * waves, RW, blocks * waves, a.n_reads, a.n_dev != nullptr ? 1 : 0);
+        bdx_note_launch(KB > 0 ? "pairs" : "wave", name, wp.grid, 64 * wp.waves, RW, wp.grid * wp.waves, a.n_reads, a.n_dev != nullptr ? 1 : 0);
     }
     return hipGetLastError();
 }
 
-void fill_args(WaveArgs &a, const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const BdxDevOut &out, unsigned long long *d_counts,
-               uint32_t *list, unsigned int *list_count, int dbg, const BdxWaveSplit *sp) {
+// Everything of the argument block that every form fills the same way: from the config, the plan, the batch, the hand-over
+// (empty unless the launch is a split form) and the lists.  tier_slo1 is left 0: the forms with a second pass set it.
+void fill_args(WaveArgs &a, const BdxDevCfg &cfg, const BdxWavePlan &wp, int hist_entries, const BdxBatch &b, const BdxHandOver &ho, const BdxTierArgs &t) {
+    a.seq = b.seq;
+    a.off = b.off;
+    a.n_reads = b.n_reads;
+    a.tier = t.tier1;
+    a.tier_slo = t.slo[0];
     a.max_error_rate = cfg.max_error_rate;
     a.min_delta = cfg.min_delta;
     a.counts_stride2 = cfg.counts_stride2;
-    a.out = out;
-    a.counts = d_counts;
+    a.out = b.out;
+    a.counts = b.counts;
     a.hist_entries = hist_entries;
     a.bitmap = wp.d_bitmap;
     a.bm_bytes = wp.bm_bytes;
@@ -1908,20 +1914,20 @@ void fill_args(WaveArgs &a, const BdxDevCfg &cfg, const BdxWavePlan &wp, int his
     a.B = wp.n_barcodes;
     a.q = wp.q;
     a.span_cap = wp.span_cap;
-    a.per_wave = (int)bdx_wave_area_bytes(wp.rw, wp.span_cap, wp.pairs_kb > 0, wp.hq_cap, wp.sq_cap, wp.cand_words + (wp.ranged ? 4 : 0), wp.winm != 0);
+    a.per_wave = (int)bdx_wave_area_bytes(wp);
     a.hq_cap = wp.hq_cap;
     a.sq_cap = wp.sq_cap;
-    a.list = list;
-    a.list_count = list_count;
+    a.list = t.out.ids;
+    a.list_count = t.out.count;
     a.carry_ent = wp.d_carry;
-    a.dbg = dbg;
+    a.dbg = wp.dbg;
     a.B0 = wp.b0;
     for (int k = 0; k < 2; ++k) {
-        a.cw[k] = sp ? sp->cw[k] : 0;
-        a.cand_out[k] = sp ? sp->cand_out[k] : nullptr;
-        a.wins_out[k] = sp ? sp->wins_out[k] : nullptr;
-        a.wcnt_out[k] = sp ? sp->wcnt_out[k] : nullptr;
-        a.short_lb[k] = sp ? sp->short_lb[k] : 0;
+        a.cw[k] = ho.cand_words[k];
+        a.cand_out[k] = ho.cand[k];
+        a.wins_out[k] = ho.wins[k];
+        a.wcnt_out[k] = ho.wcnt[k];
+        a.short_lb[k] = ho.short_lb[k];
     }
     a.sg = cfg.algorithm == BDX_ALG_SEMIGLOBAL ? 1 : 0;
     a.ngroups = wp.groups > 0 ? wp.groups : 1;
@@ -1942,14 +1948,6 @@ void fill_args(WaveArgs &a, const BdxDevCfg &cfg, const BdxWavePlan &wp, int his
     a.cpr_inv = 65536;
     a.idmap = nullptr;
     a.n_dev = nullptr;
-}
-
-// Workgroups of a launch over contiguous tiles: the plan's, but no more than give every wave one tile; at least one.
-long long wave_grid(const BdxWavePlan &wp, long long n_reads) {
-    const long long tiles = (n_reads + wp.rw - 1) / wp.rw;
-    const long long useful = (tiles + wp.waves - 1) / wp.waves;
-    const long long blocks = wp.blocks < useful ? (long long)wp.blocks : useful;
-    return blocks < 1 ? 1 : blocks;
 }
 
 // ---- dispatch ladders: from a plan to one instantiation ----
@@ -2005,10 +2003,10 @@ hipError_t seeded_ladder(const BdxWavePlan &wp, Leaf leaf) {
 
 // The seeded ladder of a launcher with one form: every cell launches its <SPLIT, KEND, GEN, WINM> instantiation.
 template <bool SPLIT, int KEND, bool GEN, bool WINM = false>
-hipError_t launch_seeded(const WaveArgs &a, const BdxWavePlan &wp, size_t lds, long long blocks, hipStream_t stream) {
+hipError_t launch_seeded(const WaveArgs &a, const BdxWavePlan &wp, hipStream_t stream) {
     return seeded_ladder<WINM>(wp, [&](auto c) {
         using C = decltype(c);
-        return launch_wave<C::RW, C::TF, C::NV, C::Q, SPLIT, 0, 0, false, KEND, GEN, WINM>(a, lds, wp.waves, blocks, stream);
+        return launch_wave<C::RW, C::TF, C::NV, C::Q, SPLIT, 0, 0, false, KEND, GEN, WINM>(a, wp, stream);
     });
 }
 
@@ -2043,10 +2041,10 @@ hipError_t pairs_ladder(const BdxWavePlan &wp, Leaf leaf) {
 
 // The pairs ladder of a launcher with one form: every cell launches its <SPLIT, KEND> instantiation.
 template <bool SPLIT, int KEND>
-hipError_t launch_pairs_form(const WaveArgs &a, const BdxWavePlan &wp, size_t lds, long long blocks, hipStream_t stream) {
+hipError_t launch_pairs_form(const WaveArgs &a, const BdxWavePlan &wp, hipStream_t stream) {
     return pairs_ladder<false>(wp, [&](auto c) {
         using C = decltype(c);
-        return launch_wave<16, 12, C::NV, 4, SPLIT, C::KB, C::NW, false, KEND>(a, lds, wp.waves, blocks, stream);
+        return launch_wave<16, 12, C::NV, 4, SPLIT, C::KB, C::NW, false, KEND>(a, wp, stream);
     });
 }
 
@@ -2055,11 +2053,11 @@ hipError_t launch_pairs_form(const WaveArgs &a, const BdxWavePlan &wp, size_t ld
 // Launchers that one translation unit calls in another (the argument block crosses as bytes: WaveArgs is unit-local,
 // compiled into each of them).
 // bdx_wave_end.hip / bdx_pairs.hip: the general (dual / ranged) forms of bdx_launch_wave's non-split and split kernels
-hipError_t bdx_launch_wave_gen(const void *wave_args, const BdxWavePlan &wp, size_t lds, long long blocks, hipStream_t stream);
-hipError_t bdx_launch_wave_split_gen(const void *wave_args, const BdxWavePlan &wp, size_t lds, long long blocks, hipStream_t stream);
+hipError_t bdx_launch_wave_gen(const void *wave_args, const BdxWavePlan &wp, hipStream_t stream);
+hipError_t bdx_launch_wave_split_gen(const void *wave_args, const BdxWavePlan &wp, hipStream_t stream);
 // bdx_wave_rev.hip: the known-trim instantiations with reversed sweeps, KEND = 2
-hipError_t bdx_launch_wave_end_rev(const void *wave_args, const BdxWavePlan &wp, size_t lds, long long blocks, hipStream_t stream);
-hipError_t bdx_launch_pairs_rev(const void *wave_args, const BdxWavePlan &wp, size_t lds, long long blocks, hipStream_t stream);
+hipError_t bdx_launch_wave_end_rev(const void *wave_args, const BdxWavePlan &wp, hipStream_t stream);
+hipError_t bdx_launch_pairs_rev(const void *wave_args, const BdxWavePlan &wp, hipStream_t stream);
 // bdx_wave_aln.hip: the known-alignment instantiations, KEND = 3
-hipError_t bdx_launch_wave_end_aln(const void *wave_args, const BdxWavePlan &wp, size_t lds, long long blocks, hipStream_t stream);
-hipError_t bdx_launch_pairs_aln(const void *wave_args, const BdxWavePlan &wp, size_t lds, long long blocks, hipStream_t stream);
+hipError_t bdx_launch_wave_end_aln(const void *wave_args, const BdxWavePlan &wp, hipStream_t stream);
+hipError_t bdx_launch_pairs_aln(const void *wave_args, const BdxWavePlan &wp, hipStream_t stream);

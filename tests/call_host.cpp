@@ -8,7 +8,7 @@
 //
 //   call_host CASES [REPEAT | launches]
 //     REPEAT > 0: also prints the mean host time of one bdx_plan_call per case on stderr (ns, not compared)
-//     launches: also prints the launches every plan leads to (report_launches), for the comparison with bdx_last_launches
+//     launches: also prints the launches every plan holds (report_launches), for the golden file and the comparison with bdx_last_launches
 //
 // (diag_nw / diag_qcap are reported for a launch whose seed plan is the two-intact-pieces index; nothing else reads them)
 #include <algorithm>
@@ -60,7 +60,7 @@ static void report_tiles(const char *key, const BdxWavePlan &w) {
 // c<i>.fused / .t1: reads_per_block stage_bytes slot_bytes seed_span r_cap diag_nw diag_qcap LDS bytes
 // c<i>.wfront / .wmid / .wfull: rw waves blocks span_cap hq_cap sq_cap slot cpr scan_gpr winm read_len_hint
 // c<i>.seed: per set 0: the set's own seed plan, 1: the weak single seeds kept beside it, 2: no seeds
-static void report_call(int i, int rc, const std::string &err, const CallPlan &p, const BdxPlanOut &po, const BdxCallEnv &env, const BdxSeedChoice seed[2]) {
+static void report_call(int i, int rc, const std::string &err, const CallPlan &p, const BdxPlanOut &po, const BdxSeedChoice seed[2]) {
     char key[32];
     const auto k = [&](const char *field) {
         snprintf(key, sizeof key, "c%d.%s", i, field);
@@ -73,10 +73,9 @@ static void report_call(int i, int rc, const std::string &err, const CallPlan &p
         printf("%s %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d\n", k("plan"), p.npass, p.tier_len, p.batch_len, (int)p.split, (int)p.windows, (int)p.dense_w,
                p.short_lb[0], p.short_lb[1], (int)p.front, (int)p.t1_exact, (int)p.middle, (int)p.full, (int)p.exact, (int)p.carry, (int)p.aln);
         printf("%s %s\n", k("path"), p.path.c_str());
-        report_fused(k("fused"), p.fused, bdx_seed_plan(po.fs[0], p.seed[0]), p.lds_bytes);
+        report_fused(k("fused"), p.fused, bdx_seed_plan(po.fs[0], p.seed[0]), p.fused.lds_bytes);
         if (p.front == Front::bitpar) {
-            const BdxSeedPlan s1 = bdx_seed_plan(po.fs[1], p.seed[1]);
-            report_fused(k("t1"), p.t1, s1, bdx_bitpar_lds_bytes(env.dev, p.t1, env.plan, &s1));
+            report_fused(k("t1"), p.t1, bdx_seed_plan(po.fs[1], p.seed[1]), p.t1.lds_bytes);
         } else if (p.front != Front::none) {
             report_tiles(k("wfront"), p.wfront);
         }
@@ -88,10 +87,11 @@ static void report_call(int i, int rc, const std::string &err, const CallPlan &p
     printf("%s %d %d\n", k("seed"), eff[0], eff[1]);
 }
 
-// What the launchers make of a plan (bdx_launch_bitpar, wave_grid, bdx_launch_pairs, bdx_launch_generic), one line per classify
-// kernel in the order of the stages: family blocks threads tile list + the template arguments the plan decides
+// The launches a plan holds, one line per classify kernel in the order of the stages: family, then blocks, threads, tile and
+// list flag as the plan states them (the launchers take the grid from the plan; tests/golden/call_plans.json holds these lines
+// as the launchers of the commit before computed them), then the template arguments the plan decides
 //   bitpar: R SEED DIAG NW WL | wave, pairs: RW SPLIT KEND WINM | generic: BS
-static void report_launches(int i, const CallPlan &p, const BdxPlanOut &po, const BdxCallEnv &env, long long n_reads) {
+static void report_launches(int i, const CallPlan &p, const BdxPlanOut &po) {
     int j = 0;
     const auto line = [&](const char *family, long long blocks, int threads, int tile, int list, int a, int b, int c, int d, int e) {
         printf("c%d.launch%d %s %lld %d %d %d %d %d %d %d %d\n", i, j++, family, blocks, threads, tile, list, a, b, c, d, e);
@@ -99,31 +99,21 @@ static void report_launches(int i, const CallPlan &p, const BdxPlanOut &po, cons
     const auto fused = [&](int set, const BdxBitparPlan &b, int list) {
         const BdxSeedPlan sp = bdx_seed_plan(po.fs[set], p.seed[set]);
         const bool diag = sp.enabled && sp.diag;
-        long long per_cu = bdx_lds_residency(bdx_bitpar_lds_bytes(env.dev, b, env.plan, &sp));
-        per_cu = per_cu < 1 ? 1 : per_cu > 8 ? 8 : per_cu;
-        const long long tiles = (n_reads + b.reads_per_block - 1) / b.reads_per_block;
-        line("bitpar", std::min(env.n_cu * per_cu, tiles), 256, b.reads_per_block, list, b.reads_per_block, sp.enabled != 0, diag, diag && b.diag_nw > 5 ? 10 : 5,
+        line("bitpar", b.grid, 256, b.reads_per_block, list, b.reads_per_block, sp.enabled != 0, diag, diag && b.diag_nw > 5 ? 10 : 5,
              b.word_bytes == 8 ? 1 : b.word_bytes == 16 ? 2 : 0);
     };
-    const auto wave = [&](const BdxWavePlan &w) {
-        const long long tiles = (n_reads + w.rw - 1) / w.rw, useful = (tiles + w.waves - 1) / w.waves;
-        line("wave", std::max(1LL, std::min<long long>(w.blocks, useful)), 64 * w.waves, w.rw, 0, w.rw, w.split, w.kend, w.winm, 0);
-    };
-    const auto pairs = [&](const BdxWavePlan &w, int list) { line("pairs", std::max(1, w.blocks), 64 * w.waves, 16, list, 16, w.split, w.kend, 0, 0); };
-    const auto generic = [&](int list) {
-        long long blocks = (n_reads + env.plan.threads - 1) / env.plan.threads;
-        if (list) blocks = std::min(blocks, 4LL * env.plan.n_cu);
-        line("generic", blocks, env.plan.threads, env.plan.threads, list, env.plan.threads, 0, 0, 0, 0);
-    };
-    if (!p.filtered) return generic(0);
+    const auto wave = [&](const BdxWavePlan &w) { line("wave", w.grid, 64 * w.waves, w.rw, 0, w.rw, w.split, w.kend, w.winm, 0); };
+    const auto pairs = [&](const BdxWavePlan &w, int list) { line("pairs", w.grid, 64 * w.waves, 16, list, 16, w.split, w.kend, 0, 0); };
+    const auto generic = [&](long long blocks, int list) { line("generic", blocks, po.plan.threads, po.plan.threads, list, po.plan.threads, 0, 0, 0, 0); };
+    if (!p.filtered) return generic(p.exact_blocks, 0);
     if (p.front == Front::bitpar) fused(1, p.t1, 0);
     else if (p.front == Front::pairs) pairs(p.wfront, 0);
     else if (p.front != Front::none) wave(p.wfront);
-    if (p.t1_exact) generic(0);
+    if (p.t1_exact) generic(p.t1_exact_blocks, 0);
     if (p.middle != Middle::none) pairs(p.wmid, p.middle != Middle::all);
     if (p.full == Full::wave_split) wave(p.wfull);
     if (p.full == Full::bitpar) fused(0, p.fused, p.front != Front::none);
-    generic(p.exact != Exact::split);
+    generic(p.exact_blocks, p.exact != Exact::split);
 }
 
 // ---- the planner under test: one context's worth of state and one call ------------------------------------------------
@@ -162,8 +152,8 @@ static void run_case(const Case &cs, int repeat, bool launches) {
         std::string err;
         const BdxCallArgs a = parse_call(cs.calls[i]);
         const int crc = ses.call(a, p, err);
-        report_call((int)i, crc, err, p, po, ses.env(), ses.seed);
-        if (launches && crc == BDX_OK) report_launches((int)i, p, po, ses.env(), a.n_reads);
+        report_call((int)i, crc, err, p, po, ses.seed);
+        if (launches && crc == BDX_OK) report_launches((int)i, p, po);
     }
     printf("digest.after %016llx\n", (unsigned long long)digest(po, npass));
     if (repeat > 0 && !cs.calls.empty()) {  // the last call again and again, on the state the sequence left

@@ -43,6 +43,7 @@ static bool set_tuning(Case &cs, const std::string &key, const std::string &val)
     T(no_kend) T(no_pairs) T(no_wave) T(no_tier) T(no_band_roll) T(no_known_exact) T(no_kaln) T(pairs_nw)
     T(no_win) T(no_carry) T(no_windows) T(no_slot) T(tier0_div) T(wave_rw) T(wave_waves) T(wave_maxres) T(bitpar_r)
 #undef T
+    if (key == "grid") { t.grid = atoll(val.c_str()); return true; }
     if (key == "wave_chance") { t.wave_chance = atof(val.c_str()); return true; }
     if (key == "n_cu") { cs.n_cu = atoi(val.c_str()); return true; }
     return false;

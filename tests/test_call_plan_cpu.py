@@ -4,8 +4,10 @@ runs agree, a call never changes what the create-time planner produced, and ever
 tests/golden/call_plans.json — recorded from size_* / plan_call / call_path of the commit before the call planner was split
 out of bdx_abi.cpp, run on the CPU over a stub of the HIP runtime, every sequence on one context.  One step differs by design:
 there the parent handed a dense request the slot-mode geometry the call before had left in the shared plan; the
-golden file holds the parent's value with that history and on a fresh context, and the latter is asserted.  The same driver
-then runs under ASan / UBSan (no Python process loads sanitised code)."""
+golden file holds the parent's value with that history and on a fresh context, and the latter is asserted.  The launch lines
+(c<i>.launch<j>: the grid, block size, tile and list flag of every classify kernel) were recorded from the commit before the
+planner took the grids over from the launchers, whose formulas that commit's driver restated.  The same driver then runs under
+ASan / UBSan (no Python process loads sanitised code)."""
 import json
 
 import pytest
@@ -17,7 +19,7 @@ from test_sanitizers import ENV, SAN
 @pytest.fixture(scope="module")
 def reports(tmp_path_factory):
     d = tmp_path_factory.mktemp("call")
-    return CC.run_driver(CC.build_driver(d), d), d
+    return CC.run_driver(CC.build_driver(d), d, launches=True), d
 
 
 @pytest.fixture(scope="module")
@@ -39,7 +41,7 @@ def test_call_case_sits_on_its_side(reports, case):
 
 def test_call_planner_is_deterministic(reports, tmp_path):
     first, d = reports
-    again = CC.run_driver(str(d / "call_host"), tmp_path)
+    again = CC.run_driver(str(d / "call_host"), tmp_path, launches=True)
     assert {k: v.flat() for k, v in again.items()} == {k: v.flat() for k, v in first.items()}
 
 
@@ -72,5 +74,5 @@ def test_call_plan_equals_the_golden_file(reports, golden, case):
 
 def test_call_planner_under_asan_ubsan(tmp_path):
     exe = CC.build_driver(tmp_path, flags=SAN)
-    got = CC.run_driver(exe, tmp_path, env=ENV)
+    got = CC.run_driver(exe, tmp_path, env=ENV, launches=True)
     assert len(got) == len(CC.CASES)

@@ -1,7 +1,8 @@
 """The library launches what the per-call planner decides: a dozen call shapes of tests/call_cases.py's kind at their smallest
 real size — a few thousand synthetic reads with BDX_CU_COUNT=2, so that the tile thresholds sit at ~1 000 reads — among them a
 sequence on one context (313 bases, then 150) and a call that wants the per-pass positions, and the headline shape at the
-device's own compute-unit count.  For every call bdx_kernel_path and every line of bdx_last_launches (family, blocks, threads,
+device's own compute-unit count, the fused kernel under a forced grid (BDX_GRID below and above its tile count) and a config
+outside the filters' domain (the generic kernel alone).  For every call bdx_kernel_path and every line of bdx_last_launches (family, blocks, threads,
 tile, list flag and the template arguments the plan decides) equal what tests/call_host.cpp, built and run here with the same
 switches and n_cu, predicts from csrc/bdx_call.cpp alone; the verdicts equal the oracle."""
 import ctypes
@@ -20,7 +21,7 @@ from biodemux_jl_amd import synth
 pytestmark = pytest.mark.gpu
 
 NTHREADS = min(16, os.cpu_count() or 1)
-KNOBS = {"BDX_CU_COUNT": "n_cu", "BDX_WAVE_RW": "wave_rw", "BDX_NO_WAVE": "no_wave", "BDX_NO_TIER": "no_tier"}
+KNOBS = {"BDX_CU_COUNT": "n_cu", "BDX_WAVE_RW": "wave_rw", "BDX_NO_WAVE": "no_wave", "BDX_NO_TIER": "no_tier", "BDX_GRID": "grid"}
 B1 = synth.make_barcodes(96, 24, seed=20260515)
 B4A, B4B = synth.make_barcodes(24, 24, seed=1), synth.make_barcodes(16, 24, seed=2)
 
@@ -48,6 +49,12 @@ SHAPES = {
     "hamming_wave_split": (dict(max_error_rate=0.1, matching_algorithm="hamming"), False, {"BDX_CU_COUNT": "2"}, False, [(3001, 150)], "wave+verify"),
     "seq_313_then_150": (dict(max_error_rate=0.13), False, {"BDX_CU_COUNT": "2", "BDX_NO_WAVE": "1", "BDX_NO_TIER": "1"}, False, [(2001, 313), (3001, 150)],
                          "bitpar+verify"),
+    # the fused kernel's forced grid: three workgroups; more than there are tiles: one per tile
+    "grid_3": (dict(max_error_rate=0.1), False, {"BDX_CU_COUNT": "2", "BDX_NO_WAVE": "1", "BDX_GRID": "3"}, False, [(3001, 150)], "qgram+bitpar+verify"),
+    "grid_1000_clamped": (dict(max_error_rate=0.1), False, {"BDX_CU_COUNT": "2", "BDX_NO_WAVE": "1", "BDX_GRID": "1000"}, False, [(3001, 150)],
+                          "qgram+bitpar+verify"),
+    # a match that scores is outside every filter's cost domain: the generic kernel alone, a thread per read
+    "generic_alone": (dict(max_error_rate=0.2, match=-1, mismatch=2, indel=3), False, {"BDX_CU_COUNT": "2"}, False, [(3001, 150)], "generic"),
 }
 ALG = {"semiglobal": PC.SEMIGLOBAL, "hamming": PC.HAMMING, "exact": PC.EXACT}
 
@@ -80,7 +87,7 @@ def _predicted(driver, name, kw, dual, env, want_pass, calls):
     passes = [PC.one_pass(B4A if dual else B1, trim=kw.get("trim_side") or 0)] + ([PC.one_pass(B4B, trim=kw.get("trim_side2") or 0)] if dual else [])
     wanted = 0x3FF if want_pass else 0xF
     case = CC.CallCase(name, None, [CC.call(n, L, wanted=wanted) for n, L in calls], passes=passes, rate=kw["max_error_rate"], min_delta=kw.get("min_delta", 0.0),
-                       costs=(0, 1, kw.get("indel", 1)), algorithm=ALG[kw.get("matching_algorithm", "semiglobal")], tune=tune)
+                       costs=(kw.get("match", 0), kw.get("mismatch", 1), kw.get("indel", 1)), algorithm=ALG[kw.get("matching_algorithm", "semiglobal")], tune=tune)
     exe, d = driver
     return CC.run_driver(exe, d, cases=[case], launches=True)[name]
 
@@ -104,7 +111,8 @@ def test_the_library_launches_the_planned_call(name, driver, monkeypatch):
             got = hc.classify(seq, off)
             launches = hc.last_launches
             what = f"{name} call {c} [{hc.kernel_path}] {launches}"
-            assert hc.kernel_path == want.path(c) and path_holds in hc.kernel_path, f"{what}: planned {want.path(c)}"
+            planned_path = want.path(c) if want.i("c%d.filtered" % c) else "generic"
+            assert hc.kernel_path == planned_path and path_holds in hc.kernel_path, f"{what}: planned {planned_path}"
             planned = want.launches(c)
             assert [ln["family"] for ln in launches] == [p["family"] for p in planned], f"{what}: planned {planned}"
             for ln, p in zip(launches, planned):
@@ -116,7 +124,13 @@ def test_the_library_launches_the_planned_call(name, driver, monkeypatch):
                     assert a["BS"] == p["args"][0], f"{what}: planned {p}"
                 else:
                     assert (a["RW"], int(a["SPLIT"]), a["KEND"], int(a["WINM"])) == p["args"][:4] and (a["KB"] > 0) == (p["family"] == "pairs"), f"{what}: planned {p}"
+            if "BDX_GRID" in env:  # as forced, but never more workgroups than tiles
+                fused = [ln for ln in launches if ln["family"] == "bitpar"]
+                assert fused and all(ln["blocks"] == min(int(env["BDX_GRID"]), -(-n // ln["tile"])) for ln in fused), what
             fuzz.assert_same(got, oc.classify(seq, off), what)
             assert np.array_equal(hc.counts, oc.counts), f"{what}: counters"
         info = hc.launch_info()
-        assert info["reads_per_block"] == want.fused(len(calls) - 1)["reads_per_block"] and info["lds_bytes_per_block"] == want.fused(len(calls) - 1)["lds"]
+        if want.i("c%d.filtered" % (len(calls) - 1)):
+            assert info["reads_per_block"] == want.fused(len(calls) - 1)["reads_per_block"] and info["lds_bytes_per_block"] == want.fused(len(calls) - 1)["lds"]
+        else:
+            assert (info["blocks"], info["reads_per_block"]) == (planned[0]["blocks"], planned[0]["tile"]) and len(planned) == 1
