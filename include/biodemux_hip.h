@@ -163,7 +163,13 @@ int32_t bdx_classify_host(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t 
 
 /* Same, with every pointer (seq_bytes, seq_off, outputs) already resident in HBM on
  * ctx's device.  Asynchronous on the context's stream; call bdx_sync() before reading.
- * This is the entry the multi-GPU driver and bench.py use. */
+ * This is the entry the multi-GPU driver and bench.py use.
+ * Calls may be enqueued one after another with nothing in between.  A call waits for the
+ * stream before it returns in three cases only: config.need_traceback (summary = true: the
+ * batch's longest read is measured, the statistics tables may grow), no read-length hint
+ * (bdx_set_read_length_hint: the batch is measured), and a batch larger than any before
+ * (a hand-over buffer grows: the old one is released with hipFree, which synchronises the
+ * device).  Inputs and outputs must stay valid until the stream has passed the call. */
 int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int64_t *d_seq_off,
                             int64_t n_reads, const bdx_outputs_t *d_out);
 
@@ -177,7 +183,10 @@ int32_t bdx_set_read_length_hint(bdx_ctx *ctx, int32_t typical_read_length);
 int32_t bdx_sync(bdx_ctx *ctx);
 
 /* Use an existing hipStream_t (e.g. PyTorch's current stream) for all work of this context.
- * NULL restores the context's own stream. */
+ * NULL restores the context's own stream.  The library does not order the new stream after
+ * the old one: a caller that switches while work of this context may still be running makes
+ * the new stream wait for it first (an event recorded on the old stream, or bdx_sync()).  The
+ * counter vector (bdx_set_counts_buffer) and the statistics tables are untouched by a switch. */
 int32_t bdx_set_stream(bdx_ctx *ctx, void *hip_stream);
 
 /* DemuxStats scalar part (classification.jl:736-744, updated at :942,:950,:953,:963,:966,
