@@ -1,6 +1,6 @@
 // bdx_abi.cpp — C-ABI of libbiodemux_hip.so (see include/biodemux_hip.h for the contract and
 // the reference lines each entry point replaces).  Host-side only: validation, upload of what the create-time planner
-// (bdx_plan.cpp) produced, reserve and enqueue of what the per-call planner (bdx_call.cpp) decided (the host entry point, bdx_classify_host, is bdx_host.cpp).  All arithmetic of the hot path runs in the gfx950
+// (bdx_plan.cpp) produced, reserve and enqueue of what the per-call planner (bdx_call.cpp) decided — bdx_classify_batch, which both entry points end in (the host entry point, bdx_classify_host, is bdx_host.cpp).  All arithmetic of the hot path runs in the gfx950
 // kernels of bdx_device.hip / bdx_filter.hip; there is NO CPU fallback — without a usable
 // HIP device every entry point fails with BDX_E_DEVICE.
 #include <cmath>
@@ -252,10 +252,9 @@ int bdx_stats_reserve(bdx_ctx *ctx, long long rows, bool exact) {
     // zeroing and copying run on the context's stream (the kernels that add to the tables do, and a non-blocking or
     // caller-supplied stream has no implicit order with the NULL stream); old tables are freed after one more sync
     const int npass = ctx->dev.is_dual ? 2 : 1;
-    std::vector<DevBuf> retired;
+    std::vector<DevBuf> retired;  // old tables: freed once the stream is idle (a new table of a failed step dies after the same wait)
     auto retire_all = [&]() {
         (void)hipStreamSynchronize(ctx->stream);
-        for (DevBuf &b : retired) b.release();
         retired.clear();
     };
     if (!ctx->st_len_fixed) {
@@ -274,12 +273,11 @@ int bdx_stats_reserve(bdx_ctx *ctx, long long rows, bool exact) {
                                       hipMemcpyDeviceToDevice, ctx->stream);
             if (e1 != hipSuccess) {
                 retire_all();
-                nb.release();
                 ctx->st_len_rows = old_rows;
                 return fail(ctx, BDX_E_DEVICE, "growing the statistics tables failed: %s", hipGetErrorString(e1));
             }
-            retired.push_back(ctx->st_tab[p][1]);
-            ctx->st_tab[p][1] = nb;
+            retired.push_back(std::move(ctx->st_tab[p][1]));
+            ctx->st_tab[p][1] = std::move(nb);
         }
     }
     for (int p = 0; p < npass; ++p)
@@ -292,11 +290,10 @@ int bdx_stats_reserve(bdx_ctx *ctx, long long rows, bool exact) {
             if (e1 == hipSuccess && old_bytes) e1 = hipMemcpyAsync(nb.p, ctx->st_tab[p][w].p, old_bytes, hipMemcpyDeviceToDevice, ctx->stream);
             if (e1 != hipSuccess) {
                 retire_all();
-                nb.release();
                 return fail(ctx, BDX_E_DEVICE, "growing the statistics tables failed: %s", hipGetErrorString(e1));
             }
-            retired.push_back(ctx->st_tab[p][w]);
-            ctx->st_tab[p][w] = nb;  // row-major by key: the old table is a prefix of the new one
+            retired.push_back(std::move(ctx->st_tab[p][w]));
+            ctx->st_tab[p][w] = std::move(nb);  // row-major by key: the old table is a prefix of the new one
         }
     retire_all();
     ctx->st_rows = want;
@@ -449,64 +446,19 @@ void bdx_destroy(bdx_ctx *ctx) {
         unsigned int rej[2] = {0, 0};
         if (hipMemcpy(rej, ctx->d_dbg.p, sizeof rej, hipMemcpyDeviceToHost) == hipSuccess) g_rejected_windows += (long long)rej[0] + rej[1];
     }
-    ctx->d_dbg.release();
-    for (int k = 0; k < 2; ++k) {
-        ctx->bc_bytes[k].release();
-        ctx->bc_off[k].release();
-        ctx->bc_nn[k].release();
-        ctx->d_cand[k].release();
-        ctx->d_wins[k].release();
-        ctx->d_wcnt[k].release();
-    }
-    ctx->counts_own.release();
-    for (BdxFilterSet &f : ctx->fs) {
-        f.bp_tables.release();
-        f.seed_tables.release();
-        f.seed_tables_alt.release();
-        f.wave_tables.release();
-        f.pair_tables.release();
-    }
-    ctx->d_wlist.release();
-    ctx->d_tier.release();
-    ctx->d_carry.release();
-    ctx->d_maxlen.release();
-    ctx->d_exc.release();
-    ctx->d_seq.release();
-    ctx->d_off.release();
-    ctx->d_out_i32.release();
-    ctx->d_out_f64.release();
-    ctx->d_vlen.release();
-    ctx->d_vlo.release();
-    ctx->h_stage.release();
-    ctx->h_in.release();
-    ctx->h_back.release();
     if (ctx->back_events_made)
         for (hipEvent_t &e : ctx->back_events)
             if (e) (void)hipEventDestroy(e);
-    ctx->back_events_made = false;
     bdx_comm_release(ctx);
-    ctx->counts_sum.release();
-    for (int p = 0; p < 2; ++p)
-        for (int w = 0; w < 3; ++w) {
-            ctx->st_tab[p][w].release();
-            ctx->st_sum[p][w].release();
-        }
-    ctx->st_flag.release();
-    for (DevBuf &b : ctx->fq) b.release();
-    for (DevBuf &b : ctx->dfl) b.release();
-    for (DevBuf &b : ctx->inf) b.release();
-    delete ctx;
+    delete ctx;  // (every DevBuf / PinnedBuf of the context frees itself, on the device selected above and after its streams are idle)
 }
 
 int32_t bdx_set_stream(bdx_ctx *ctx, void *hip_stream) {
     if (!ctx) return BDX_E_INVALID;
     const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
-    if (s != ctx->stream) {
-        // the scratch half the next call takes was cleared by a launch on the old stream, which the new one is not ordered
-        // after: the next call clears its scratch words itself
-        ctx->scratch_clean[0] = ctx->scratch_clean[1] = false;
-        ctx->scratch_zeroed = false;
-    }
+    // the scratch half the next call takes was cleared by a launch on the old stream, which the new one is not ordered
+    // after: the next call clears its scratch words itself
+    if (s != ctx->stream) ctx->turn.stream_changed();
     ctx->stream = s;
     return BDX_OK;
 }
@@ -523,11 +475,11 @@ int32_t bdx_sync(bdx_ctx *ctx) {
     return BDX_OK;
 }
 
-// ---- one filtered classify call: plan (bdx_plan_call, bdx_call.cpp), reserve (buffers, poison, scratch), enqueue ----------------
+// ---- one filtered classify call, after its plan (bdx_plan_call, bdx_call.cpp): reserve (buffers, poison, scratch), enqueue ------
 
 // Buffers of the plan's hand-overs, the test switch's fills, this call's half of the scratch block and the per-launch
 // fields of the plans.
-static int reserve(bdx_ctx *ctx, CallPlan &p, long long n_reads) {
+static int reserve(bdx_ctx *ctx, CallPlan &p, long long n_reads, bool scratch_cleared) {
     const bool tiered = p.tier_len > 0;
     const size_t list_bytes = (size_t)n_reads * 4 + 64;
     for (int k = 0; k < p.npass; ++k) {
@@ -560,10 +512,7 @@ static int reserve(bdx_ctx *ctx, CallPlan &p, long long n_reads) {
     // already did: the halves alternate, so a call needs no memset of its own (5 us of fill + a launch gap per call, 1 % of a
     // 10 M-read C2 step)
     BdxScratch *const scratch = ctx->scratch();
-    const int spar = ctx->scratch_par & 1;
-    if (!ctx->scratch_zeroed && !ctx->scratch_clean[spar]) HIP_TRY(ctx, hipMemsetAsync(scratch->tile_queue, 0, 4 * BDX_SCRATCH_WORDS, ctx->stream));
-    ctx->scratch_zeroed = false;
-    ctx->scratch_clean[spar] = false;  // (a call that fails half-way leaves it that way: the next one clears it itself)
+    if (ctx->turn.begin_call(scratch_cleared)) HIP_TRY(ctx, hipMemsetAsync(scratch->tile_queue, 0, 4 * BDX_SCRATCH_WORDS, ctx->stream));
     for (int set = tiered ? 1 : 0; set >= 0; --set) {
         BdxBitparPlan &b = set ? p.t1 : p.fused;
         b.d_tile_counter = set ? scratch->tile_queue_t1 : scratch->tile_queue;
@@ -573,7 +522,8 @@ static int reserve(bdx_ctx *ctx, CallPlan &p, long long n_reads) {
     return BDX_OK;
 }
 
-static int enqueue(bdx_ctx *ctx, const CallPlan &p, const BdxBatch &b, const BdxDevStats *stp) {
+// dev: the call's copy of the device config (a window upload's per-read pointers are in it)
+static int enqueue(bdx_ctx *ctx, const CallPlan &p, const BdxDevCfg &dev, const BdxBatch &b, const BdxDevStats *stp) {
     const BdxFilterSet &f0 = ctx->fs[0], &f1 = ctx->fs[1];
     const bool tiered = p.tier_len > 0;
     BdxScratch *const scratch = ctx->scratch();
@@ -581,7 +531,7 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const BdxBatch &b, const Bdx
     BdxHandOver ho{};
     for (int k = 0; k < 2; ++k) {
         const int buf = k < p.npass ? k : 0;
-        ho.cand_words[k] = k < p.npass ? ctx->dev.pass[k].cand_words : 0;
+        ho.cand_words[k] = k < p.npass ? dev.pass[k].cand_words : 0;
         ho.cand[k] = (uint32_t *)ctx->d_cand[buf].p;
         ho.wins[k] = p.windows ? (uint32_t *)ctx->d_wins[buf].p : nullptr;
         ho.wcnt[k] = p.windows ? (uint8_t *)ctx->d_wcnt[buf].p : nullptr;
@@ -595,23 +545,12 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const BdxBatch &b, const Bdx
     const BdxTierArgs no_lists{}, tier1{none, front, 1, {slo[0], slo[1]}};
     const BdxTierArgs front_out = tiered ? tier1 : BdxTierArgs{none, front, 0, {0.0, 0.0}};  // a front stage that settles and lists
     const auto over = [&](const BdxDevList &in, const BdxDevList &out) { return BdxTierArgs{in, out, 0, {0.0, 0.0}}; };
-    // diagonal-band DP of the exact kernel (sg_core_band): clean class, every barcode of the config with the same
-    // number of rows and of the pass with the same budget, column windows handed over by tracked sweeps
-    const auto band_cfg = [&](const BdxFilterSet &f) {
-        BdxDevCfg dv = ctx->dev;
-        dv.dense_w = (&f == &ctx->fs[0]) && p.dense_w;
-        for (int k = 0; k < p.npass; ++k) {
-            const int kb = f.bplan.kb_uniform[k];
-            // (rolling band, barcodes beyond 32 rows: any uniform budget; the first end column is rebuilt from the hand-over row
-            // when every barcode has the same length — band_lb is made of max_m)
-            const bool on = ctx->plan.band_roll ? (p.windows && ctx->plan.same_len && kb >= 0)
-                                                : (p.windows && ctx->plan.clean && ctx->plan.uniform_len > 0 && !ctx->tune.no_band &&
-                                                   ctx->dev.algorithm == BDX_ALG_SEMIGLOBAL && kb >= 0 && kb <= 4);
-            dv.band_m = ctx->plan.uniform_len;
-            dv.band_kb[k] = on ? kb : -1;
-            if (on && !ctx->plan.band_roll) ctx->band_launches += 1;
-            dv.band_lb[k] = p.short_lb[k] ? ctx->dev.max_m + kb : 2 * (ctx->dev.max_m + kb) + 1;
-        }
+    // the device config of a launch of the generic kernel: the band fields are the plan's
+    const auto with_band = [&](const BdxBandPlan &bd) {
+        BdxDevCfg dv = dev;
+        dv.dense_w = bd.dense_w;
+        dv.band_m = bd.m;
+        for (int k = 0; k < 2; ++k) dv.band_kb[k] = bd.kb[k], dv.band_lb[k] = bd.lb[k];
         return dv;
     };
     // test switch BDX_POISON: between a producer and its consumer, every element the consumer will read must have
@@ -621,7 +560,7 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const BdxBatch &b, const Bdx
         unsigned int *dbg = (unsigned int *)ctx->d_dbg.p;
         if (!with_windows || !p.windows) return list.ids ? bdx_launch_poison_check(b, list, ho, -1, 0, (check_list ? 1 : 0) | (packed ? 2 : 0), dbg) : hipSuccess;
         for (int k = 0; k < p.npass; ++k) {
-            hipError_t e = bdx_launch_poison_check(b, list, ho, k, ctx->dev.pass[k].n_barcodes, (check_list && k == 0) ? 1 : 0, dbg);
+            hipError_t e = bdx_launch_poison_check(b, list, ho, k, dev.pass[k].n_barcodes, (check_list && k == 0) ? 1 : 0, dbg);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
@@ -630,34 +569,36 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const BdxBatch &b, const Bdx
     const auto counted = [](hipError_t e, int64_t &launches) { if (e == hipSuccess) launches += 1; return e; };
     const int he = ctx->plan.hist_entries;
     const auto wave = [&](const BdxWavePlan &wp, bool filter) {
-        return counted(filter ? bdx_launch_wave(ctx->dev, wp, he, b.uncounted(), ho, no_lists) : bdx_launch_wave(ctx->dev, wp, he, b, BdxHandOver{}, front_out), ctx->wave_launches);
+        return counted(filter ? bdx_launch_wave(dev, wp, he, b.uncounted(), ho, no_lists) : bdx_launch_wave(dev, wp, he, b, BdxHandOver{}, front_out), ctx->wave_launches);
     };
     const auto pairs = [&](const BdxWavePlan &wp, const BdxDevList &in, bool filter, const BdxDevStats *st) {
-        return counted(filter ? bdx_launch_pairs(ctx->dev, wp, he, b.uncounted(), ho, over(in, none), st) : bdx_launch_pairs(ctx->dev, wp, he, b, BdxHandOver{}, over(in, mid), st),
+        return counted(filter ? bdx_launch_pairs(dev, wp, he, b.uncounted(), ho, over(in, none), st) : bdx_launch_pairs(dev, wp, he, b, BdxHandOver{}, over(in, mid), st),
                        ctx->pair_launches);
     };
-    const auto generic = [&](const BdxDevCfg &dv, const BdxTierArgs &t, long long blocks, bool last) {
+    const auto generic = [&](const BdxBandPlan &bd, const BdxTierArgs &t, long long blocks, bool last) {
         // (the call's last launch clears the other scratch half for the next call)
-        return bdx_launch_generic(dv, ctx->plan, b, ho, t, stp, blocks, last ? (uint32_t *)ctx->scratch(true)->tile_queue : nullptr);
+        const hipError_t e = bdx_launch_generic(with_band(bd), ctx->plan, b, ho, t, stp, blocks, last ? (uint32_t *)ctx->scratch(true)->tile_queue : nullptr);
+        if (e == hipSuccess) ctx->band_launches += bd.launches;
+        return e;
     };
 
     BdxDevList todo = none;  // the list the next stage walks (none: every read of the batch)
     // 1. front stage
     switch (p.front) {
         case Front::none: break;
-        case Front::bitpar: HIP_TRY(ctx, bdx_launch_bitpar(ctx->dev, ctx->plan, p.t1, bdx_seed_plan(f1, p.seed[1]), b, ho, exc, tier1)); break;
+        case Front::bitpar: HIP_TRY(ctx, bdx_launch_bitpar(dev, ctx->plan, p.t1, bdx_seed_plan(f1, p.seed[1]), b, ho, exc, tier1)); break;
         case Front::wave: HIP_TRY(ctx, wave(p.wfront, false)); break;
-        case Front::wave_win: HIP_TRY(ctx, counted(bdx_launch_wave_win(ctx->dev, p.wfront, he, b, front_out), ctx->wave_launches)); break;
+        case Front::wave_win: HIP_TRY(ctx, counted(bdx_launch_wave_win(dev, p.wfront, he, b, front_out), ctx->wave_launches)); break;
         case Front::wave_split: HIP_TRY(ctx, wave(p.wfront, true)); break;  // (the exact kernel settles and lists)
         case Front::wave_end:  // verdicts + trimmed keep range of what it settles
-            HIP_TRY(ctx, counted(bdx_launch_wave_end(ctx->dev, p.wfront, he, b, front_out, p.aln ? stp : nullptr), ctx->wave_launches));
+            HIP_TRY(ctx, counted(bdx_launch_wave_end(dev, p.wfront, he, b, front_out, p.aln ? stp : nullptr), ctx->wave_launches));
             break;
         case Front::pairs: HIP_TRY(ctx, pairs(p.wfront, none, true, nullptr)); break;
     }
     // 2. tier 1's exact launch: it answers what tier 1 settles and lists the rest (known-score / known-end configs: the filter kernel did)
     if (p.t1_exact) {
         HIP_TRY(ctx, poison_check(none, false, true));
-        HIP_TRY(ctx, generic(band_cfg(f1), tier1, p.t1_exact_blocks, false));
+        HIP_TRY(ctx, generic(p.band_t1, tier1, p.t1_exact_blocks, false));
     }
     if (p.front != Front::none) {  // tier 0 / the plain front stage's filter set walks the list
         todo = front;
@@ -681,7 +622,7 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const BdxBatch &b, const Bdx
         case Full::wave_split: HIP_TRY(ctx, wave(p.wfull, true)); break;
         case Full::bitpar: {
             const BdxTierArgs listed{todo, none, 0, {p.fused.tier_slo[0], p.fused.tier_slo[1]}};
-            HIP_TRY(ctx, bdx_launch_bitpar(ctx->dev, ctx->plan, p.fused, bdx_seed_plan(f0, p.seed[0]), b, ho, exc, p.front != Front::none ? listed : no_lists));
+            HIP_TRY(ctx, bdx_launch_bitpar(dev, ctx->plan, p.fused, bdx_seed_plan(f0, p.seed[0]), b, ho, exc, p.front != Front::none ? listed : no_lists));
             break;
         }
     }
@@ -689,21 +630,18 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const BdxBatch &b, const Bdx
     switch (p.exact) {
         case Exact::known:
             HIP_TRY(ctx, poison_check(exc, true, false));
-            HIP_TRY(ctx, generic(ctx->dev, over(exc, none), p.exact_blocks, true));
+            HIP_TRY(ctx, generic(p.band_exact, over(exc, none), p.exact_blocks, true));
             break;
         case Exact::split:
             HIP_TRY(ctx, poison_check(none, false, true));
-            HIP_TRY(ctx, generic(band_cfg(f0), no_lists, p.exact_blocks, true));
+            HIP_TRY(ctx, generic(p.band_exact, no_lists, p.exact_blocks, true));
             break;
         case Exact::split_list:  // (tiered: list mode over the reads tier 1 handed on)
             HIP_TRY(ctx, poison_check(todo, false, true));
-            HIP_TRY(ctx, generic(band_cfg(f0), over(todo, none), p.exact_blocks, true));
+            HIP_TRY(ctx, generic(p.band_exact, over(todo, none), p.exact_blocks, true));
             break;
     }
-    const int spar = ctx->scratch_par & 1;
-    // (the call's last launch is enqueued: the other half will hold zeros when the next call's kernels start)
-    ctx->scratch_clean[1 - spar] = true;
-    ctx->scratch_par = 1 - spar;
+    ctx->turn.finish_call();  // (the other half will hold zeros when the next call's kernels start)
 #ifdef BDX_TUNING
     if (ctx->tune.debug & 128) {  // tuning statistics of the fused kernel (see bdx_bitpar.hip)
             unsigned int st[4] = {0, 0, 0, 0}, tl = 0;
@@ -717,38 +655,41 @@ static int enqueue(bdx_ctx *ctx, const CallPlan &p, const BdxBatch &b, const Bdx
     return BDX_OK;
 }
 
-int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int64_t *d_seq_off, int64_t n_reads,
-                            const bdx_outputs_t *d_out) {
-    if (!ctx) return BDX_E_INVALID;
-    if (!ctx->log_host_call) ctx->launch_log.clear();
-    if (n_reads < 0) return fail(ctx, BDX_E_INVALID, "n_reads is negative");
-    if (n_reads == 0) return BDX_OK;
-    if (!d_seq_bytes || !d_seq_off || !d_out) return fail(ctx, BDX_E_INVALID, "NULL device pointer");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+}  // extern "C"
+
+// ---- one classify call: the batch's read length, the statistics tables, plan, reserve, enqueue ---------------------------------
+int bdx_classify_batch(bdx_ctx *ctx, const BdxBatchIn &in) {
+    if (!in.append_log) ctx->launch_log.clear();
+    const long long n_reads = in.n_reads;
     // the launchers note what they enqueue into this call's log (test visibility: bdx_last_launches)
     struct LogScope {
         std::string *prev;
         explicit LogScope(std::string *log) : prev(t_launch_log) { t_launch_log = log; }
         ~LogScope() { t_launch_log = prev; }
     } log_scope(&ctx->launch_log);
-    const BdxDevOut o{d_out->bc1,      d_out->bc2,      d_out->keep_start, d_out->keep_end,   d_out->pass_start,
-                      d_out->pass_end, d_out->pass_raw, d_out->pass_bc,    d_out->pass_score, d_out->pass_delta};
+    const BdxDevOut o{in.out.bc1,      in.out.bc2,      in.out.keep_start, in.out.keep_end,   in.out.pass_start,
+                      in.out.pass_end, in.out.pass_raw, in.out.pass_bc,    in.out.pass_score, in.out.pass_delta};
+    // the batch's read length (bdx_batch_len holds the rule); measured here and nowhere else: one tiny kernel, a 4-byte copy
+    // and a stream synchronisation
+    const bool window_upload = in.vlen != nullptr;
+    const auto batch_len = [&](int measured) {
+        return bdx_batch_len(window_upload ? in.known_maxlen : 0, window_upload ? 0 : in.known_maxlen, ctx->user_len_hint, ctx->dev.need_traceback != 0,
+                             ctx->fs[0].bplan.enabled != 0, measured);
+    };
+    BdxBatchLen bl = batch_len(-1);
+    if (bl.measure) {
+        int measured = 0;
+        HIP_TRY(ctx, ctx->d_maxlen.ensure(1024));
+        HIP_TRY(ctx, bdx_launch_maxlen((const long long *)in.d_off, n_reads, (int *)ctx->d_maxlen.p, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&measured, ctx->d_maxlen.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        bl = batch_len(measured < 0 ? 0 : measured);
+    }
     BdxDevStats st{};
     const BdxDevStats *stp = nullptr;
-    int measured_len = -1;
-    if (ctx->virt_maxlen > 0) {
-        measured_len = ctx->virt_maxlen;  // window upload: the host has seen every length
-    } else if (ctx->host_maxlen > 0) {
-        measured_len = ctx->host_maxlen;  // host entry point: the offsets were on the host anyway
-    } else if (ctx->dev.need_traceback) {
-        // statistics tables are sized from the batch's true maximum read length (a hint is only a hint)
-        HIP_TRY(ctx, ctx->d_maxlen.ensure(1024));
-        HIP_TRY(ctx, bdx_launch_maxlen((const long long *)d_seq_off, n_reads, (int *)ctx->d_maxlen.p, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(&measured_len, ctx->d_maxlen.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
     if (ctx->dev.need_traceback) {
-        int rc = bdx_stats_reserve(ctx, (long long)measured_len + ctx->dev.max_m + 2);
+        // (sized from the batch's true maximum read length: a hint is only a hint)
+        int rc = bdx_stats_reserve(ctx, (long long)bl.longest + ctx->dev.max_m + 2);
         if (rc != BDX_OK) return rc;
         for (int p = 0; p < 2; ++p) {
             st.pos[p] = (unsigned long long *)ctx->st_tab[p][0].p;
@@ -764,23 +705,11 @@ int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int6
         st.overflow = (unsigned int *)ctx->st_flag.p;
         stp = &st;
     }
-    int len = 0;  // the read length the filtered launches are planned for
-    if (ctx->fs[0].bplan.enabled) {
-        len = ctx->virt_maxlen > 0 ? ctx->virt_maxlen : ctx->user_len_hint;
-        if (len <= 0 && measured_len >= 0) len = measured_len > 0 ? measured_len : 1;
-        if (len <= 0) {  // measure the batch: one tiny kernel + a 4-byte copy
-            int host_len = 0;
-            HIP_TRY(ctx, bdx_launch_maxlen((const long long *)d_seq_off, n_reads, (int *)ctx->d_maxlen.p, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(&host_len, ctx->d_maxlen.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            len = host_len;
-        }
-    }
     const BdxCallEnv env{ctx->dev, ctx->plan, ctx->fs[0], ctx->fs[1], *ctx, ctx->tune, ctx->n_cu};
     BdxCallArgs args;
     args.n_reads = n_reads;
-    args.read_len = len;
-    args.window_upload = ctx->dev.vlen != nullptr;
+    args.read_len = bl.planned;
+    args.window_upload = window_upload;
     void *const vectors[10] = {o.bc1, o.bc2, o.keep_start, o.keep_end, o.pass_start, o.pass_end, o.pass_raw, o.pass_bc, o.pass_score, o.pass_delta};
     for (int i = 0; i < 10; ++i) args.wanted |= vectors[i] ? 1u << i : 0u;
     args.stats = stp != nullptr;
@@ -788,22 +717,43 @@ int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int6
     std::string why;
     int rc = bdx_plan_call(env, args, ctx->seed, p, why);
     if (rc != BDX_OK) return fail(ctx, rc, "%s", why.c_str());
-    const BdxBatch batch{d_seq_bytes, (const long long *)d_seq_off, n_reads, o, ctx->counts, ctx->stream};
+    BdxDevCfg dev = ctx->dev;  // the launches' config: what bdx_create produced + this batch's window-upload pointers
+    dev.vlen = in.vlen;
+    dev.vlo = in.vlo;
+    const BdxBatch batch{in.d_seq, (const long long *)in.d_off, n_reads, o, ctx->counts, ctx->stream};
     if (p.filtered) {
-        rc = reserve(ctx, p, n_reads);
-        if (rc == BDX_OK) rc = enqueue(ctx, p, batch, stp);
+        rc = reserve(ctx, p, n_reads, in.scratch_cleared);
+        if (rc == BDX_OK) rc = enqueue(ctx, p, dev, batch, stp);
         if (rc != BDX_OK) return rc;
         ctx->last_blocks = (n_reads + p.fused.reads_per_block - 1) / p.fused.reads_per_block;
         ctx->path = p.path;
         ctx->filter_used = bdx_seed_plan(ctx->fs[0], p.seed[0]).enabled ? BDX_FILTER_QGRAM : BDX_FILTER_BITPAR;
     } else {
-        HIP_TRY(ctx, bdx_launch_generic(ctx->dev, ctx->plan, batch, BdxHandOver{}, BdxTierArgs{}, stp, p.exact_blocks, nullptr));
+        HIP_TRY(ctx, bdx_launch_generic(dev, ctx->plan, batch, BdxHandOver{}, BdxTierArgs{}, stp, p.exact_blocks, nullptr));
         ctx->last_blocks = p.exact_blocks;
         ctx->path = "generic";
         ctx->filter_used = BDX_FILTER_OFF;
     }
     ctx->launches += 1;
     return BDX_OK;
+}
+
+extern "C" {
+
+int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int64_t *d_seq_off, int64_t n_reads,
+                            const bdx_outputs_t *d_out) {
+    if (!ctx) return BDX_E_INVALID;
+    ctx->launch_log.clear();
+    if (n_reads < 0) return fail(ctx, BDX_E_INVALID, "n_reads is negative");
+    if (n_reads == 0) return BDX_OK;
+    if (!d_seq_bytes || !d_seq_off || !d_out) return fail(ctx, BDX_E_INVALID, "NULL device pointer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BdxBatchIn in;  // (nothing known of the batch: the library measures what it needs)
+    in.d_seq = d_seq_bytes;
+    in.d_off = d_seq_off;
+    in.n_reads = n_reads;
+    in.out = *d_out;
+    return bdx_classify_batch(ctx, in);
 }
 
 int64_t bdx_counts_len(const bdx_ctx *ctx) { return ctx ? ctx->dev.n_counts : 0; }

@@ -290,6 +290,26 @@ bool grid_generic(const BdxGenericPlan &gp, long long n_reads, bool list, long l
     return true;
 }
 
+// The band fields of a launch of the generic kernel that filter set `set` hands its windows to.
+// (rolling band, barcodes beyond 32 rows: any uniform budget; the first end column is rebuilt from the hand-over row when
+// every barcode has the same length — lb is made of max_m)
+BdxBandPlan plan_band(const BdxCallEnv &env, const CallPlan &p, int set) {
+    const BdxGenericPlan &gp = env.plan;
+    BdxBandPlan bd;
+    bd.dense_w = set == 0 && p.dense_w;
+    bd.m = gp.uniform_len;
+    for (int k = 0; k < p.npass; ++k) {
+        const int kb = (set ? env.f1 : env.f0).bplan.kb_uniform[k];
+        const bool on = gp.band_roll ? (p.windows && gp.same_len && kb >= 0)
+                                     : (p.windows && gp.clean && gp.uniform_len > 0 && !env.tune.no_band && env.dev.algorithm == BDX_ALG_SEMIGLOBAL &&
+                                        kb >= 0 && kb <= 4);
+        bd.kb[k] = on ? kb : -1;
+        bd.launches += on && !gp.band_roll;
+        bd.lb[k] = p.short_lb[k] ? env.dev.max_m + kb : 2 * (env.dev.max_m + kb) + 1;
+    }
+    return bd;
+}
+
 // the stages of a filtered call, front first
 std::string call_path(const BdxSeedPlan &sp, const CallPlan &p) {
     std::string s = sp.enabled ? (sp.diag ? "qgram2+bitpar+verify" : "qgram+bitpar+verify") : "bitpar+verify";
@@ -497,6 +517,18 @@ int bdx_plan_call(const BdxCallEnv &env, const BdxCallArgs &args, BdxSeedChoice 
     wave_launch(p.full == Full::wave_split, p.wfull);
     if (!grid_generic(env.plan, n_reads, false, p.t1_exact_blocks) || !grid_generic(env.plan, n_reads, p.exact != Exact::split, p.exact_blocks))
         return fail(BDX_E_DEVICE, too_many);
+    p.band_t1 = p.band_exact = BdxBandPlan{dev.dense_w, dev.band_m, {dev.band_kb[0], dev.band_kb[1]}, {dev.band_lb[0], dev.band_lb[1]}, 0};
+    if (p.t1_exact) p.band_t1 = plan_band(env, p, 1);
+    if (p.exact != Exact::known) p.band_exact = plan_band(env, p, 0);
     p.path = call_path(sp, p);
     return BDX_OK;
+}
+
+BdxBatchLen bdx_batch_len(int window_len, int host_len, int hint, bool stats, bool filter, int measured) {
+    const int known = window_len > 0 ? window_len : host_len > 0 ? host_len : 0;
+    const bool wanted = !known && (stats || (filter && hint <= 0));
+    const int longest = known ? known : (wanted ? measured : -1);
+    int planned = 0;
+    if (filter) planned = window_len > 0 ? window_len : hint > 0 ? hint : std::max(longest, 1);
+    return BdxBatchLen{wanted && measured < 0, longest, planned};
 }

@@ -1,7 +1,8 @@
 // bdx_call.h — the per-call planner (bdx_call.cpp): which kernels one batch runs on and with which tile, queue and LDS
 // geometry, and the grid and LDS bytes of every launch (the launchers decide neither).  Host-only like bdx_plan.cpp: no HIP
-// runtime call, no device buffer, no context.  bdx_classify_device (bdx_abi.cpp) runs it once per call and launches from
-// the CallPlan it returns; tests/call_host.cpp runs it on a CPU.
+// runtime call, no device buffer, no context.  bdx_classify_batch (bdx_abi.cpp) runs it once per call and launches from
+// the CallPlan it returns; tests/call_host.cpp runs it on a CPU.  With it, host-only in the same way: the rule for a batch's
+// read length (bdx_batch_len) and the turn of the scratch halves (BdxScratchTurn).
 #pragma once
 #include <string>
 
@@ -19,7 +20,8 @@ enum class Middle { none, end, list, split, all };
 enum class Full { none, wave_split, bitpar };  // the full-budget filter (none: the pairs mode already filtered)
 enum class Exact { known, split, split_list };  // the generic kernel: over the fused kernel's hand-over list / dense / over a list
 
-// what bdx_create produced (nothing here is written by a call)
+// what bdx_create produced (nothing here is written by a call: a window upload's per-read pointers go into the call's own
+// copy of BdxDevCfg, bdx_abi.cpp)
 struct BdxCallEnv {
     const BdxDevCfg &dev;
     const BdxGenericPlan &plan;
@@ -54,6 +56,15 @@ inline BdxSeedPlan bdx_seed_plan(const BdxSetPlans &f, BdxSeedChoice c) {
     return c == BDX_SEED_MAIN ? f.splan : c == BDX_SEED_ALT ? f.splan_alt : BdxSeedPlan{};
 }
 
+// The exact kernel's diagonal-band DP (sg_core_band) for one launch of the generic kernel, as the launch's BdxDevCfg carries
+// it: clean class, every barcode of the config with the same number of rows and of the pass with the same budget, column
+// windows handed over by tracked sweeps.  launches: what the launch adds to bdx_band_launches (passes with the band on).
+struct BdxBandPlan {
+    int dense_w = 0, m = 0;
+    int kb[2] = {-1, -1}, lb[2] = {0, 0};
+    int launches = 0;
+};
+
 struct CallPlan {
     bool filtered = false;  // false: the generic kernel alone (of what is below only exact_blocks is set)
     int npass = 1, tier_len = 0, batch_len = 0;  // tier_len > 0: tiered; batch_len: the read length the launches were planned for
@@ -71,6 +82,7 @@ struct CallPlan {
     BdxBitparPlan t1{}, fused{};            // the fused kernel: tier 1 over the batch; at the full budgets (dense, or over the list)
     BdxSeedChoice seed[2] = {BDX_SEED_MAIN, BDX_SEED_MAIN};  // the seed plans t1 (seed[1]) and fused (seed[0]) were sized with
     long long t1_exact_blocks = 0, exact_blocks = 0;  // grids of the generic kernel: tier 1's exact launch, the exact stage
+    BdxBandPlan band_t1{}, band_exact{};              //   ... and their band fields (a launch without the band: the config's own)
     size_t lds_bytes = 0;  // LDS of a `fused` workgroup (fused.lds_bytes: what bdx_launch_info reports)
     std::string path;      // the stages, front first (bdx_kernel_path)
 };
@@ -78,3 +90,37 @@ struct CallPlan {
 // Plans one classify call.  seed[set] is read and may be demoted.  BDX_OK with out.filtered = false: the config has no
 // filter, or no geometry of the fused kernel fits this batch.  Otherwise the code of a refusal with its message in err.
 int bdx_plan_call(const BdxCallEnv &env, const BdxCallArgs &args, BdxSeedChoice seed[2], CallPlan &out, std::string &err);
+
+// The read length of a batch.  window_len / host_len: the longest read as a window upload / the host entry point has seen it
+// (0: not known); hint: bdx_set_read_length_hint; measured: bdx_launch_maxlen's answer, -1 before it was asked.
+//   measure  the config collects statistics, or has a filter and neither a window upload nor a hint, and nothing is known:
+//            the caller measures on the device and asks again
+//   longest  the known, else the measured longest read: the statistics tables are reserved for longest + max_m + 2 rows
+//   planned  what the filtered launches are planned for: the window upload's value, else a positive hint (also when the host
+//            knows better), else `longest` with values below 1 counted as 1; 0 without a filter
+struct BdxBatchLen {
+    bool measure;
+    int longest, planned;
+};
+BdxBatchLen bdx_batch_len(int window_len, int host_len, int hint, bool stats, bool filter, int measured = -1);
+
+// Whose turn it is with the two halves of the scratch block (BdxScratch, bdx_internal.h).  A filtered call runs on mine();
+// its last launch clears other(), which the next call then takes without a memset of its own.  A call that fails between
+// begin_call and finish_call leaves its half dirty and does not turn; an unfiltered call touches nothing.
+struct BdxScratchTurn {
+    int half = 0;
+    bool clean[2] = {false, false};  // the half is known to hold zeros when the next launch on the context's stream starts
+    int mine() const { return half; }
+    int other() const { return 1 - half; }
+    // true: this call clears mine() with a memset (cleared_by_copy: the host entry's copy kernel already did, for this call)
+    bool begin_call(bool cleared_by_copy) {
+        const bool need_memset = !cleared_by_copy && !clean[half];
+        clean[half] = false;
+        return need_memset;
+    }
+    void finish_call() {  // the call's last launch is enqueued
+        clean[other()] = true;
+        half = other();
+    }
+    void stream_changed() { clean[0] = clean[1] = false; }  // (the clearing launch ran on a stream the new one is not ordered after)
+};

@@ -11,30 +11,47 @@
 #define BDX_DFL_SCRATCH 4  // scratch buffers of the device DEFLATE encoder (bdx_deflate.hip)
 #define BDX_INF_SCRATCH 2  // scratch buffers of the device inflate (bdx_inflate.hip)
 
-struct DevBuf {
+// An allocation that frees itself: move-only, so a block has one owner (the context, or a local that retires it).
+template <hipError_t (*Free)(void *)>
+struct OwnedBlock {
     void *p = nullptr;
     size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes < 256 ? 256 : bytes;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
+    OwnedBlock() = default;
+    OwnedBlock(OwnedBlock &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    OwnedBlock &operator=(OwnedBlock &&o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
     }
+    OwnedBlock(const OwnedBlock &) = delete;
+    OwnedBlock &operator=(const OwnedBlock &) = delete;
+    ~OwnedBlock() { release(); }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) (void)Free(p);
         p = nullptr;
         cap = 0;
     }
 };
 
+struct DevBuf : OwnedBlock<hipFree> {  // device memory
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap && p) return hipSuccess;
+        release();
+        size_t want = bytes < 256 ? 256 : bytes;
+        hipError_t e = hipMalloc(&p, want);
+        if (e == hipSuccess)
+            cap = want;
+        else
+            p = nullptr;
+        return e;
+    }
+};
+
 // Page-locked host twin of DevBuf: grows to `bytes` + `slack` (room for somewhat larger calls to come)
-struct PinnedBuf {
-    void *p = nullptr;
-    size_t cap = 0;
+struct PinnedBuf : OwnedBlock<hipHostFree> {
     hipError_t ensure(size_t bytes, size_t slack) {
         if (bytes <= cap && p) return hipSuccess;
         release();
@@ -44,11 +61,6 @@ struct PinnedBuf {
         else
             p = nullptr;
         return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
     }
 };
 
@@ -94,13 +106,9 @@ struct bdx_ctx : BdxPlanChoice {  // (tiered, tier_q, tier_cap_fixed, pairs_tier
     DevBuf d_seq, d_off, d_out_i32, d_out_f64;
     // window upload (host entry point, long reads with short column windows): per-read true lengths / window starts
     DevBuf d_vlen, d_vlo;
-    int virt_maxlen = 0;     // > 0 while a window-upload batch is being classified: its longest read
-    int scratch_par = 0;             // which half of the scratch block the next classify call uses
-    bool scratch_clean[2] = {false, false};  // that half is known to hold zeros (cleared by the previous call's last launch)
-    bool scratch_zeroed = false;  // the small-batch copy kernel has already cleared the filter kernels' scratch words
+    BdxScratchTurn turn;  // which half of the scratch block the next classify call uses, and which halves hold zeros
     // the half the next classify call uses (while it runs: this call's) / other: the half the last call used, which this call's last launch clears
-    BdxScratch *scratch(bool other = false) const { return (BdxScratch *)d_maxlen.p + ((scratch_par & 1) ^ (other ? 1 : 0)); }
-    int host_maxlen = 0;     // > 0 while bdx_classify_host runs an ordinary batch: its longest read (seen on the host)
+    BdxScratch *scratch(bool other = false) const { return (BdxScratch *)d_maxlen.p + (other ? turn.other() : turn.mine()); }
     PinnedBuf h_stage;  // page-locked staging for the verdict vectors of small batches
     PinnedBuf h_in;     // page-locked staging for the bytes + offsets of small batches
     PinnedBuf h_back;   // page-locked staging for the result vectors of large batches handed over in pageable memory (download_items)
@@ -129,11 +137,27 @@ struct bdx_ctx : BdxPlanChoice {  // (tiered, tier_q, tier_cap_fixed, pairs_tier
     DevBuf dfl[BDX_DFL_SCRATCH];  // scratch of the device DEFLATE encoder (bdx_deflate.hip): chunk table, member sizes / offsets, tokens, slots
     DevBuf inf[BDX_INF_SCRATCH];  // scratch of the device inflate (bdx_inflate.hip): member table, member status
     std::string err;
-    std::string launch_log;      // the classify kernels the last classify call enqueued (bdx_last_launches)
-    bool log_host_call = false;  // a bdx_classify_host call is in progress: its device calls add to one log
+    std::string launch_log;      // the classify kernels the last classify call enqueued (bdx_last_launches; a host call: all of its device calls)
     int64_t launches = 0;
     int64_t last_blocks = 0;
 };
+
+// One batch on the device with what its caller knows of it: the value behind bdx_classify_device (which knows nothing) and
+// bdx_classify_host (bdx_host.cpp), whose facts hold for this call only.
+struct BdxBatchIn {
+    const uint8_t *d_seq = nullptr;
+    const int64_t *d_off = nullptr;
+    int64_t n_reads = 0;
+    bdx_outputs_t out{};
+    int known_maxlen = 0;  // the batch's longest read, clamped to [1, 2^30] (0: not known) — of the true reads when vlen is set
+    // window upload: d_seq / d_off hold only each read's window; per read its true length and its window's first position
+    // (BdxDevCfg::vlen / vlo of the call's launches).  Null: whole reads.
+    const int32_t *vlen = nullptr, *vlo = nullptr;
+    bool scratch_cleared = false;  // the copy kernel that brought the batch up already zeroed this call's scratch half
+    bool append_log = false;       // the call continues the launch log of a host call
+};
+// arguments checked by the callers (n_reads > 0, no null pointer, device selected)
+int bdx_classify_batch(bdx_ctx *ctx, const BdxBatchIn &in);
 
 // records the message on ctx (or as the create error when ctx is NULL) and returns `code`
 int bdx_fail(bdx_ctx *ctx, int code, const char *fmt, ...);

@@ -127,9 +127,9 @@ int download_items(bdx_ctx *ctx, const BackItems &items) {
 }
 
 // ---- host entry point: shared tail (device outputs, launch, download) and the window upload ----------
-int run_and_download(bdx_ctx *ctx, const uint8_t *d_seq, const int64_t *d_off, int64_t n_reads, const bdx_outputs_t *out,
-                     const bool mapped_outputs = false) {
-    const size_t n = (size_t)n_reads;
+// in: the batch on the device and what the host has seen of it; its outputs are set here
+int run_and_download(bdx_ctx *ctx, BdxBatchIn in, const bdx_outputs_t *out, const bool mapped_outputs = false) {
+    const size_t n = (size_t)in.n_reads;
     // Small batches (the reference hands over chunks of 4000 reads, core.jl:5-10) that want the four verdict vectors
     // only: they come back through h_stage, side by side
     const bool verdicts_only = n <= (size_t)(256 * 1024) && !out->pass_start && !out->pass_end && !out->pass_raw &&
@@ -154,8 +154,8 @@ int run_and_download(bdx_ctx *ctx, const uint8_t *d_seq, const int64_t *d_off, i
         i32 = (int32_t *)ctx->d_out_i32.p;
         f64 = (double *)ctx->d_out_f64.p;
     }
-    const bdx_outputs_t d = out_slots(*out, i32, f64, n);
-    const int rc = bdx_classify_device(ctx, d_seq, d_off, n_reads, &d);
+    const bdx_outputs_t d = in.out = out_slots(*out, i32, f64, n);
+    const int rc = bdx_classify_batch(ctx, in);
     if (rc != BDX_OK) return rc;
     if (!verdicts_only) return download_items(ctx, back_items(*out, d, n));
     // not mapped: ONE copy into h_stage and four host memcpys instead of four pageable copies with their fixed cost each
@@ -173,10 +173,10 @@ int run_and_download(bdx_ctx *ctx, const uint8_t *d_seq, const int64_t *d_off, i
 // while the kernels of the previous chunk run (one classify call per chunk on the context's stream, tied to its copy
 // by an event); the verdict vectors come back once at the end.  With pageable host memory hipMemcpyAsync returns when
 // the chunk is staged, so the launch of chunk i's kernels falls exactly between the copies of chunks i and i + 1.
-// (The longest read is known: bdx_classify_host has scanned the offsets — a device-side measurement per chunk would
-// synchronise the stream and undo the overlap.)
+// (The longest read is known, `facts` holds it: bdx_classify_host has scanned the offsets — a device-side measurement per
+// chunk would synchronise the stream and undo the overlap.)
 int classify_host_pipelined(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t *seq_off, int64_t n_reads,
-                            const bdx_outputs_t *out, int n_chunks) {
+                            const bdx_outputs_t *out, int n_chunks, BdxBatchIn facts) {
     const size_t n = (size_t)n_reads;
     const int64_t base = seq_off[0];
     const int64_t total = seq_off[n_reads] - base;
@@ -191,7 +191,7 @@ int classify_host_pipelined(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_
     int32_t *bi = (int32_t *)ctx->d_out_i32.p;
     double *bf = (double *)ctx->d_out_f64.p;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_off.p, seq_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->copy_stream));
-    const uint8_t *d_seq = (const uint8_t *)ctx->d_seq.p - base;
+    facts.d_seq = (const uint8_t *)ctx->d_seq.p - base;
     for (int c = 0; c < n_chunks; ++c) {
         // (earlier chunks take the remainder: no work buffer has to grow while kernels run)
         const size_t r0 = n / n_chunks * c + ((size_t)c < n % n_chunks ? c : n % n_chunks);
@@ -201,8 +201,10 @@ int classify_host_pipelined(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_
             HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)ctx->d_seq.p + (b0 - base), seq_bytes + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, ctx->copy_stream));
         HIP_TRY(ctx, hipEventRecord(ctx->copy_events[c], ctx->copy_stream));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->copy_events[c], 0));
-        const bdx_outputs_t d = out_slots(*out, bi, bf, n, r0);
-        const int rc = bdx_classify_device(ctx, d_seq, (const int64_t *)ctx->d_off.p + r0, (int64_t)(r1 - r0), &d);
+        facts.d_off = (const int64_t *)ctx->d_off.p + r0;
+        facts.n_reads = (int64_t)(r1 - r0);
+        facts.out = out_slots(*out, bi, bf, n, r0);
+        const int rc = bdx_classify_batch(ctx, facts);
         if (rc != BDX_OK) {
             (void)hipStreamSynchronize(ctx->copy_stream);
             return rc;
@@ -281,7 +283,7 @@ void host_union_window(const BdxDevCfg &cfg, long long n_ll, long long &ulo, lon
 
 // 1: not worth it (the caller uploads the whole reads); 0: classified through the window upload; < 0: error
 int classify_host_windows(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t *seq_off, int64_t n_reads,
-                          const bdx_outputs_t *out) {
+                          const bdx_outputs_t *out, BdxBatchIn facts) {
     if (ctx->tune.no_window_upload) return 1;
     const int64_t total = seq_off[n_reads] - seq_off[0];
     if (total < (int64_t)n_reads * 512) return 1;  // short reads: nothing to save
@@ -336,10 +338,12 @@ int classify_host_windows(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t 
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_off.p, ctx->h_coff.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_vlen.p, ctx->h_vlen.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_vlo.p, ctx->h_vlo.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
-    ctx->dev.vlen = (const int32_t *)ctx->d_vlen.p;  // (cleared again when bdx_classify_host returns)
-    ctx->dev.vlo = (const int32_t *)ctx->d_vlo.p;
-    ctx->virt_maxlen = (int)(maxlen > (1LL << 30) ? (1LL << 30) : (maxlen < 1 ? 1 : maxlen));
-    const int rc = run_and_download(ctx, (const uint8_t *)ctx->d_seq.p, (const int64_t *)ctx->d_off.p, n_reads, out);
+    facts.d_seq = (const uint8_t *)ctx->d_seq.p;
+    facts.d_off = (const int64_t *)ctx->d_off.p;
+    facts.vlen = (const int32_t *)ctx->d_vlen.p;
+    facts.vlo = (const int32_t *)ctx->d_vlo.p;
+    facts.known_maxlen = (int)(maxlen > (1LL << 30) ? (1LL << 30) : (maxlen < 1 ? 1 : maxlen));  // (of the true reads)
+    const int rc = run_and_download(ctx, facts, out);
     if (rc == BDX_OK) ctx->window_uploads += 1;
     return rc == BDX_OK ? 0 : rc;
 }
@@ -358,24 +362,18 @@ int32_t bdx_classify_host(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t 
     const int64_t base = seq_off[0];
     const int64_t total = seq_off[n_reads] - base;
     if (total < 0) return bdx_fail(ctx, BDX_E_INVALID, "seq_off is not non-decreasing");
-    // what the host has seen of this batch (the longest read; the window upload's per-read windows) is lent to the launch
-    // plan for this call only, whichever way it ends; the launch log (bdx_last_launches) spans all of its device calls
+    // what the host has seen of this batch (the longest read; the window upload's per-read windows) goes to the launch plan
+    // as a value, with the batch; the launch log (bdx_last_launches) spans all of this call's device calls
     ctx->launch_log.clear();
-    ctx->log_host_call = true;
-    struct HostFactsReset {
-        bdx_ctx *c;
-        ~HostFactsReset() {
-            c->host_maxlen = c->virt_maxlen = 0;
-            c->dev.vlen = c->dev.vlo = nullptr;
-            c->log_host_call = false;
-        }
-    } reset{ctx};
+    BdxBatchIn facts;
+    facts.n_reads = n_reads;
+    facts.append_log = true;
     {
         // Window upload: when the passes only look at a short column window of long reads (ONT-style reads with the
         // barcodes at an end, C5), copy just each read's window — the union over the passes of final_search_range
         // (+ m - 1 for :hamming / :exact), resolved exactly like the device does — instead of the whole read:
         // 10 kbp reads with "1:200" move 212 B per read over PCIe instead of 10 KB.
-        int rcw = classify_host_windows(ctx, seq_bytes, seq_off, n_reads, out);
+        int rcw = classify_host_windows(ctx, seq_bytes, seq_off, n_reads, out, facts);
         if (rcw != 1) return rcw;  // 0 done, < 0 error, 1: ordinary upload below
     }
     // The batch's longest read, for the launch plan and the statistics tables: the offsets are on the host anyway
@@ -388,7 +386,7 @@ int32_t bdx_classify_host(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t 
         bool monotone = true;
         scan_offsets(seq_off, n_reads, mx, monotone);
         if (!monotone) return bdx_fail(ctx, BDX_E_INVALID, "seq_off is not non-decreasing");
-        ctx->host_maxlen = (int)(mx > (1LL << 30) ? (1LL << 30) : (mx < 1 ? 1 : mx));
+        facts.known_maxlen = (int)(mx > (1LL << 30) ? (1LL << 30) : (mx < 1 ? 1 : mx));
     }
     if ((size_t)total + (size_t)(n_reads + 1) * 8 <= ((size_t)2 << 20)) {  // (beyond ~2 MB the extra host copy costs more than the second transfer)
         // small batches: bytes and offsets through ONE page-locked staging buffer and ONE asynchronous copy
@@ -402,11 +400,10 @@ int32_t bdx_classify_host(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t 
         HIP_TRY(ctx, hipHostGetDevicePointer(&h_in_dev, ctx->h_in.p, 0));
         const bool zero_scratch = ctx->d_maxlen.p != nullptr;  // (allocated at bdx_create when a filter is in use)
         HIP_TRY(ctx, bdx_launch_copy(ctx->d_seq.p, h_in_dev, bytes, ctx->stream, zero_scratch ? ctx->scratch()->tile_queue : nullptr, 4 * BDX_SCRATCH_WORDS));
-        ctx->scratch_zeroed = zero_scratch;
-        const int rcs = run_and_download(ctx, (const uint8_t *)ctx->d_seq.p - base, (const int64_t *)((const char *)ctx->d_seq.p + o_off),
-                                         n_reads, out, /*mapped_outputs=*/true);
-        ctx->scratch_zeroed = false;  // (also when the batch took a path that never looked at the flag)
-        return rcs;
+        facts.scratch_cleared = zero_scratch;  // (a credit for the one call below, whatever path it takes)
+        facts.d_seq = (const uint8_t *)ctx->d_seq.p - base;
+        facts.d_off = (const int64_t *)((const char *)ctx->d_seq.p + o_off);
+        return run_and_download(ctx, facts, out, /*mapped_outputs=*/true);
     }
     // (worth it when the kernels take a noticeable part of the call — tiered budgets, split mode, no filter; the
     // single fused launch of a plain known-score config is 3 ms per 10 M reads, chunking it costs more than it hides:
@@ -416,7 +413,7 @@ int32_t bdx_classify_host(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t 
     if (heavy && total >= ((int64_t)96 << 20) && n_reads >= 8 * 65536 && !ctx->tune.no_pipeline) {
         int k = (int)(total / ((int64_t)48 << 20));
         k = k < 2 ? 2 : (k > 8 ? 8 : k);
-        return classify_host_pipelined(ctx, seq_bytes, seq_off, n_reads, out, k);
+        return classify_host_pipelined(ctx, seq_bytes, seq_off, n_reads, out, k, facts);
     }
     // The offsets are uploaded as given; the byte pointer is rebased so that off[0] indexes it.
     HIP_TRY(ctx, ctx->d_seq.ensure((size_t)total + 64));
@@ -424,7 +421,9 @@ int32_t bdx_classify_host(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t 
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_seq.p, seq_bytes + base, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_off.p, seq_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     // kernel sees the byte base shifted by -base so that off[i] addresses read i
-    return run_and_download(ctx, (const uint8_t *)ctx->d_seq.p - base, (const int64_t *)ctx->d_off.p, n_reads, out);
+    facts.d_seq = (const uint8_t *)ctx->d_seq.p - base;
+    facts.d_off = (const int64_t *)ctx->d_off.p;
+    return run_and_download(ctx, facts, out);
 }
 
 // Page-locked host memory for the buffers handed to bdx_classify_host (reads, offsets, outputs): the

@@ -94,10 +94,19 @@ class AsyncCase:
         return out
 
     def hint_for(self, schedule, call):
+        """The hint the host sets before the call (bdx_set_read_length_hint): the call's own, else the schedule's longest read."""
         return call.hint if call.hint is not None else max(c.max_len for c in self.calls(schedule))
 
-    def plan_case(self, schedule, n_cu):
-        """The case as tests/call_host.cpp reads it: the same barcodes, switches and calls, the schedule twice over."""
+    def length_rows(self, schedule):
+        """Per call what bdx_batch_len (csrc/bdx_call.cpp) is asked as a host drives the device entry point: no window upload,
+        nothing seen on the host, the hint in force, and the batch's true longest read were the device to measure it.
+        (filter: as the config asks for one; a config outside every filter's domain runs the generic kernel at any length.)"""
+        return [(0, 0, self.hint_for(schedule, c), int(self.summary), int(self.filter != "off"), int(np.diff(make_batch(self, c)[1]).max()))
+                for c in self.calls(schedule)]
+
+    def plan_case(self, schedule, n_cu, planned):
+        """The case as tests/call_host.cpp reads it: the same barcodes, switches and calls, the schedule twice over.  planned: per
+        call of the schedule the read length the library plans it for (the driver's answer to length_rows)."""
         def rng(key):
             r = self.kw.get(key)
             if r is None:
@@ -109,7 +118,7 @@ class AsyncCase:
             passes.append(PC.one_pass(self.bcs2, trim=self.kw.get("trim_side2") or 0))
         tune = {KNOBS[k]: int(v) for k, v in self.env.items()}
         tune["n_cu"] = n_cu
-        calls = [CC.call(c.size, self.hint_for(schedule, c), wanted=c.mask, stats=int(self.summary)) for c in self.calls(schedule) * 2]
+        calls = [CC.call(c.size, L, wanted=c.mask, stats=int(self.summary)) for c, L in list(zip(self.calls(schedule), planned)) * 2]
         return CC.CallCase(self.name + "." + schedule, None, calls, passes=passes, rate=self.kw["max_error_rate"], min_delta=self.min_delta,
                            costs=(self.kw.get("match", 0), self.kw.get("mismatch", 1), self.kw.get("indel", 1)),
                            algorithm=ALG[self.kw.get("matching_algorithm", "semiglobal")], summary=int(self.summary),
@@ -240,11 +249,15 @@ NO_SUMMARY = [c.name for c in CASES if not c.summary]
 def predicted_paths(directory, exe=None):
     """{(case, schedule, n_cu): [path per call of the schedule run twice on one context]} from the stand-alone planner driver."""
     exe = exe or CC.build_driver(directory)
+    asked = [(c, s) for c in CASES for s in SCHEDULES]
+    rows = [c.length_rows(s) for c, s in asked]
+    answers = iter(CC.run_lengths(exe, directory, [r for per_case in rows for r in per_case]))
+    planned = {(c.name, s): [next(answers)[2] for _ in per_case] for (c, s), per_case in zip(asked, rows)}
     cases, keys = [], []
     for c in CASES:
         for s in SCHEDULES:
             for n_cu in (7, 256):
-                pc = c.plan_case(s, n_cu)
+                pc = c.plan_case(s, n_cu, planned[(c.name, s)])
                 pc.name = "%s.%s.%d" % (c.name, s, n_cu)
                 cases.append(pc)
                 keys.append((c.name, s, n_cu))

@@ -18,6 +18,7 @@ MIDDLE = ["none", "end", "list", "split", "all"]
 FULL = ["none", "wave_split", "bitpar"]
 EXACT = ["known", "split", "split_list"]
 PLAN_KEYS = "npass tier_len batch_len split windows dense_w short_lb0 short_lb1 front t1_exact middle full exact carry aln".split()
+BAND_KEYS = "dense_w m kb0 kb1 lb0 lb1 launches".split()
 FUSED_KEYS = "reads_per_block stage_bytes slot_bytes seed_span r_cap diag_nw diag_qcap lds".split()
 TILE_KEYS = "rw waves blocks span_cap hq_cap sq_cap slot cpr scan_gpr winm read_len_hint".split()
 BY_NAME = {c.name: c for c in PC.CASES}
@@ -61,6 +62,15 @@ class Report(dict):
     def tiles(self, which, c=0):
         return dict(zip(TILE_KEYS, map(int, self["c%d.%s" % (c, which)])))
 
+    def band(self, which, c=0):
+        """The band fields of tier 1's exact launch (band_t1) / the exact stage (band_exact); None: the call has no such launch."""
+        t = self.get("c%d.%s" % (c, which))
+        return None if t is None else dict(zip(BAND_KEYS, map(int, t)))
+
+    def band_launches(self, c=0):
+        """What the call adds to bdx_band_launches."""
+        return sum((self.band(w, c) or {}).get("launches", 0) for w in ("band_t1", "band_exact"))
+
     def path(self, c=0):
         return " ".join(self["c%d.path" % c])
 
@@ -97,6 +107,30 @@ def run_driver(exe, directory, cases=None, env=None, launches=False):
     assert out.returncode == 0, out.stderr[-3000:]
     assert "call driver ok: %d cases" % len(cases) in out.stdout
     return parse(out.stdout)
+
+
+def _run_lines(exe, directory, mode, lines, env=None):
+    path = os.path.join(str(directory), mode + ".txt")
+    with open(path, "w") as f:
+        f.write("".join(line + "\n" for line in lines))
+    out = subprocess.run([exe, mode, path], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    got = out.stdout.splitlines()
+    assert got[-1].endswith("driver ok: %d lines" % len(lines)) and len(got) == len(lines) + 1, got[-1]
+    return got[:-1]
+
+
+def run_lengths(exe, directory, rows, env=None):
+    """bdx_batch_len (csrc/bdx_call.cpp) for rows of (window_len, host_len, hint, stats, filter, measured): per row
+    (measure, longest, planned) — measure: the device is asked, and the other two are the answer once it said `measured`."""
+    return [tuple(map(int, ln.split())) for ln in _run_lines(exe, directory, "lengths", ["%d %d %d %d %d %d" % tuple(map(int, r)) for r in rows], env)]
+
+
+def run_scratch(exe, directory, sequences, env=None):
+    """BdxScratchTurn over event sequences (call, copy, fail, plain, stream): per sequence, per event (memset, mine, other);
+    memset None: the event begins no call."""
+    return [[(None if a == "-" else int(a), int(b), int(c)) for a, b, c in (ev.split(":") for ev in ln.split())]
+            for ln in _run_lines(exe, directory, "scratch", [" ".join(seq) for seq in sequences], env)]
 
 
 def parse(stdout):

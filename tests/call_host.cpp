@@ -9,6 +9,11 @@
 //   call_host CASES [REPEAT | launches]
 //     REPEAT > 0: also prints the mean host time of one bdx_plan_call per case on stderr (ns, not compared)
 //     launches: also prints the launches every plan holds (report_launches), for the golden file and the comparison with bdx_last_launches
+//   call_host lengths FILE   bdx_batch_len's answers, one line per line `WINDOW_LEN HOST_LEN HINT STATS FILTER MEASURED` of FILE:
+//                            `measure longest planned` (measure 1: asked again with MEASURED, whose answer the other two are)
+//   call_host scratch FILE   BdxScratchTurn over the events of every line of FILE (call, copy: a call whose scratch the copy kernel
+//                            cleared, fail: a call that never finishes, plain: an unfiltered call, stream: a stream switch); per
+//                            event `memset:mine:other` (memset -: the event begins no call)
 //
 // (diag_nw / diag_qcap are reported for a launch whose seed plan is the two-intact-pieces index; nothing else reads them)
 #include <algorithm>
@@ -59,6 +64,7 @@ static void report_tiles(const char *key, const BdxWavePlan &w) {
 // c<i>.plan: npass tier_len batch_len split windows dense_w short_lb[2] front t1_exact middle full exact carry aln
 // c<i>.fused / .t1: reads_per_block stage_bytes slot_bytes seed_span r_cap diag_nw diag_qcap LDS bytes
 // c<i>.wfront / .wmid / .wfull: rw waves blocks span_cap hq_cap sq_cap slot cpr scan_gpr winm read_len_hint
+// c<i>.band_t1 / .band_exact: dense_w band_m band_kb[2] band_lb[2] of tier 1's exact launch / the exact stage, and what the launch adds to bdx_band_launches
 // c<i>.seed: per set 0: the set's own seed plan, 1: the weak single seeds kept beside it, 2: no seeds
 static void report_call(int i, int rc, const std::string &err, const CallPlan &p, const BdxPlanOut &po, const BdxSeedChoice seed[2]) {
     char key[32];
@@ -81,6 +87,11 @@ static void report_call(int i, int rc, const std::string &err, const CallPlan &p
         }
         if (p.middle != Middle::none) report_tiles(k("wmid"), p.wmid);
         if (p.full == Full::wave_split) report_tiles(k("wfull"), p.wfull);
+        const auto band = [&](const char *field, const BdxBandPlan &b) {
+            printf("%s %d %d %d %d %d %d %d\n", k(field), b.dense_w, b.m, b.kb[0], b.kb[1], b.lb[0], b.lb[1], b.launches);
+        };
+        if (p.t1_exact) band("band_t1", p.band_t1);
+        band("band_exact", p.band_exact);
     }
     int eff[2];
     for (int s = 0; s < 2; ++s) eff[s] = bdx_seed_plan(po.fs[s], seed[s]).enabled ? (int)seed[s] : (int)BDX_SEED_NONE;
@@ -168,10 +179,56 @@ static void run_case(const Case &cs, int repeat, bool launches) {
     }
 }
 
+static int run_lengths(FILE *f) {
+    int w, h, hint, stats, filter, measured, n = 0;
+    while (fscanf(f, "%d %d %d %d %d %d", &w, &h, &hint, &stats, &filter, &measured) == 6) {
+        BdxBatchLen a = bdx_batch_len(w, h, hint, stats != 0, filter != 0);
+        const bool measure = a.measure;
+        if (measure) a = bdx_batch_len(w, h, hint, stats != 0, filter != 0, measured);
+        if (a.measure) return 4;  // (asked twice)
+        printf("%d %d %d\n", (int)measure, a.longest, a.planned);
+        ++n;
+    }
+    printf("length driver ok: %d lines\n", n);
+    return 0;
+}
+
+static int run_scratch(FILE *f) {
+    char line[4096];
+    int n = 0;
+    while (fgets(line, sizeof line, f)) {
+        BdxScratchTurn t;
+        std::string out;
+        for (char *ev = strtok(line, " \n"); ev; ev = strtok(nullptr, " \n")) {
+            const std::string e = ev;
+            char memset_needed = '-';
+            if (e == "call" || e == "copy" || e == "fail") {
+                memset_needed = t.begin_call(e == "copy") ? '1' : '0';
+                if (e != "fail") t.finish_call();
+            } else if (e == "stream") {
+                t.stream_changed();
+            } else if (e != "plain") {
+                return 4;
+            }
+            out += (out.empty() ? "" : " ") + std::string(1, memset_needed) + ":" + std::to_string(t.mine()) + ":" + std::to_string(t.other());
+        }
+        printf("%s\n", out.c_str());
+        ++n;
+    }
+    printf("scratch driver ok: %d lines\n", n);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2 || argc > 3) return 2;
-    FILE *f = fopen(argv[1], "r");
-    if (!f) { fprintf(stderr, "cannot open %s\n", argv[1]); return 3; }
+    const bool lengths = argc == 3 && !strcmp(argv[1], "lengths"), scratch = argc == 3 && !strcmp(argv[1], "scratch");
+    FILE *f = fopen(argv[lengths || scratch ? 2 : 1], "r");
+    if (!f) { fprintf(stderr, "cannot open %s\n", argv[lengths || scratch ? 2 : 1]); return 3; }
+    if (lengths || scratch) {
+        const int rc = lengths ? run_lengths(f) : run_scratch(f);
+        fclose(f);
+        return rc;
+    }
     const bool launches = argc == 3 && !strcmp(argv[2], "launches");
     const int repeat = argc == 3 && !launches ? atoi(argv[2]) : 0;
     Case cs;

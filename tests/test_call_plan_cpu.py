@@ -7,7 +7,14 @@ there the parent handed a dense request the slot-mode geometry the call before h
 golden file holds the parent's value with that history and on a fresh context, and the latter is asserted.  The launch lines
 (c<i>.launch<j>: the grid, block size, tile and list flag of every classify kernel) were recorded from the commit before the
 planner took the grids over from the launchers, whose formulas that commit's driver restated.  The same driver then runs under
-ASan / UBSan (no Python process loads sanitised code)."""
+ASan / UBSan (no Python process loads sanitised code).  The band fields (c<i>.band_t1 / .band_exact) were recorded before the
+planner held them, from that commit's band_cfg formula (enqueue, bdx_abi.cpp) in a scratch copy of this driver fed from that
+commit's plans.
+
+The same driver answers for the two other host-only pieces of a call: the read length of a batch (bdx_batch_len), held against
+the rule written out below over its whole input lattice, and the turn of the scratch halves (BdxScratchTurn), held against
+event sequences."""
+import itertools
 import json
 
 import pytest
@@ -72,7 +79,88 @@ def test_call_plan_equals_the_golden_file(reports, golden, case):
     assert reports[0][case.name].flat() == want
 
 
+def test_band_fields_are_reported_for_every_exact_launch(reports):
+    seen = set()
+    for case in CC.CASES:
+        r = reports[0][case.name]
+        for c in range(len(case.calls)):
+            if r.i("c%d.rc" % c) != 0 or not r.i("c%d.filtered" % c):
+                assert r.band("band_exact", c) is None and r.band_launches(c) == 0
+                continue
+            p, t1, ex = r.plan(c), r.band("band_t1", c), r.band("band_exact", c)
+            assert (t1 is not None) == bool(p["t1_exact"]) and ex is not None
+            for b, dense in ((t1, 0), (ex, p["dense_w"] if p["exact"] != "known" else 0)):
+                if b is not None:
+                    assert b["dense_w"] == dense and 0 <= b["launches"] <= sum(k >= 0 for k in (b["kb0"], b["kb1"])) <= p["npass"]
+            if p["exact"] == "known":  # no hand-over of windows: the config's own fields
+                assert ex == dict(dense_w=0, m=0, kb0=-1, kb1=-1, lb0=0, lb1=0, launches=0)
+            seen.add((t1 or ex)["launches"])
+    assert {0, 1, 2} <= seen  # no band, one pass, both passes of a dual config
+
+
+# ---- the read length of a batch ---------------------------------------------------------------------------------------------
+LENGTH_ROWS = list(itertools.product((0, 1, 212), (0, 1, 150), (0, -5, 100, 313), (1, 0), (1, 0), (0, 1, 150)))
+
+
+def length_rule(window_len, host_len, hint, stats, filt, measured):
+    """The rule, written out (not the function under test): (measure, longest, planned)."""
+    known = window_len if window_len > 0 else host_len if host_len > 0 else None
+    measure = (bool(stats) and known is None) or (bool(filt) and window_len <= 0 and hint <= 0 and known is None)
+    longest = known if known is not None else measured if measure else None  # the statistics tables: longest + max_m + 2 rows
+    if not filt:
+        planned = 0  # with the filter off, no length is planned
+    elif window_len > 0:
+        planned = window_len
+    elif hint > 0:
+        planned = hint  # also when the host entry knows the true longest read
+    else:
+        planned = max(longest, 1)
+    return int(measure), -1 if longest is None else longest, planned
+
+
+def test_length_rule_over_its_lattice(reports):
+    assert len(LENGTH_ROWS) == 3 * 3 * 4 * 2 * 2 * 3
+    got = CC.run_lengths(str(reports[1] / "call_host"), reports[1], LENGTH_ROWS)
+    want = [length_rule(*row) for row in LENGTH_ROWS]
+    for row, g, w in zip(LENGTH_ROWS, got, want):
+        assert g == w, (row, g, w)
+    # the lattice reaches every branch: measured for the statistics alone, for the plan alone, for both; all three sources of the plan
+    assert {(0, 0, 100, 1, 1, 150), (0, 0, 0, 0, 1, 150), (0, 0, -5, 1, 1, 0)} <= {r for r, w in zip(LENGTH_ROWS, want) if w[0]}
+    assert {w[2] for r, w in zip(LENGTH_ROWS, want) if r[4]} == {1, 100, 150, 212, 313} and {w[2] for r, w in zip(LENGTH_ROWS, want) if not r[4]} == {0}
+
+
+# ---- the scratch halves -------------------------------------------------------------------------------------------------------
+# (events, per event: memset needed (None: the event begins no call), the half the next call takes, the other one)
+SCRATCH = [
+    (("call", "call"), [(1, 1, 0), (0, 0, 1)]),  # the first call clears its half, its last launch the second call's
+    (("call", "fail", "call"), [(1, 1, 0), (0, 1, 0), (1, 0, 1)]),  # the failed call took the clean half and did not turn: the next clears it again
+    (("call", "stream", "call"), [(1, 1, 0), (None, 1, 0), (1, 0, 1)]),
+    (("copy",), [(0, 1, 0)]),  # the copy kernel cleared this call's half
+    (("copy", "call"), [(0, 1, 0), (0, 0, 1)]),  # ... and the next call is judged by the clean flag alone: clean
+    (("copy", "stream", "call"), [(0, 1, 0), (None, 1, 0), (1, 0, 1)]),  # ... not clean: no credit is left over
+    (("call", "plain", "call"), [(1, 1, 0), (None, 1, 0), (0, 0, 1)]),  # an unfiltered call changes nothing
+    (("plain", "call", "plain", "plain", "call"), [(None, 0, 1), (1, 1, 0), (None, 1, 0), (None, 1, 0), (0, 0, 1)]),
+    (("fail", "fail", "call", "call"), [(1, 0, 1), (1, 0, 1), (1, 1, 0), (0, 0, 1)]),
+]
+
+
+def test_scratch_turn_sequences(reports):
+    got = CC.run_scratch(str(reports[1] / "call_host"), reports[1], [s for s, _ in SCRATCH])
+    for (events, want), g in zip(SCRATCH, got):
+        assert g == want, (events, g)
+        # other() after a finished call is the half that call used
+        mine = 0
+        for ev, (_, now, other) in zip(events, g):
+            if ev in ("call", "copy"):
+                assert other == mine and now == 1 - mine, events
+            else:
+                assert now == mine, events
+            mine = now
+
+
 def test_call_planner_under_asan_ubsan(tmp_path):
     exe = CC.build_driver(tmp_path, flags=SAN)
     got = CC.run_driver(exe, tmp_path, env=ENV, launches=True)
     assert len(got) == len(CC.CASES)
+    assert CC.run_lengths(exe, tmp_path, LENGTH_ROWS, env=ENV) == [length_rule(*row) for row in LENGTH_ROWS]
+    assert CC.run_scratch(exe, tmp_path, [s for s, _ in SCRATCH], env=ENV) == [w for _, w in SCRATCH]

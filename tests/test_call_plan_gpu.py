@@ -4,7 +4,8 @@ sequence on one context (313 bases, then 150) and a call that wants the per-pass
 device's own compute-unit count, the fused kernel under a forced grid (BDX_GRID below and above its tile count) and a config
 outside the filters' domain (the generic kernel alone).  For every call bdx_kernel_path and every line of bdx_last_launches (family, blocks, threads,
 tile, list flag and the template arguments the plan decides) equal what tests/call_host.cpp, built and run here with the same
-switches and n_cu, predicts from csrc/bdx_call.cpp alone; the verdicts equal the oracle."""
+switches and n_cu, predicts from csrc/bdx_call.cpp alone, and bdx_band_launches advances by the count the plan states; the
+verdicts equal the oracle."""
 import ctypes
 import os
 
@@ -108,6 +109,7 @@ def test_the_library_launches_the_planned_call(name, driver, monkeypatch):
             second = dict(second=(B4B, L - 50, L - 24)) if dual else {}
             seq, off, _ = synth.make_reads(B4A if dual else B1, n, L, seed=77 + c, **second)
             assert int((off[1:] - off[:-1]).max()) == L
+            band_before = hc.band_launches
             got = hc.classify(seq, off)
             launches = hc.last_launches
             what = f"{name} call {c} [{hc.kernel_path}] {launches}"
@@ -124,6 +126,8 @@ def test_the_library_launches_the_planned_call(name, driver, monkeypatch):
                     assert a["BS"] == p["args"][0], f"{what}: planned {p}"
                 else:
                     assert (a["RW"], int(a["SPLIT"]), a["KEND"], int(a["WINM"])) == p["args"][:4] and (a["KB"] > 0) == (p["family"] == "pairs"), f"{what}: planned {p}"
+            # the diagonal-band DP of the exact kernel: counted where its launch is made, by what the plan states
+            assert hc.band_launches - band_before == want.band_launches(c), f"{what}: planned {want.band('band_t1', c)} {want.band('band_exact', c)}"
             if "BDX_GRID" in env:  # as forced, but never more workgroups than tiles
                 fused = [ln for ln in launches if ln["family"] == "bitpar"]
                 assert fused and all(ln["blocks"] == min(int(env["BDX_GRID"]), -(-n // ln["tile"])) for ln in fused), what
