@@ -38,6 +38,7 @@
 #include <cstdlib>
 
 #include "bdx_core.h"
+#include "bdx_sweep_col.h"
 
 // a launcher that refuses its plan says where (stderr, only with BDX_TRACE_LAUNCH set: developer aid)
 #define BDX_BAD_PLAN() (getenv("BDX_TRACE_LAUNCH") ? (void)fprintf(stderr, "[bdx] launch refused at %s:%d\n", __FILE__, __LINE__) : (void)0, hipErrorInvalidValue)
@@ -187,31 +188,6 @@ __device__ __forceinline__ void pack16(const u32x4 v, uint32_t &p2, uint32_t &nl
     p2 = lo | hi;
 }
 
-// One column of Myers' recurrence on a top-aligned pattern (bdx_bitpar.hip `step`); TRACK: the horizontal delta
-// of the barcode's last row is the carry-out of the shift and updates the score.
-template <bool TRACK>
-__device__ __forceinline__ uint32_t sweep_step(const uint32_t Eq, uint32_t &Pv, uint32_t &Mv, int &score, int &best) {
-    const uint32_t Xv = Eq | Mv;
-    const uint32_t ep = Eq & Pv;  // (returned: its top bit is the known-start class's "the diagonal move into the last row is optimal")
-    const uint32_t Xh = ((ep + Pv) ^ Pv) | Eq;
-    uint32_t Ph = Mv | ~(Xh | Pv);
-    uint32_t Mh = Pv & Xh;
-    if (TRACK) {
-        uint32_t cp, cm;
-        Ph = __builtin_addc(Ph, Ph, 0u, &cp);
-        Mh = __builtin_addc(Mh, Mh, 0u, &cm);
-        score += (int)cp;
-        score -= (int)cm;
-    } else {
-        Ph = Ph + Ph;
-        Mh = Mh + Mh;
-    }
-    Pv = Mh | ~(Xv | Ph);
-    Mv = Ph & Xv;
-    if (TRACK) best = score < best ? score : best;
-    return ep;
-}
-
 // 32 columns of one sweep; columns [0, TF) cannot end an alignment within any barcode's budget (the score after
 // j + 1 columns is >= m - (j + 1)), so the score is first needed at column TF, where it is popcount(Pv) -
 // popcount(Mv): D[m][j] = D[0][j] + the vertical deltas, D[0][j] = 0 (free start), the virtual rows below the
@@ -248,9 +224,11 @@ __device__ __forceinline__ int wave_cols(const int rem) {
 // bit of Eq & Pv BEFORE the step: "the barcode's last row matches this column and its vertical delta was +1", i.e. the
 // diagonal move into the last row attains the column's value (needed by the reversed sweeps of trim_side = 3 passes, see
 // sweep_lane: there the last row is the barcode's FIRST base).
-// COLS: `nc` (wave-uniform, 1..32) is the number of columns some lane still needs and the block stops there, after any
-// column, with a scalar branch (the loads of a group of eight stay whole); else `nc` counts the groups of eight columns
-// some lane still needs (1..4) and the block stops between groups.
+// COLS (the kernel's LEAN forms): `nc` (wave-uniform, 1..32) is the number of columns some lane still needs and the block
+// stops there, after any column, with a scalar branch (the loads of a group of eight stay whole); else `nc` counts the
+// groups of eight columns some lane still needs (1..4) and the block stops between groups.  COLS also selects the column
+// code of bdx_sweep_col.h: byte-field addresses and, in the untracked columns, doublings as adds; every other form keeps
+// the bit-field address and the shifts (they sit at the register limit).
 template <int TF, int TRACKW, bool COLS>
 __device__ __forceinline__ void sweep_block(const uint32_t A0, const uint32_t A1, const uint32_t A2, const uint32_t A3,
                                             const uint32_t pbase, uint32_t &Pv, uint32_t &Mv, int &score, int &best, const int kk1,
@@ -258,10 +236,22 @@ __device__ __forceinline__ void sweep_block(const uint32_t A0, const uint32_t A1
     const int ngr = COLS ? (nc + 7) >> 3 : nc;
     const uint32_t A[4] = {A0, A1, A2, A3};
     uint32_t Eq[2][8];
+    uint32_t fmask = BDX_COL_FIELD_MASK;
+    if (COLS) asm("" : "+v"(fmask));  // (in a register: a literal is the dearer operand class)
     const auto issue = [&](const int h) __attribute__((always_inline)) {
         uint32_t addr[8];
+        if (COLS) {
+            // the group's codes as byte fields of 4 x code; behind the fence the compiler keeps the fields and adds each to
+            // the base with a byte-select add, one instruction per column
+            uint32_t ev, od;
+            bdx_col_fields(A[h], fmask, ev, od);
+            asm volatile("" : "+v"(ev), "+v"(od));
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) addr[jj] = pbase + (__builtin_amdgcn_ubfe(A[h], 4 * jj, 3) << 2);
+            for (int jj = 0; jj < 8; ++jj) addr[jj] = pbase + bdx_col_field(ev, od, jj);
+        } else {
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) addr[jj] = pbase + (__builtin_amdgcn_ubfe(A[h], 4 * jj, 3) << 2);
+        }
         lds_read8(Eq[h & 1], addr);
     };
     issue(0);
@@ -277,11 +267,11 @@ __device__ __forceinline__ void sweep_block(const uint32_t A0, const uint32_t A1
             const int j = 8 * h + jj;
             if (COLS && jj > 0 && j >= nc) break;  // (wave-uniform: the group's remaining columns are junk in every lane)
             if (j < TF) {
-                sweep_step<false>(Eq[h & 1][jj], Pv, Mv, score, best);
+                sweep_step<false, COLS>(Eq[h & 1][jj], Pv, Mv, score, best);
             } else {
                 if (j == TF && TF > 0) score = __builtin_popcount(Pv) - __builtin_popcount(Mv);
                 const int best_before = best;
-                const uint32_t ep = sweep_step<true>(Eq[h & 1][jj], Pv, Mv, score, best);
+                const uint32_t ep = sweep_step<true, COLS>(Eq[h & 1][jj], Pv, Mv, score, best);
                 if (TRACKW == 1) inm = __builtin_amdgcn_alignbit(inm, (uint32_t)(score - kk1), 31);  // (inm << 1) | (score <= budget)
                 if (TRACKW >= 2) inm = __builtin_amdgcn_alignbit(inm, (uint32_t)(score - best_before), 31);  // (inm << 1) | (score < minimum so far)
                 if (TRACKW >= 3) inm2 = __builtin_amdgcn_alignbit(inm2, ep, 31);

@@ -51,7 +51,15 @@
     F(38, "v_lshrrev_b64 x2,3,x2", "v_lshrrev_b64 %3, 3, %3", 1)                                          \
     F(39, "v_and_b32 x,x,s (sgpr)", "v_and_b32 %0, %4, %0", 1)                                            \
     F(40, "v_dot4_u32_u8 x,x,b,c (vgpr weights)", "v_dot4_u32_u8 %0, %0, %1, %2", 1)                      \
-    F(41, "v_dot4_u32_u8 x,x,s,c (sgpr weights)", "v_dot4_u32_u8 %0, %0, %4, %2", 1)
+    F(41, "v_dot4_u32_u8 x,x,s,c (sgpr weights)", "v_dot4_u32_u8 %0, %0, %4, %2", 1)                     \
+    F(42, "v_add_u32_sdwa x,b,x src0_sel:BYTE_1", "v_add_u32_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD", 1) \
+    F(43, "v_add_u32_sdwa x,b,x src0_sel:BYTE_3", "v_add_u32_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD", 1) \
+    F(44, "v_ashrrev_i32 x,31,x", "v_ashrrev_i32 %0, 31, %0", 1)                                          \
+    F(45, "v_lshrrev_b32 x,31,x", "v_lshrrev_b32 %0, 31, %0", 1)                                          \
+    F(46, "v_add_u32 x,x,x", "v_add_u32 %0, %0, %0", 1)                                                   \
+    F(47, "v_lshlrev_b32 x,1,x (again, next to row 46)", "v_lshlrev_b32 %0, 1, %0", 1)                    \
+    F(48, "v_and_b32 x,x,28 + v_add_u32 x,x,b", "v_and_b32 %0, 28, %0\n\tv_add_u32 %0, %0, %1", 2)
+// (v_add3_u32 is row 32; rows 42 / 43: the sweeps' column address, rows 44 .. 47: their score update and doublings)
 // (no row with literal weights: gfx950's VOP3P encoding takes no literal operand, the assembler refuses it; the compiler
 // moves such a constant into an SGPR, which is row 41)
 
