@@ -101,7 +101,8 @@ static void report_call(int i, int rc, const std::string &err, const CallPlan &p
 // The launches a plan holds, one line per classify kernel in the order of the stages: family, then blocks, threads, tile and
 // list flag as the plan states them (the launchers take the grid from the plan; tests/golden/call_plans.json holds these lines
 // as the launchers of the commit before computed them), then the template arguments the plan decides
-//   bitpar: R SEED DIAG NW WL | wave, pairs: RW SPLIT KEND WINM | generic: BS
+//   bitpar: R SEED DIAG NW WL | wave, pairs: RW SPLIT KEND WINM | generic: BS reg_rows clean uniform_m band_roll (the ladder of
+//   bdx_launch_generic spells the instantiation from these: tests/kernel_lattice.py generic_name)
 static void report_launches(int i, const CallPlan &p, const BdxPlanOut &po) {
     int j = 0;
     const auto line = [&](const char *family, long long blocks, int threads, int tile, int list, int a, int b, int c, int d, int e) {
@@ -115,7 +116,9 @@ static void report_launches(int i, const CallPlan &p, const BdxPlanOut &po) {
     };
     const auto wave = [&](const BdxWavePlan &w) { line("wave", w.grid, 64 * w.waves, w.rw, 0, w.rw, w.split, w.kend, w.winm, 0); };
     const auto pairs = [&](const BdxWavePlan &w, int list) { line("pairs", w.grid, 64 * w.waves, 16, list, 16, w.split, w.kend, 0, 0); };
-    const auto generic = [&](long long blocks, int list) { line("generic", blocks, po.plan.threads, po.plan.threads, list, po.plan.threads, 0, 0, 0, 0); };
+    const auto generic = [&](long long blocks, int list) {
+        line("generic", blocks, po.plan.threads, po.plan.threads, list, po.plan.threads, po.plan.reg_rows, po.plan.clean, po.plan.uniform_m, po.plan.band_roll);
+    };
     if (!p.filtered) return generic(p.exact_blocks, 0);
     if (p.front == Front::bitpar) fused(1, p.t1, 0);
     else if (p.front == Front::pairs) pairs(p.wfront, 0);
