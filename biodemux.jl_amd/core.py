@@ -23,6 +23,7 @@ from .config import DemuxConfig, build_config
 from .fileio import read_fastq
 from . import deviceio, nativeio
 from .hipabi import HipClassifier, load_library
+from .outputs import OutputLayout
 from .reporting import canonical_duration, generate_summary_report
 
 _PREFIX_RE = re.compile(r"\.fastq(\.gz)?$")
@@ -82,12 +83,12 @@ def _log(msg: str):
 
 
 def _demux(fastq1: str, fastq2: Optional[str], config: DemuxConfig, output_directory: str, prefix1: str,
-           prefix2: str, classifier, batch_reads: int, on_batch=None, batches_per_device: Optional[list] = None) -> None:
-    """``classifier`` may be a list of N classifiers: batch k then goes to classifier k % N, one batch at a time (the
-    plain statement of what nativeio's dealer does with threads); ``batches_per_device`` receives the counts."""
+           prefix2: str, classifiers: list, batch_reads: int, on_batch=None,
+           batches_per_device: Optional[list] = None) -> None:
+    """Batch k goes to classifier k % N of the N ``classifiers``, one batch at a time (the plain statement of what
+    nativeio's dealer does with threads); ``batches_per_device`` receives the counts."""
     writer = _Writer(output_directory, config)
-    do_trim = config.trim_side is not None or config.trim_side2 is not None  # core.jl:240
-    classifiers = list(classifier) if isinstance(classifier, (list, tuple)) else [classifier]
+    streams = OutputLayout(config, output_directory, prefix1, prefix2, fastq2 is not None).streams
     dealt = [0] * len(classifiers)
 
     def flush(r1: List[list], r2: Optional[List[list]]):
@@ -105,22 +106,20 @@ def _demux(fastq1: str, fastq2: Optional[str], config: DemuxConfig, output_direc
         bc1, bc2, ks, ke = out["bc1"], out["bc2"], out["keep_start"], out["keep_end"]
         for i, (h1, s1, p1, q1) in enumerate(r1):
             filename = filename_for(config, int(bc1[i]), int(bc2[i]))
-            if do_trim and ks[i] != -1:  # core.jl:250-254, :162-173
-                a = max(int(ks[i]), 1)
-                b = min(int(ke[i]), len(s1))
-                if a <= b:
-                    s1 = s1[a - 1:b]
-                    q1 = q1[a - 1:b]
-                else:
-                    s1 = b""
-                    q1 = b""
-            if config.classify_both and r2 is not None:  # core.jl:175-185
-                writer.write_entry(prefix1 + "." + filename, h1, s1, p1, q1)
-                writer.write_entry(prefix2 + "." + filename, *r2[i])
-            elif r2 is not None:  # core.jl:186-190
-                writer.write_entry(prefix2 + "." + filename, *r2[i])
-            else:  # core.jl:191-196
-                writer.write_entry(prefix1 + "." + filename, h1, s1, p1, q1)
+            for src, prefix, trim in streams:  # core.jl:175-196
+                if src == 1:
+                    writer.write_entry(prefix + "." + filename, *r2[i])
+                    continue
+                if trim and ks[i] != -1:  # core.jl:250-254, :162-173
+                    a = max(int(ks[i]), 1)
+                    b = min(int(ke[i]), len(s1))
+                    if a <= b:
+                        s1 = s1[a - 1:b]
+                        q1 = q1[a - 1:b]
+                    else:
+                        s1 = b""
+                        q1 = b""
+                writer.write_entry(prefix + "." + filename, h1, s1, p1, q1)
 
     try:
         with read_fastq(fastq1) as io1:
@@ -296,14 +295,10 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         raise ValueError("_io='device': the device FASTQ pipeline needs the HIP classifier (no _classifier_factory)")
     # summary=true: the HIP classifier collects the histograms of classification.jl:827-865 on the device
     # (bdx_get_stats); a test-injected classifier without such tables hands over per-pass outputs instead
-    if multi:
-        classifiers = _open_classifiers(config, devs, _classifier_factory)
-        classifier = classifiers[0]
-    else:
-        classifier = _classifier_factory(config) if _classifier_factory else HipClassifier(config, device=devs[0])
+    classifiers = _open_classifiers(config, devs, _classifier_factory)
     if _timings is not None:  # barcode table + device context: before the first batch can move
         _timings["setup_s"] = (_dt.datetime.now() - start_time).total_seconds()
-    device_stats = hasattr(classifier, "stats_tables")
+    device_stats = hasattr(classifiers[0], "stats_tables")
     hist = DemuxStats() if (config.summary and not device_stats) else None
 
     def on_batch(out):
@@ -317,37 +312,29 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         if _timings is not None:
             _timings["pre_s"] = (_dt.datetime.now() - start_time).total_seconds()  # everything before the first batch can be read
         if _io == "device":
-            deviceio.demux_device(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifier, _batch_reads,
+            deviceio.demux_device(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers[0], _batch_reads,
                                   _timings, gzip_device=_gzip == "device", gunzip_device=_gunzip == "device")
         elif use_native:
             t_call = _dt.datetime.now()
-            nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2,
-                                  classifiers if multi else classifier, _batch_reads, on_batch, _timings)
+            nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers, _batch_reads,
+                                  on_batch, _timings)
             if _timings is not None:  # (beyond the pipeline's own wall clock: releasing its batch buffers)
                 _timings["native_call_s"] = (_dt.datetime.now() - t_call).total_seconds()
-        elif multi:
+        else:
             dealt: List[int] = []
             _demux(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers, _batch_reads, on_batch,
                    dealt)
-            if _timings is not None:
+            if multi and _timings is not None:
                 _timings["batches_per_device"] = dealt
-        else:
-            _demux(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifier, _batch_reads, on_batch)
-        if multi:  # merge_stats (reporting.jl:1-9) over the contexts: a host sum of a few KB, no collective
-            counts = np.sum([np.asarray(c.counts, dtype=np.int64) for c in classifiers], axis=0)
-            tables = (merge_stats_tables([c.stats_tables() for c in classifiers]) if (config.summary and device_stats)
-                      else None)
-            if _timings is not None:
-                _timings["devices"] = list(devs)
-        else:
-            counts = np.asarray(classifier.counts)
-            tables = classifier.stats_tables() if (config.summary and device_stats) else None
+        # merge_stats (reporting.jl:1-9) over the contexts: a host sum of a few KB, no collective
+        counts = np.sum([np.asarray(c.counts, dtype=np.int64) for c in classifiers], axis=0)
+        tables = (merge_stats_tables([c.stats_tables() for c in classifiers]) if (config.summary and device_stats)
+                  else None)
+        if multi and _timings is not None:
+            _timings["devices"] = list(devs)
     finally:
         t_close = _dt.datetime.now()
-        if multi:
-            _close_all(classifiers)
-        else:
-            classifier.close()
+        _close_all(classifiers)
         if _timings is not None:  # releasing the device context (staging buffers, tables)
             _timings["close_s"] = (_dt.datetime.now() - t_close).total_seconds()
 

@@ -33,8 +33,8 @@ from typing import Optional
 import numpy as np
 
 from . import nativeio
-from .classification import filename_for
 from .hipabi import BdxError, pinned_empty
+from .outputs import OutputLayout
 
 _H2D, _D2H = 1, 2  # hipMemcpyKind
 _NONBLOCKING = 1   # hipStreamNonBlocking
@@ -149,10 +149,13 @@ def check_gunzip_inputs(paths, lib) -> None:
 
 class _Input:
     """One FASTQ input: its host bytes (mapped, or inflated in the background; or, for the device inflate, the mapped
-    COMPRESSED members and their table) and its device side (two byte windows, the line table of the current batch)."""
+    COMPRESSED members and their table) and its device side (two byte windows, the line table of the current batch).
+    ``io_lib`` is libbdx_io.so, ``classifier`` the context whose stream the inflate and the index run on, ``busy`` the
+    run's counters."""
 
-    def __init__(self, path: str, rt: _Runtime, batch_reads: int, members=None):
+    def __init__(self, path: str, rt: _Runtime, io_lib, classifier, busy: dict, batch_reads: int, members=None):
         self.path = path
+        self.rt, self.L, self.cl, self.busy, self.batch_reads = rt, io_lib, classifier, busy, batch_reads
         self.gz = members  # nativeio.GzMembers: this input is inflated on the device
         self.f = nativeio.FastqFile(path) if members is None else None
         self.comp = [_DevBuf(rt), _DevBuf(rt)]  # compressed form: the members of the window
@@ -166,6 +169,101 @@ class _Input:
         self.d_len = _DevBuf(rt)
         self.d_off.ensure(4 * batch_reads * 8)
         self.d_len.ensure(4 * batch_reads * 4)
+
+    def want_bytes(self) -> int:
+        return int(self.batch_reads * self.avg_record * 1.05) + 65536
+
+    def upload(self, s_copy: int, slot: int, want: int):
+        """bytes [cursor, cursor + want) of the input (what is there of them) -> the device window `slot`"""
+        t0 = time.perf_counter()
+        # (the current device belongs to the thread: the upload thread has to choose it as well)
+        self.rt.check(self.rt.hipSetDevice(int(getattr(self.cl, "device", 0))), "hipSetDevice")
+        if self.gz is not None:
+            self.upload_members(s_copy, slot, want)
+        else:
+            self.upload_text(s_copy, slot, want)
+        self.busy["upload_s"] += time.perf_counter() - t0
+
+    def upload_text(self, s_copy: int, slot: int, want: int):
+        """the plain text bytes (mapped, or inflated so far by the host: waits for them) -> the device buffer text[slot]"""
+        rt, L = self.rt, self.L
+        avail, fin = C.c_int64(0), C.c_int32(0)
+        if L.bdx_fq_wait(self.f.h, self.cursor + want, C.byref(avail), C.byref(fin)) != 0:
+            raise OSError(L.bdx_io_last_error().decode())
+        end = min(avail.value, self.cursor + want)
+        nbytes = max(0, end - self.cursor)
+        final = bool(fin.value) and end >= avail.value
+        dst = self.text[slot].ensure(nbytes + 64)
+        if nbytes:
+            src = L.bdx_fq_data(self.f.h) + self.cursor
+            rt.check(rt.hipMemcpyAsync(dst, src, nbytes, _H2D, s_copy), "hipMemcpyAsync (upload)")
+            rt.check(rt.hipStreamSynchronize(s_copy), "hipStreamSynchronize (upload)")
+        self.win[slot] = (nbytes, final)
+        self.d_text[slot] = dst
+
+    def upload_members(self, s_copy: int, slot: int, want: int):
+        """the compressed members that cover the text bytes [cursor, cursor + want) -> the device buffer comp[slot]"""
+        g, rt = self.gz, self.rt
+        n, po = len(g), g.plain_off
+        m0 = min(int(np.searchsorted(po, self.cursor, side="right")) - 1, n)  # the member that holds the cursor
+        m1 = max(m0, min(int(np.searchsorted(po, self.cursor + want, side="left")), n))
+        while m1 < n and g.isize[m1] == 0:  # (an empty member behind the window: the BGZF end marker)
+            m1 += 1
+        if m1 > m0:
+            c0 = int(g.comp_off[m0])
+            nbytes = int(g.comp_off[m1 - 1]) + int(g.comp_len[m1 - 1]) - c0
+            dst = self.comp[slot].ensure(nbytes)
+            rt.check(rt.hipMemcpyAsync(dst, g.data + c0, nbytes, _H2D, s_copy), "hipMemcpyAsync (upload)")
+            rt.check(rt.hipStreamSynchronize(s_copy), "hipStreamSynchronize (upload)")
+            self.busy["compressed_in_bytes"] += nbytes
+        self.wmem[slot] = (m0, m1)
+        self.win[slot] = (max(0, int(po[m1]) - self.cursor), m1 == n)
+
+    def inflate(self, slot: int):
+        """comp[slot] -> text[slot] on the context's stream (the calling thread); the window's text starts at the
+        cursor, somewhere inside the first member"""
+        t_i = time.perf_counter()
+        g, lib, h = self.gz, self.cl.lib, self.cl.h
+        m0, m1 = self.wmem[slot]
+        k = m1 - m0
+        total = int(g.plain_off[m1] - g.plain_off[m0])
+        d_text = self.text[slot].ensure(total + 64)
+        if k:
+            coff = np.ascontiguousarray(g.comp_off[m0:m1] - g.comp_off[m0])
+            poff = np.ascontiguousarray(g.plain_off[m0:m1] - g.plain_off[m0])
+            clen = np.ascontiguousarray(g.comp_len[m0:m1])
+            plen = np.ascontiguousarray(g.isize[m0:m1])
+            status = np.zeros(k, dtype=np.int32)
+            rc = lib.bdx_fq_inflate_device(h, self.comp[slot].p, coff.ctypes.data, clen.ctypes.data, poff.ctypes.data,
+                                           plen.ctypes.data, k, d_text, total, status.ctypes.data)
+            if rc != 0:
+                bad = np.flatnonzero(status)
+                msg = lib.bdx_last_error(h).decode()
+                if len(bad):
+                    msg = f"{self.path}: gzip member {m0 + int(bad[0])} is refused by the device inflate ({msg})"
+                raise BdxError(msg)
+            self.busy["plain_in_bytes"] += total
+        self.d_text[slot] = d_text + (self.cursor - int(g.plain_off[m0]))
+        self.busy["inflate_s"] += time.perf_counter() - t_i
+
+    def index(self, s_copy: int, slot: int):
+        """The line table of the batch that starts window `slot` (on the context's stream, after the inflate if there is
+        one) -> (records, bytes they take).  A window that ends before ``batch_reads`` records do is uploaded again,
+        twice as large, from the calling thread."""
+        want = self.want_bytes()
+        while True:
+            if self.gz is not None:
+                self.inflate(slot)
+            nbytes, final = self.win[slot]
+            n, nxt = C.c_int64(0), C.c_int64(0)
+            self.cl._check(self.cl.lib.bdx_fq_index_device(self.cl.h, self.d_text[slot], nbytes, int(final), self.batch_reads,
+                                                           self.d_off.p, self.d_len.p, C.byref(n), C.byref(nxt)))
+            if n.value >= self.batch_reads or final:
+                return n.value, nxt.value
+            want = 2 * max(want, nbytes)  # a record did not fit: a larger window
+            t_up = time.perf_counter()
+            self.upload(s_copy, slot, want)
+            self.busy["device_s"] -= time.perf_counter() - t_up  # (upload_s has it; the driver counts this whole call)
 
     def release(self):
         """everything below the cursor is uploaded: the host pages can go"""
@@ -183,6 +281,86 @@ class _Input:
                 f.close()
 
 
+class _Slots:
+    """The pinned download buffers: batch k is downloaded into one while the writer appends batch k - 1 from the other.
+    ``free`` holds the slots the writer is done with, ``events[s]`` fires when the copy into ``hbuf[s]`` has landed."""
+
+    def __init__(self, rt: _Runtime, n: int = 2):
+        self.events = [rt.event() for _ in range(n)]
+        self.hbuf = [None] * n
+        self.free: "queue.Queue" = queue.Queue()
+        for s in range(n):
+            self.free.put(s)
+
+
+def _deflate(classifier, d_out: _DevBuf, d_gz: _DevBuf, blocks, n_classes: int, busy: dict):
+    """The batch's gathered blocks in d_out (the streams' blocks are one run of n_classes * len(blocks) blocks: one
+    deflate call) -> finished gzip members in d_gz; -> (their blocks, their bytes)"""
+    t_z = time.perf_counter()
+    lib = classifier.lib
+    cb_all = np.concatenate([cb for _, cb, _ in blocks])
+    d_gz.ensure(int(lib.bdx_fq_deflate_bound(cb_all.ctypes.data, len(cb_all))))
+    zb = np.zeros(len(cb_all), dtype=np.int64)
+    classifier._check(lib.bdx_fq_deflate_device(classifier.h, d_out.p, cb_all.ctypes.data, len(cb_all), d_gz.p, d_gz.cap,
+                                                zb.ctypes.data))
+    busy["plain_bytes"] += int(cb_all.sum())
+    zblocks, pos = [], 0
+    for k, (_, _, prefix) in enumerate(blocks):
+        cz = zb[k * n_classes:(k + 1) * n_classes].copy()
+        zblocks.append((pos, cz, prefix))
+        pos += int(cz.sum())
+    busy["compressed_bytes"] += pos
+    busy["deflate_s"] += time.perf_counter() - t_z
+    return zblocks, pos
+
+
+def _download(rt: _Runtime, s_main: int, slots: _Slots, errors: list, d_src: _DevBuf, nbytes: int):
+    """Starts the copy of the batch's `nbytes` into a free host slot (the writer hands them back) and records the
+    slot's event behind it: the writer waits for the copy.  -> the slot, or None when the run has failed meanwhile"""
+    while True:
+        try:
+            hs = slots.free.get(timeout=0.05)
+            break
+        except queue.Empty:
+            if errors:
+                return None
+    if errors:
+        return None
+    if slots.hbuf[hs] is None or len(slots.hbuf[hs]) < nbytes:
+        slots.hbuf[hs] = pinned_empty(max(nbytes, 1) + (max(nbytes, 1) >> 3), np.uint8)
+    if nbytes:
+        rt.check(rt.hipMemcpyAsync(slots.hbuf[hs].ctypes.data, d_src.p, nbytes, _D2H, s_main), "hipMemcpyAsync (download)")
+    rt.check(rt.hipEventRecord(slots.events[hs], s_main), "hipEventRecord")
+    return hs
+
+
+def _write_loop(q_w, slots: _Slots, errors: list, rt: _Runtime, L, layout: OutputLayout, raw: bool, T: int, busy: dict):
+    """The writer thread: per batch, waits for its download and appends one block per file and stream, in batch
+    order.  ``raw``: the blocks are finished gzip members, appended as they are."""
+    for slot, blocks in iter(q_w.get, None):
+        try:
+            if errors:
+                continue
+            t0 = time.perf_counter()
+            rt.check(rt.hipEventSynchronize(slots.events[slot]), "hipEventSynchronize (download)")
+            t1 = time.perf_counter()
+            base = slots.hbuf[slot].ctypes.data
+            for off, cb, prefix in blocks:
+                paths = layout.c_paths(prefix, np.flatnonzero(cb))
+                if raw:
+                    rc = L.bdx_fq_write_blocks_raw(base + off, cb.ctypes.data, layout.n_classes, paths, T)
+                else:
+                    rc = L.bdx_fq_write_blocks(base + off, cb.ctypes.data, layout.n_classes, paths, layout.gz, T)
+                if rc != 0:
+                    raise OSError(L.bdx_io_last_error().decode())
+            busy["download_s"] += t1 - t0
+            busy["write_s"] += time.perf_counter() - t1
+        except BaseException as e:  # noqa: BLE001 - forwarded to the caller
+            errors.append(e)
+        finally:
+            slots.free.put(slot)
+
+
 def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
                  classifier, batch_reads: int, timings: Optional[dict] = None, gzip_device: bool = False,
                  gunzip_device: bool = False) -> None:
@@ -197,42 +375,32 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
     t_wall = time.perf_counter()
     busy = {"upload_s": 0.0, "device_s": 0.0, "download_s": 0.0, "write_s": 0.0, "batches": 0}
     L = _io()
-    rt = _Runtime(classifier.lib)
-    dev = int(getattr(classifier, "device", 0))
-    rt.check(rt.hipSetDevice(dev), "hipSetDevice")
+    lib, h, check = classifier.lib, classifier.h, classifier._check
+    rt = _Runtime(lib)
+    rt.check(rt.hipSetDevice(int(getattr(classifier, "device", 0))), "hipSetDevice")
     T = nativeio._threads()
     batch_reads = max(1, int(batch_reads))
-    stride = max(1, len(config.bc_seqs2)) if config.is_dual else 1
-    n_classes = 2 + len(config.bc_seqs) * stride
-    do_trim = config.trim_side is not None or config.trim_side2 is not None
-    gz = int(bool(config.gzip_output))
-    dev_gz = bool(gzip_device) and bool(gz)
+    paired = fastq2 is not None
+    layout = OutputLayout(config, output_directory, prefix1, prefix2, paired)
+    n_classes = layout.n_classes
+    dev_gz = bool(gzip_device) and bool(layout.gz)
     if dev_gz:
         busy.update(deflate_s=0.0, plain_bytes=0, compressed_bytes=0)
-    paired = fastq2 is not None
-    # output streams of a batch: (input, prefix, trim) — core.jl:175-196
-    if paired and config.classify_both:
-        outs = [(0, prefix1, do_trim), (1, prefix2, False)]
-    elif paired:
-        outs = [(1, prefix2, False)]
-    else:
-        outs = [(0, prefix1, do_trim)]
 
     ins = []
     s_main = s_copy = 0
-    events = []
+    slots = None
     dbufs = []
     errors = []
     q_w: "queue.Queue" = queue.Queue(maxsize=1)
-    free: "queue.Queue" = queue.Queue()
     up = ThreadPoolExecutor(max_workers=1, thread_name_prefix="bdx-upload")
     fut = None
     writer = None
     try:
         for path in (fastq1, fastq2) if paired else (fastq1,):  # (each input judged on its own)
-            members = open_members(path, classifier.lib) if gunzip_device and _is_gz(path) else None
+            members = open_members(path, lib) if gunzip_device and _is_gz(path) else None
             try:
-                ins.append(_Input(path, rt, batch_reads, members))
+                ins.append(_Input(path, rt, L, classifier, busy, batch_reads, members))
             except BaseException:
                 if members is not None:
                     members.close()
@@ -247,230 +415,65 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
         d_seq_off.ensure((batch_reads + 1) * 8)
         for b in d_v.values():
             b.ensure(batch_reads * 4)
-        n_slots = 2  # download / write buffers: batch k is downloaded while k-1 is written
-        events = [rt.event() for _ in range(n_slots)]
-        hbuf = [None] * n_slots
-        for s in range(n_slots):
-            free.put(s)
-
-        def upload(inp: _Input, slot: int, want: int):
-            """bytes [cursor, cursor + want) of the input (what is there of them) -> the device window `slot`"""
-            t0 = time.perf_counter()
-            rt.check(rt.hipSetDevice(dev), "hipSetDevice")
-            if inp.gz is not None:
-                upload_members(inp, slot, want)
-                busy["upload_s"] += time.perf_counter() - t0
-                return
-            avail, fin = C.c_int64(0), C.c_int32(0)
-            if L.bdx_fq_wait(inp.f.h, inp.cursor + want, C.byref(avail), C.byref(fin)) != 0:
-                raise OSError(L.bdx_io_last_error().decode())
-            end = min(avail.value, inp.cursor + want)
-            nbytes = max(0, end - inp.cursor)
-            final = bool(fin.value) and end >= avail.value
-            dst = inp.text[slot].ensure(nbytes + 64)
-            if nbytes:
-                src = L.bdx_fq_data(inp.f.h) + inp.cursor
-                rt.check(rt.hipMemcpyAsync(dst, src, nbytes, _H2D, s_copy), "hipMemcpyAsync (upload)")
-                rt.check(rt.hipStreamSynchronize(s_copy), "hipStreamSynchronize (upload)")
-            inp.win[slot] = (nbytes, final)
-            inp.d_text[slot] = dst
-            busy["upload_s"] += time.perf_counter() - t0
-
-        def upload_members(inp: _Input, slot: int, want: int):
-            """the compressed members that cover the text bytes [cursor, cursor + want) -> the device buffer comp[slot]"""
-            g = inp.gz
-            n, po = len(g), g.plain_off
-            m0 = min(int(np.searchsorted(po, inp.cursor, side="right")) - 1, n)  # the member that holds the cursor
-            m1 = max(m0, min(int(np.searchsorted(po, inp.cursor + want, side="left")), n))
-            while m1 < n and g.isize[m1] == 0:  # (an empty member behind the window: the BGZF end marker)
-                m1 += 1
-            if m1 > m0:
-                c0 = int(g.comp_off[m0])
-                nbytes = int(g.comp_off[m1 - 1]) + int(g.comp_len[m1 - 1]) - c0
-                dst = inp.comp[slot].ensure(nbytes)
-                rt.check(rt.hipMemcpyAsync(dst, g.data + c0, nbytes, _H2D, s_copy), "hipMemcpyAsync (upload)")
-                rt.check(rt.hipStreamSynchronize(s_copy), "hipStreamSynchronize (upload)")
-                busy["compressed_in_bytes"] += nbytes
-            inp.wmem[slot] = (m0, m1)
-            inp.win[slot] = (max(0, int(po[m1]) - inp.cursor), m1 == n)
-
-        def inflate(inp: _Input, slot: int):
-            """comp[slot] -> text[slot] on the context's stream (the calling thread); the window's text starts at the
-            cursor, somewhere inside the first member"""
-            t_i = time.perf_counter()
-            g = inp.gz
-            m0, m1 = inp.wmem[slot]
-            k = m1 - m0
-            total = int(g.plain_off[m1] - g.plain_off[m0])
-            d_text = inp.text[slot].ensure(total + 64)
-            if k:
-                coff = np.ascontiguousarray(g.comp_off[m0:m1] - g.comp_off[m0])
-                poff = np.ascontiguousarray(g.plain_off[m0:m1] - g.plain_off[m0])
-                clen = np.ascontiguousarray(g.comp_len[m0:m1])
-                plen = np.ascontiguousarray(g.isize[m0:m1])
-                status = np.zeros(k, dtype=np.int32)
-                rc = lib.bdx_fq_inflate_device(h, inp.comp[slot].p, coff.ctypes.data, clen.ctypes.data, poff.ctypes.data,
-                                               plen.ctypes.data, k, d_text, total, status.ctypes.data)
-                if rc != 0:
-                    bad = np.flatnonzero(status)
-                    msg = lib.bdx_last_error(h).decode()
-                    if len(bad):
-                        msg = f"{inp.path}: gzip member {m0 + int(bad[0])} is refused by the device inflate ({msg})"
-                    raise BdxError(msg)
-                busy["plain_in_bytes"] += total
-            inp.d_text[slot] = d_text + (inp.cursor - int(g.plain_off[m0]))
-            busy["inflate_s"] += time.perf_counter() - t_i
-
-        def want_bytes(inp: _Input) -> int:
-            return int(batch_reads * inp.avg_record * 1.05) + 65536
+        slots = _Slots(rt)
 
         def upload_all(slot: int):
             for inp in ins:
-                upload(inp, slot, want_bytes(inp))
+                inp.upload(s_copy, slot, inp.want_bytes())
 
-        def write_loop():
-            while True:
-                item = q_w.get()
-                if item is None:
-                    return
-                slot, blocks = item
-                try:
-                    if errors:
-                        continue
-                    t0 = time.perf_counter()
-                    rt.check(rt.hipEventSynchronize(events[slot]), "hipEventSynchronize (download)")
-                    t1 = time.perf_counter()
-                    base = hbuf[slot].ctypes.data
-                    for off, cb, prefix in blocks:
-                        if dev_gz:  # finished gzip members: appended as they are
-                            rc = L.bdx_fq_write_blocks_raw(base + off, cb.ctypes.data, n_classes, _paths(prefix, cb), T)
-                        else:
-                            rc = L.bdx_fq_write_blocks(base + off, cb.ctypes.data, n_classes, _paths(prefix, cb), gz, T)
-                        if rc != 0:
-                            raise OSError(L.bdx_io_last_error().decode())
-                    busy["download_s"] += t1 - t0
-                    busy["write_s"] += time.perf_counter() - t1
-                except BaseException as e:  # noqa: BLE001 - forwarded to the caller
-                    errors.append(e)
-                finally:
-                    free.put(slot)
-
-        def _paths(prefix, cb):
-            arr = (C.c_char_p * n_classes)()
-            for c in np.flatnonzero(cb):
-                c = int(c)
-                if c == 0:
-                    b1, b2 = 0, 0
-                elif c == 1:
-                    b1, b2 = -1, 0
-                else:
-                    b1, b2 = divmod(c - 2, stride)
-                    b1, b2 = b1 + 1, (b2 + 1 if config.is_dual else 0)
-                arr[c] = os.path.join(output_directory, prefix + "." + filename_for(config, b1, b2)).encode()
-            return arr
-
-        writer = threading.Thread(target=write_loop, name="bdx-device-writer")
+        writer = threading.Thread(target=_write_loop, name="bdx-device-writer",
+                                  args=(q_w, slots, errors, rt, L, layout, dev_gz, T, busy))
         writer.start()
-        lib = classifier.lib
-        h = classifier.h
-
-        def check(rc):
-            if rc != 0:
-                raise BdxError(lib.bdx_last_error(h).decode())
-
         slot = 0
         fut = up.submit(upload_all, slot)
         while True:
-            fut.result()
+            fut.result()  # 1. the upload of this batch's windows
             fut = None
             if errors:
                 break
             t0 = time.perf_counter()
-            ns, nexts = [], []
-            for inp in ins:
-                want = want_bytes(inp)
-                while True:
-                    if inp.gz is not None:
-                        inflate(inp, slot)
-                    nbytes, final = inp.win[slot]
-                    n, nxt = C.c_int64(0), C.c_int64(0)
-                    check(lib.bdx_fq_index_device(h, inp.d_text[slot], nbytes, int(final), batch_reads, inp.d_off.p,
-                                                  inp.d_len.p, C.byref(n), C.byref(nxt)))
-                    if n.value >= batch_reads or final:
-                        break
-                    want = 2 * max(want, nbytes)  # a record did not fit: a larger window
-                    busy["device_s"] += time.perf_counter() - t0
-                    upload(inp, slot, want)
-                    t0 = time.perf_counter()
-                ns.append(n.value)
-                nexts.append(nxt.value)
+            found = [inp.index(s_copy, slot) for inp in ins]  # 2. the line index of each input
+            ns = [k for k, _ in found]
             n = min(ns)
             last = paired and ns[0] != ns[1]  # lock-step pairs: stop at the shorter file (core.jl:48)
             if n == 0:
                 break
-            for inp, nx, k in zip(ins, nexts, ns):  # (the index's cursor is relative to the window = the input's cursor)
+            # 3. the cursors move behind the batch (the index's cursor is relative to the window = the input's cursor)
+            for inp, (k, nx) in zip(ins, found):
                 if k:
                     inp.avg_record = nx / k
                 inp.cursor += nx
                 inp.release()  # uploaded: the host pages of this batch can go
-            r1 = ins[0]
             wins = [inp.win[slot][0] for inp in ins]
-            if not last:
+            if not last:  # 4. the next batch's windows go up beside this batch's kernels
                 fut = up.submit(upload_all, slot ^ 1)
-            # pack -> ONE classify call -> the gathers
-            nb1 = wins[0]
-            d_seq.ensure(nb1 + 64)
-            check(lib.bdx_fq_pack_device(h, r1.d_text[slot], nb1, r1.d_off.p, r1.d_len.p, n, d_seq.p, d_seq.cap,
+            # 5. pack -> ONE classify call -> the gathers
+            r1 = ins[0]
+            d_seq.ensure(wins[0] + 64)
+            check(lib.bdx_fq_pack_device(h, r1.d_text[slot], wins[0], r1.d_off.p, r1.d_len.p, n, d_seq.p, d_seq.cap,
                                          d_seq_off.p, None))
             classifier.classify_device(d_seq.p, d_seq_off.p, n, **{k: b.p for k, b in d_v.items()})
-            out_cap = sum(wins[i] + 64 for i, _, _ in outs)
-            d_out.ensure(out_cap)
+            d_out.ensure(sum(wins[i] + 64 for i, _, _ in layout.streams))
             blocks, pos = [], 0
-            for i, prefix, trim in outs:
+            for i, prefix, trim in layout.streams:
                 inp = ins[i]
                 cb = np.zeros(n_classes, dtype=np.int64)
                 check(lib.bdx_fq_gather_device(h, inp.d_text[slot], wins[i], inp.d_off.p, inp.d_len.p, n, d_v["bc1"].p,
-                                               d_v["bc2"].p, stride, n_classes, d_v["keep_start"].p, d_v["keep_end"].p,
-                                               int(bool(trim)), d_out.p + pos, d_out.cap - pos, cb.ctypes.data))
+                                               d_v["bc2"].p, layout.stride, n_classes, d_v["keep_start"].p,
+                                               d_v["keep_end"].p, int(bool(trim)), d_out.p + pos, d_out.cap - pos,
+                                               cb.ctypes.data))
                 blocks.append((pos, cb, prefix))
                 pos += int(cb.sum())
             d_src = d_out
-            if dev_gz:  # the streams' blocks are one run of n_classes * len(outs) blocks: one deflate call
-                t_z = time.perf_counter()
-                cb_all = np.concatenate([cb for _, cb, _ in blocks])
-                bound = int(lib.bdx_fq_deflate_bound(cb_all.ctypes.data, len(cb_all)))
-                d_gz.ensure(bound)
-                zb = np.zeros(len(cb_all), dtype=np.int64)
-                check(lib.bdx_fq_deflate_device(h, d_out.p, cb_all.ctypes.data, len(cb_all), d_gz.p, d_gz.cap,
-                                                zb.ctypes.data))
-                busy["plain_bytes"] += pos
-                prefixes = [prefix for _, _, prefix in blocks]
-                blocks, pos = [], 0
-                for k, prefix in enumerate(prefixes):
-                    cz = zb[k * n_classes:(k + 1) * n_classes].copy()
-                    blocks.append((pos, cz, prefix))
-                    pos += int(cz.sum())
-                busy["compressed_bytes"] += pos
-                busy["deflate_s"] += time.perf_counter() - t_z
+            if dev_gz:  # 6. only finished gzip members come back
+                blocks, pos = _deflate(classifier, d_out, d_gz, blocks, n_classes, busy)
                 d_src = d_gz
             busy["device_s"] += time.perf_counter() - t0
             busy["batches"] += 1
-            # download into a free host slot (the writer hands them back); the writer waits for the copy
-            while True:
-                try:
-                    hs = free.get(timeout=0.05)
-                    break
-                except queue.Empty:
-                    if errors:
-                        break
-            if errors:
+            hs = _download(rt, s_main, slots, errors, d_src, pos)  # 7.
+            if hs is None:
                 break
-            if hbuf[hs] is None or len(hbuf[hs]) < pos:
-                hbuf[hs] = pinned_empty(max(pos, 1) + (max(pos, 1) >> 3), np.uint8)
-            if pos:
-                rt.check(rt.hipMemcpyAsync(hbuf[hs].ctypes.data, d_src.p, pos, _D2H, s_main), "hipMemcpyAsync (download)")
-            rt.check(rt.hipEventRecord(events[hs], s_main), "hipEventRecord")
-            q_w.put((hs, blocks))
+            q_w.put((hs, blocks))  # 8. the writer waits for the copy and appends the blocks
             if last:
                 break
             slot ^= 1
@@ -493,7 +496,7 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
             b.free()
         for inp in ins:
             inp.close()
-        for e in events:
+        for e in (slots.events if slots is not None else ()):
             rt.hipEventDestroy(e)
         for s in (s_main, s_copy):
             if s:

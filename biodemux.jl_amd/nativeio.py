@@ -9,13 +9,15 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import queue
 import subprocess
 import threading
+import time
 from typing import Optional
 
 import numpy as np
 
-from .classification import filename_for
+from .outputs import OutputLayout
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "csrc", "bdx_io.cpp")
@@ -207,75 +209,88 @@ def release_buffers() -> None:
         del _BUFFER_POOL[:]
 
 
-def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
-                 classifier, batch_reads: int, on_batch=None, timings: Optional[dict] = None) -> None:
-    """Native counterpart of core._demux: index -> pack -> ONE C-ABI classify call -> in-order write,
-    as a three-stage pipeline (reader thread | classify on the calling thread | writer thread; the
-    native calls release the GIL).  Batches flow through bounded FIFO queues, so per-file order is
-    input order exactly as with the reference's single writer task (core.jl:139-148).
+class _Batch:
+    """One batch on its way reader -> classify -> writer: its id (the input order), ``n`` records, the line tables of both
+    inputs, the packed chunk (``seq``, ``so``), the inputs' cursors behind it, the buffer set ``buf`` all these arrays
+    belong to and — once classified — the output class of every read (``cls``), what is kept of it (``ks``, ``ke``) and the
+    classes in use (``used``)."""
+    __slots__ = ("bid", "n", "off1", "ln1", "off2", "ln2", "seq", "so", "cur1", "cur2", "buf", "cls", "ks", "ke", "used")
 
-    ``classifier`` may also be a list of N > 1 classifiers (one per device context): then N classify threads take the
-    batches from the reader as they come free (first free context wins) and a reorder step hands the results to the
-    writer strictly by batch id, so the files are those of a single context.  ``on_batch`` is then called under a lock."""
-    import queue
-    import time
+    def __init__(self, bid, n, off1, ln1, off2, ln2, seq, so, cur1, cur2, buf):
+        self.bid, self.n, self.off1, self.ln1, self.off2, self.ln2 = bid, n, off1, ln1, off2, ln2
+        self.seq, self.so, self.cur1, self.cur2, self.buf = seq, so, cur1, cur2, buf
+        self.cls = self.ks = self.ke = self.used = None
 
-    classifiers = list(classifier) if isinstance(classifier, (list, tuple)) else [classifier]
-    N = len(classifiers)
-    busy = {"index_s": 0.0, "pack_s": 0.0, "classify_s": 0.0, "write_s": 0.0, "batches": 0}
-    t_wall = time.perf_counter()
-    L = _load()
-    T = _threads()
-    # (developer knobs: host threads of the reader's / the writer's parallel sections — both default to the whole quota)
-    TR = max(1, int(os.environ.get("BDX_IO_READER_THREADS", T)))
-    TW = max(1, int(os.environ.get("BDX_IO_WRITER_THREADS", T)))
-    f1 = FastqFile(fastq1)
-    f2 = FastqFile(fastq2) if fastq2 is not None else None
-    stride = max(1, len(config.bc_seqs2)) if config.is_dual else 1
-    n_classes = 2 + len(config.bc_seqs) * stride
-    do_trim = config.trim_side is not None or config.trim_side2 is not None
-    gz = int(bool(config.gzip_output))
-    q_in: "queue.Queue" = queue.Queue(maxsize=1)
-    errors = []
-    # Batch buffers travel reader -> classify -> writer and come back through `free`: line tables, the packed chunk and
-    # the verdict vectors are allocated a handful of times per run, not once per batch (fresh arrays of this size are
-    # page-faulted in by whoever writes them first: ~15 % of the reader's time)
-    free: "queue.Queue" = queue.Queue()
-    # One context: one set per stage (reader, classify, writer) + one waiting in front of each of the two consumers.
-    # N contexts: 1 being filled by the reader + 1 waiting in q_in + N in the contexts + N - 1 results parked early in the
-    # reorder step (while the oldest batch is still being classified) + 1 being written + 1 queued for the writer = 2N + 3.
-    # The count only decides how much overlaps; the dealer cannot deadlock with any count >= 1: every set is owned by a
-    # batch that was read and is not yet written.  If the reader waits for a set, let r be the oldest of those batches.
-    # Every batch before r is written, so r is never parked: it is in q_in or in a context (which classify it without
-    # waiting for anything: the reorder step and the writer's queue are unbounded, their size is bounded by the sets),
-    # or with the writer.  Either way r reaches the disk and its set comes back.
-    n_sets = 5 if N == 1 else 2 * N + 3
-    with _BUFFER_POOL_LOCK:
-        bufs = [(_BUFFER_POOL.pop() if _BUFFER_POOL else {}) for _ in range(n_sets)]
-    for b in bufs:
-        free.put(b)
 
-    def reader():
+class _NativeRun:
+    """The threads of one demux_native call and what they share: reader -> q_in -> one classify thread per context -> the
+    reorder step -> q_out -> writer, and the batch buffer sets coming back through ``free``."""
+
+    def __init__(self, fastq1, fastq2, layout, classifiers, batch_reads, on_batch):
+        self.layout, self.classifiers, self.batch_reads, self.on_batch = layout, classifiers, batch_reads, on_batch
+        N = len(classifiers)
+        self.busy = {"index_s": 0.0, "pack_s": 0.0, "classify_s": 0.0, "write_s": 0.0, "batches": 0}
+        self.L = _load()
+        self.T = _threads()
+        # (developer knobs: host threads of the reader's / the writer's parallel sections — both default to the whole quota)
+        self.TR = max(1, int(os.environ.get("BDX_IO_READER_THREADS", self.T)))
+        self.TW = max(1, int(os.environ.get("BDX_IO_WRITER_THREADS", self.T)))
+        self.f1 = FastqFile(fastq1)
+        self.f2 = FastqFile(fastq2) if fastq2 is not None else None
+        self.errors: list = []
+        self.q_in: "queue.Queue" = queue.Queue(maxsize=1)
+        # (the reorder step puts into this under its lock: it must never block — the batch sets bound it)
+        self.q_out: "queue.Queue" = queue.Queue()
+        self.per_dev_s = [0.0] * N
+        self.per_dev_b = [0] * N
+        self.parked: dict = {}  # batch id -> batch, for results that finished before an older batch
+        self.next_id = 0
+        self.order_lock = threading.Lock()
+        self.batch_lock = threading.Lock()  # serialises on_batch (the summary of an injected classifier)
+        # Batch buffers travel reader -> classify -> writer and come back through `free`: line tables, the packed chunk and
+        # the verdict vectors are allocated a handful of times per run, not once per batch (fresh arrays of this size are
+        # page-faulted in by whoever writes them first: ~15 % of the reader's time)
+        self.free: "queue.Queue" = queue.Queue()
+        # N contexts: 1 being filled by the reader + 1 waiting in q_in + N in the contexts + N - 1 results parked early in the
+        # reorder step (while the oldest batch is still being classified) + 1 being written + 1 queued for the writer = 2N + 3.
+        # (One context: 5 — one set per stage (reader, classify, writer) + one waiting in front of each of the two consumers.)
+        # The count only decides how much overlaps; the dealer cannot deadlock with any count >= 1: every set is owned by a
+        # batch that was read and is not yet written.  If the reader waits for a set, let r be the oldest of those batches.
+        # Every batch before r is written, so r is never parked: it is in q_in or in a context (which classify it without
+        # waiting for anything: the reorder step and the writer's queue are unbounded, their size is bounded by the sets),
+        # or with the writer.  Either way r reaches the disk and its set comes back.
+        n_sets = 2 * N + 3
+        with _BUFFER_POOL_LOCK:
+            self.bufs = [(_BUFFER_POOL.pop() if _BUFFER_POOL else {}) for _ in range(n_sets)]
+        for b in self.bufs:
+            self.free.put(b)
+
+    def give_back(self, batch: _Batch) -> None:
+        """A batch that will not be written (an error somewhere): its buffer set goes back to the reader."""
+        self.free.put(batch.buf)
+
+    def reader(self):
+        f1, f2, TR, busy = self.f1, self.f2, self.TR, self.busy
         try:
             bid = 0
             while True:
                 # (a batch dropped on an error path never comes back through `free`: poll, and stop once anything failed —
-                # the reader must always reach its final q_in.put(None), or the caller waits for it forever)
+                # the reader must always reach its final q_in.put(None), or the classify threads wait for it forever)
                 while True:
                     try:
-                        buf = free.get(timeout=0.05)
+                        buf = self.free.get(timeout=0.05)
                         break
                     except queue.Empty:
-                        if errors:
+                        if self.errors:
                             return
-                if errors:
+                if self.errors:
                     return
                 t0 = time.perf_counter()
-                n1, off1, ln1 = f1.next_batch(batch_reads, TR, buf.get("off1"), buf.get("ln1"))
+                n1, off1, ln1 = f1.next_batch(self.batch_reads, TR, buf.get("off1"), buf.get("ln1"))
                 buf["off1"], buf["ln1"] = off1, ln1
                 off2 = ln2 = None
                 if f2 is not None:
-                    n2, off2, ln2 = f2.next_batch(batch_reads, TR, buf.get("off2"), buf.get("ln2"))
+                    n2, off2, ln2 = f2.next_batch(self.batch_reads, TR, buf.get("off2"), buf.get("ln2"))
                     buf["off2"], buf["ln2"] = off2, ln2
                     n = min(n1, n2)  # lock-step pairs: stop at the shorter file (core.jl:48)
                     last = n1 != n2
@@ -291,214 +306,143 @@ def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: s
                     buf["so"] = so.base
                 busy["index_s"] += t1 - t0
                 busy["pack_s"] += time.perf_counter() - t1
-                q_in.put((bid, n, off1, ln1, off2, ln2, seq, so, f1.cursor, f2.cursor if f2 is not None else 0, buf))
+                self.q_in.put(_Batch(bid, n, off1, ln1, off2, ln2, seq, so, f1.cursor, f2.cursor if f2 is not None else 0, buf))
                 bid += 1
                 if last:
                     break
         except BaseException as e:  # noqa: BLE001 - forwarded to the caller
-            errors.append(e)
+            self.errors.append(e)
         finally:
-            q_in.put(None)
+            self.q_in.put(None)
 
-    def paths(prefix, used):
-        arr = (C.c_char_p * n_classes)()
-        for c in used:
-            c = int(c)
-            if c == 0:
-                b1, b2 = 0, 0
-            elif c == 1:
-                b1, b2 = -1, 0
-            else:
-                b1, b2 = divmod(c - 2, stride)
-                b1, b2 = b1 + 1, (b2 + 1 if config.is_dual else 0)
-            arr[c] = os.path.join(output_directory, prefix + "." + filename_for(config, b1, b2)).encode()
-        return arr
-
-    # The writer gathers every batch straight into the (mapped) output files with all its threads working on all files
-    # (csrc/bdx_io.cpp): one writer thread, one class range.  (bdx_fq_demux_write_range lets several writer threads
-    # share a batch by class range — each file then still belongs to exactly one of them, in batch order: per-file order
-    # = input order, core.jl:139-148 — which pays on file systems without shared writable mappings.)
-    ranges = [(0, n_classes)]
-    # (with N contexts the reorder step puts into these under its lock: they must never block — the batch sets bound them)
-    q_outs = [queue.Queue(maxsize=1 if N == 1 else 0) for _ in ranges]
-    done_lock = threading.Lock()
-
-    def writer(wi):
-        lo, hi = ranges[wi]
-        qw = q_outs[wi]
-        tshare = TW
-        try:
-            while True:
-                item = qw.get()
-                if item is None:
-                    break
-                n, off1, ln1, off2, ln2, cls, ks, ke, cur1, cur2, buf, pending, used = item
-                tw0 = time.perf_counter()
-
-                def write(f, off, ln, prefix, trim):
-                    rc = L.bdx_fq_demux_write_range(f.h, off.ctypes.data, ln.ctypes.data, n, cls.ctypes.data, n_classes,
-                                                    paths(prefix, used), ks.ctypes.data, ke.ctypes.data, int(trim), gz, tshare, lo, hi)
-                    if rc != 0:
-                        raise OSError(L.bdx_io_last_error().decode())
-
-                if used[(used >= lo) & (used < hi)].size:
-                    if config.classify_both and f2 is not None:  # core.jl:175-185
-                        write(f1, off1, ln1, prefix1, do_trim)
-                        write(f2, off2, ln2, prefix2, False)
-                    elif f2 is not None:  # core.jl:186-190
-                        write(f2, off2, ln2, prefix2, False)
-                    else:  # core.jl:191-196
-                        write(f1, off1, ln1, prefix1, do_trim)
-                with done_lock:
-                    pending[0] -= 1
-                    last = pending[0] == 0
-                    busy["write_s"] += time.perf_counter() - tw0
-                if last:
-                    f1.release(cur1)  # this batch and everything before it is on disk
-                    if f2 is not None:
-                        f2.release(cur2)
-                    free.put(buf)
-        except BaseException as e:  # noqa: BLE001
-            errors.append(e)
-            while True:  # keep draining so the producer never blocks; the dropped batches' buffers go back
-                item = qw.get()
-                if item is None:
-                    break
-                free.put(item[10])
-
-    def classify_batch(cl, item):
-        """One batch through one context -> (verdicts, the writer's item, seconds in classify)."""
-        _bid, n, off1, ln1, off2, ln2, seq, so, cur1, cur2, buf = item
+    def classify(self, cl, b: _Batch):
+        """One batch through one context: fills in the batch's classes -> (verdicts, seconds in classify)."""
+        buf, n = b.buf, b.n
         tc0 = time.perf_counter()
         res = buf.get("out")
         reuse = (res is not None and len(res["bc1"]) >= n and getattr(cl, "want_pass", False) is False
                  and hasattr(cl, "lib"))  # (the HIP wrapper takes result arrays to reuse; test doubles may not)
         if reuse:
-            out = cl.classify(seq, so, out={k: v[:n] for k, v in res.items()})  # <- the hot path: one C-ABI call per batch
+            out = cl.classify(b.seq, b.so, out={k: v[:n] for k, v in res.items()})  # <- the hot path: one C-ABI call per batch
         else:
-            out = cl.classify(seq, so)
+            out = cl.classify(b.seq, b.so)
             if set(out) == {"bc1", "bc2", "keep_start", "keep_end"}:
                 buf["out"] = out
         dt = time.perf_counter() - tc0
-        bc1, bc2 = out["bc1"], out["bc2"]
         cls = buf.get("cls")
         if cls is None or len(cls) < n:
-            cls = buf["cls"] = np.empty(max(n, batch_reads), dtype=np.int32)
-        cls = cls[:n]
-        # class of a read: 0 unknown, 1 ambiguous, 2 + (bc1 - 1) * stride + (bc2 - 1) matched
-        np.subtract(bc1, 1, out=cls)
-        if stride != 1:
-            np.multiply(cls, stride, out=cls)
-            cls += np.maximum(bc2, 1)
-            cls += 1
-        else:
-            cls += 2
-        cls[bc1 == 0] = 0
-        cls[bc1 < 0] = 1
-        ks = np.ascontiguousarray(out["keep_start"], dtype=np.int32)
-        ke = np.ascontiguousarray(out["keep_end"], dtype=np.int32)
-        used = np.flatnonzero(np.bincount(cls, minlength=n_classes))
-        pending = [len(ranges)]
-        return out, (n, off1, ln1, off2, ln2, cls, ks, ke, cur1, cur2, buf, pending, used), dt
+            cls = buf["cls"] = np.empty(max(n, self.batch_reads), dtype=np.int32)
+        b.cls = self.layout.classes(out["bc1"], out["bc2"], cls[:n])
+        b.ks = np.ascontiguousarray(out["keep_start"], dtype=np.int32)
+        b.ke = np.ascontiguousarray(out["keep_end"], dtype=np.int32)
+        b.used = np.flatnonzero(np.bincount(b.cls, minlength=self.layout.n_classes))
+        return out, dt
 
-    # ---- N > 1: the dealer (one classify thread per context, a reorder step in front of the writer) ----
-    per_dev_s = [0.0] * N
-    per_dev_b = [0] * N
-    parked: dict = {}  # batch id -> the writer's item, for results that finished before an older batch
-    next_id = [0]
-    order_lock = threading.Lock()
-    batch_lock = threading.Lock()  # serialises on_batch (the summary of an injected classifier)
-
-    def worker(k):
-        cl = classifiers[k]
-        while True:
-            item = q_in.get()
-            if item is None:
-                q_in.put(None)  # the end mark goes on to the next worker (at most one is ever in the queue)
-                return
-            if errors:
-                free.put(item[-1])
+    def worker(self, k):
+        """The classify thread of context k: takes the batches from the reader as they come (first free context wins)
+        and hands the results to the writer strictly by batch id."""
+        cl = self.classifiers[k]
+        for b in iter(self.q_in.get, None):
+            if self.errors:
+                self.give_back(b)
                 continue
             try:
-                out, witem, dt = classify_batch(cl, item)
-                if on_batch is not None:
-                    with batch_lock:
-                        on_batch(out)
+                out, dt = self.classify(cl, b)
+                if self.on_batch is not None:
+                    with self.batch_lock:
+                        self.on_batch(out)
             except BaseException as e:  # noqa: BLE001 - forwarded to the caller
-                errors.append(e)
-                free.put(item[-1])
+                self.errors.append(e)
+                self.give_back(b)
                 continue
-            per_dev_s[k] += dt
-            per_dev_b[k] += 1
-            with order_lock:  # release strictly by batch id: per-file order = input order (core.jl:139-148)
-                parked[item[0]] = witem
-                while next_id[0] in parked:
-                    w = parked.pop(next_id[0])
-                    for qw in q_outs:
-                        qw.put(w)
-                    next_id[0] += 1
+            self.per_dev_s[k] += dt
+            self.per_dev_b[k] += 1
+            with self.order_lock:  # release strictly by batch id: per-file order = input order (core.jl:139-148)
+                self.parked[b.bid] = b
+                while self.next_id in self.parked:
+                    self.q_out.put(self.parked.pop(self.next_id))
+                    self.next_id += 1
+        self.q_in.put(None)  # the end mark goes on to the next worker (at most one is ever in the queue)
 
-    tr = threading.Thread(target=reader, name="bdx-reader")
-    tws = [threading.Thread(target=writer, args=(wi,), name=f"bdx-writer-{wi}") for wi in range(len(ranges))]
-    tks = [threading.Thread(target=worker, args=(k,), name=f"bdx-classify-{k}") for k in range(N)] if N > 1 else []
-    tr.start()
-    for tw in tws:
+    def writer(self):
+        """Gathers every batch straight into the (mapped) output files with all its threads working on all files
+        (csrc/bdx_io.cpp): one writer thread, every class.  (bdx_fq_demux_write_range could let several writer threads
+        share a batch by class range, which pays on file systems without shared writable mappings; no caller does.)"""
+        L, f1, f2, lay = self.L, self.f1, self.f2, self.layout
+        try:
+            for b in iter(self.q_out.get, None):
+                tw0 = time.perf_counter()
+                for i, prefix, trim in lay.streams:
+                    f, off, ln = (f1, b.off1, b.ln1) if i == 0 else (f2, b.off2, b.ln2)
+                    rc = L.bdx_fq_demux_write_range(f.h, off.ctypes.data, ln.ctypes.data, b.n, b.cls.ctypes.data,
+                                                    lay.n_classes, lay.c_paths(prefix, b.used), b.ks.ctypes.data,
+                                                    b.ke.ctypes.data, int(trim), lay.gz, self.TW, 0, lay.n_classes)
+                    if rc != 0:
+                        raise OSError(L.bdx_io_last_error().decode())
+                self.busy["write_s"] += time.perf_counter() - tw0
+                f1.release(b.cur1)  # this batch and everything before it is on disk
+                if f2 is not None:
+                    f2.release(b.cur2)
+                self.free.put(b.buf)
+        except BaseException as e:  # noqa: BLE001
+            self.errors.append(e)
+            for b in iter(self.q_out.get, None):  # keep draining so nobody blocks; the dropped batches' buffers go back
+                self.give_back(b)
+
+    def run(self):
+        tr = threading.Thread(target=self.reader, name="bdx-reader")
+        tw = threading.Thread(target=self.writer, name="bdx-writer-0")
+        tks = [threading.Thread(target=self.worker, args=(k,), name=f"bdx-classify-{k}") for k in range(len(self.classifiers))]
+        tr.start()
         tw.start()
-    try:
-        if N > 1:
+        try:
             for tk in tks:
                 tk.start()
             for tk in tks:
                 tk.join()
-        else:
-            while True:
-                item = q_in.get()
-                if item is None:
-                    break
-                if errors:
-                    free.put(item[-1])
-                    continue
-                out, witem, dt = classify_batch(classifiers[0], item)
-                busy["classify_s"] += dt
-                busy["batches"] += 1
-                if on_batch is not None:
-                    on_batch(out)
-                for qw in q_outs:
-                    qw.put(witem)
-    except BaseException as e:  # noqa: BLE001
-        errors.append(e)
-        for tk in tks:  # (the workers drain q_in once they see the error, the reader stops on it)
-            if tk.ident is not None:
-                tk.join()
-        while True:  # (what is left: everything, or — behind the workers — the end mark they passed on)
-            item = q_in.get()
-            if item is None:
-                break
-            free.put(item[-1])
-    finally:
-        for w in parked.values():  # (only after an error: results behind a batch that never came)
-            free.put(w[10])
-        parked.clear()
-        for qw in q_outs:
-            qw.put(None)
-        tr.join()
-        for tw in tws:
+        except BaseException as e:  # noqa: BLE001
+            self.errors.append(e)
+            for tk in tks:  # (the workers drain q_in once they see the error, the reader stops on it)
+                if tk.ident is not None:
+                    tk.join()
+            for b in iter(self.q_in.get, None):  # (what is left: everything, or — behind the workers — the end mark they passed on)
+                self.give_back(b)
+        finally:
+            for b in self.parked.values():  # (only after an error: results behind a batch that never came)
+                self.give_back(b)
+            self.parked.clear()
+            self.q_out.put(None)
+            tr.join()
             tw.join()
-        f1.close()
-        if f2 is not None:
-            f2.close()
-        with _BUFFER_POOL_LOCK:
-            for b in bufs:  # (every thread has been joined: nobody holds a set any more)
-                if len(_BUFFER_POOL) < _BUFFER_POOL_MAX:
-                    _BUFFER_POOL.append(b)
+            self.f1.close()
+            if self.f2 is not None:
+                self.f2.close()
+            with _BUFFER_POOL_LOCK:
+                for b in self.bufs:  # (every thread has been joined: nobody holds a set any more)
+                    if len(_BUFFER_POOL) < _BUFFER_POOL_MAX:
+                        _BUFFER_POOL.append(b)
+
+
+def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
+                 classifiers: list, batch_reads: int, on_batch=None, timings: Optional[dict] = None) -> None:
+    """Native counterpart of core._demux: index -> pack -> ONE C-ABI classify call -> in-order write, as a pipeline of
+    threads (reader | one classify thread per context | writer; the native calls release the GIL).  The classify
+    threads take the batches from the reader as they come free and a reorder step hands the results to the writer
+    strictly by batch id, so per-file order is input order exactly as with the reference's single writer task
+    (core.jl:139-148) and the files are those of a single context.  ``on_batch`` is called under a lock."""
+    t_wall = time.perf_counter()
+    layout = OutputLayout(config, output_directory, prefix1, prefix2, fastq2 is not None)
+    run = _NativeRun(fastq1, fastq2, layout, list(classifiers), batch_reads, on_batch)
+    run.run()
     if timings is not None:  # busy seconds of the three overlapped stages (reader = index + pack | classify | writer)
-        if N > 1:  # (classify_s: summed over the contexts, which overlap each other)
-            busy["classify_s"] = sum(per_dev_s)
-            busy["batches"] = sum(per_dev_b)
-            busy["classify_s_per_device"] = per_dev_s
-            busy["batches_per_device"] = per_dev_b
+        busy = run.busy
+        busy["classify_s"] = sum(run.per_dev_s)  # (summed over the contexts, which overlap each other)
+        busy["batches"] = sum(run.per_dev_b)
+        if len(run.classifiers) > 1:
+            busy["classify_s_per_device"] = run.per_dev_s
+            busy["batches_per_device"] = run.per_dev_b
         busy["wall_s"] = time.perf_counter() - t_wall
-        busy["threads"] = T
+        busy["threads"] = run.T
         timings.update(busy)
-    if errors:
-        raise errors[0]
+    if run.errors:
+        raise run.errors[0]

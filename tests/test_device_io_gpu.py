@@ -333,6 +333,14 @@ def test_device_errors_propagate_instead_of_hanging(tmp_path):
     assert isinstance(r.get("err"), OSError), r
     r = _in_thread(lambda: run_dev(good, str(tmp_path / "missing_R2.fastq"), bc, str(tmp_path / "o2"), _batch_reads=100))
     assert isinstance(r.get("err"), OSError), r
+    # the writer fails while most batches are still to come: a directory stands where the busiest output file goes
+    # (open() gives EISDIR on the host; nothing is wrong on the device)
+    ref = tmp_path / "ref"
+    run_nat(good, bc, str(ref), _batch_reads=1000)
+    busiest = max(os.listdir(ref), key=lambda f: os.path.getsize(ref / f))
+    (tmp_path / "o4" / busiest).mkdir(parents=True)
+    r = _in_thread(lambda: run_dev(good, bc, str(tmp_path / "o4"), _batch_reads=100))
+    assert isinstance(r.get("err"), OSError), r
     # the context is usable afterwards: a good run in the same process
     r = _in_thread(lambda: run_dev(good, bc, str(tmp_path / "o3"), _batch_reads=1000))
     assert r.get("ok"), r

@@ -324,3 +324,8 @@ def test_merged_tables_decode_like_one_table():
     s1.add_device_tables(whole, cfg)
     s2.add_device_tables(merge_stats_tables([part1, part2]), cfg)
     assert vars(s1) == vars(s2) and s1.bc1_pos_counts
+    # one context: the merge of a single table is that table (execute_demultiplexing always merges)
+    whole[0]["len"] = (np.zeros((0, 2), dtype=np.int64), 7)  # (a table without rows keeps its key0)
+    m = merge_stats_tables([whole])
+    for name, (tab, key0) in whole[0].items():
+        assert m[0][name][1] == key0 and m[0][name][0].dtype == tab.dtype and np.array_equal(m[0][name][0], tab), name
