@@ -38,6 +38,7 @@
 #include <cstdlib>
 
 #include "bdx_core.h"
+#include "bdx_read_index.h"
 #include "bdx_sweep_col.h"
 
 // a launcher that refuses its plan says where (stderr, only with BDX_TRACE_LAUNCH set: developer aid)
@@ -48,6 +49,10 @@ namespace {
 struct WaveArgs {
     double max_error_rate, min_delta;  // the two doubles of the reducers (classification.jl:632-713)
     int counts_stride2;
+    // LEAN forms: the multiplier (bdx_read_index.h) of the planned read length max_len, worked out on the host: a tile of
+    // equal-length reads of that length takes it from here.  (In the four bytes the pointer's alignment left free: no other
+    // field moves, and the hidden arguments behind the block — the grid's sizes — stay where every form reads them.)
+    uint32_t rix_mul;
     const uint8_t *seq;
     const long long *off;
     long long n_reads;
@@ -92,7 +97,7 @@ struct WaveArgs {
     // its slot, so that every load is an aligned 16-byte vector)
     int slot;                // flat positions per slot
     int vps, vps_inv;        // slot / 16 and ceil(2^16 / vps)
-    int max_len;             // the read length the scan was planned for: longer reads are handed on
+    int max_len;             // the read length the launch was planned for (pairs mode: longer reads are handed on; LEAN forms: see rix_mul)
     int win_sfe, win_so, win_efe, win_eo;  // window mode: the pass's ref_search_range (start / end: from the read's end?, offset)
     int cpr;                 // 16-diagonal chunks scanned per read
     int cpr_inv;             // ceil(2^16 / cpr)
@@ -152,15 +157,18 @@ typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
 // DOT: the four 2-bit codes of a word are gathered by one dot product (code_k * 4^k summed: v_dot4_u32_u8 with the weights
 // 1, 4, 16, 64) instead of three shift-or steps; the weights live in a register, which only the forms with registers to
 // spare take (the kernel's LEAN forms).  Same p2 either way.
+// m7, m3: the byte masks 0x07070707 and 0x03030303 as arguments: the LEAN forms keep them in vector registers (eight ANDs
+// per vector, the cheap operand class instead of a literal's); every other form passes the constants and compiles as before.
 template <bool EXACT, bool DOT>
-__device__ __forceinline__ void pack16(const u32x4 v, uint32_t &p2, uint32_t &nlo, uint32_t &nhi, uint32_t &sad) {
+__device__ __forceinline__ void pack16(const u32x4 v, uint32_t &p2, uint32_t &nlo, uint32_t &nhi, uint32_t &sad, const uint32_t m7 = 0x07070707u,
+                                       const uint32_t m3 = 0x03030303u) {
     constexpr uint32_t CODE_LO = 0x03020100u, CODE_HI = 0x04040404u;  // idx 0..3 -> 0..3, 4..7 -> 4
     constexpr uint32_t EXP_LO = 0x47544341u /* G T C A */, EXP_HI = 0x4E000000u /* idx 7: N */;
     uint32_t u[4], t2[4];
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
         const uint32_t x = v[w];
-        const uint32_t sel = (x >> 1) & 0x07070707u;
+        const uint32_t sel = (x >> 1) & m7;
         uint32_t n4 = __builtin_amdgcn_perm(CODE_HI, CODE_LO, sel);
         const uint32_t e = __builtin_amdgcn_perm(EXP_HI, EXP_LO, sel);
         if (EXACT) {
@@ -174,7 +182,7 @@ __device__ __forceinline__ void pack16(const u32x4 v, uint32_t &p2, uint32_t &nl
         u[w] = n4 | (n4 >> 4);  // bytes 0 and 2: two 4-bit codes each
         // 2-bit codes (x >> 1) & 3 of the four bytes gathered into one byte: the low one (DOT) or the top one
         if (DOT) {
-            t2[w] = __builtin_amdgcn_udot4(sel & 0x03030303u, 0x40100401u, 0u, false);
+            t2[w] = __builtin_amdgcn_udot4(sel & m3, 0x40100401u, 0u, false);
         } else {
             const uint32_t t6 = (x & 0x06060606u) << 5;
             const uint32_t a = t6 | (t6 << 6);
@@ -475,6 +483,9 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
     // bytes of tile k + 1 are requested while tile k is worked on, its offsets one tile earlier still, so the HBM
     // latency of neither is ever at the head of a tile.
     const int nwaves = (int)(gridDim.x * (blockDim.x >> 6));  // (32-bit: tile numbers stay in scalar registers)
+    // (Workgroup major: the tiles of the last, partial round go to every wave of the first few workgroups.  Dealt with the wave
+    // index major — wave x workgroups + workgroup — they would go to a wave or two of every workgroup; measured, the step is
+    // 0.6 % faster by the medians and the run sets overlap: DESIGN.md §4, round 12.)
     int tile = (int)(blockIdx.x * (blockDim.x >> 6)) + wv;
     // geometry of a tile's span from its offsets (lanes 0 .. nr hold off[r0 + lane]); everything wave-uniform
     struct Geo {
@@ -692,14 +703,16 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
         }
 
         // ---- bytes (requested one tile ago): registers -> 2-bit / 4-bit images ----
+        uint32_t m7 = 0x07070707u, m3 = 0x03030303u;
+        if (LEAN) asm volatile("" : "+v"(m7), "+v"(m3));  // (in vector registers: a literal operand slows the AND down)
 #pragma unroll
         for (int u = 0; u < NV; ++u) {
             const int k = 64 * u + lane;
             if (64 * u < nvec) {  // wave-uniform
                 uint32_t p2 = 0, nlo = 0, nhi = 0, sad = 0;
-                if (k < nvec && !BDX_DBG(32)) pack16<false, LEAN>(v[u], p2, nlo, nhi, sad);
+                if (k < nvec && !BDX_DBG(32)) pack16<false, LEAN>(v[u], p2, nlo, nhi, sad, m7, m3);
                 if (__builtin_amdgcn_ballot_w64(sad != 0)) {  // some byte is neither A, C, G, T nor N (rare)
-                    if (sad != 0) pack16<true, LEAN>(v[u], p2, nlo, nhi, sad);
+                    if (sad != 0) pack16<true, LEAN>(v[u], p2, nlo, nhi, sad, m7, m3);
                 }
                 if (k < nvec) {
                     img2_lane[64 * u] = p2;
@@ -751,7 +764,8 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
         {
             const int my = (!SCAT && lane < nr) ? fb[lane + 1] - fb[lane] : 0;
             const int l0 = __builtin_amdgcn_readfirstlane(my);
-            ulen = (l0 > 0 && !__builtin_amdgcn_ballot_w64(lane < nr && my != l0)) ? l0 : 0;
+            // (LEAN forms: reads of one base have no multiplier, bdx_read_index.h — and no seed: such a tile counts as mixed)
+            ulen = (l0 > (LEAN ? 1 : 0) && !__builtin_amdgcn_ballot_w64(lane < nr && my != l0)) ? l0 : 0;
         }
 
         // ---- sweeps: lane = one record = one (read, barcode, window) ----
@@ -1191,8 +1205,14 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                     }
                     if (ong) {
                         uint32_t hits = 0;
-                        w0 = img2[g];
-                        w1 = img2[g + 1];
+                        if constexpr (LEAN && !GEN) {
+                            // (the flat scan, g = g0i + lane: the lane's base register and the trip as an instruction offset)
+                            w0 = img2_lane[g0i];
+                            w1 = img2_lane[g0i + 1];
+                        } else {
+                            w0 = img2[g];
+                            w1 = img2[g + 1];
+                        }
                         gp = (uint32_t)g << 20;
                         const uint32_t wm = __builtin_amdgcn_alignbit(w1, w0, 16);  // bases 8 .. 23 of the group's window
                         uint32_t Wk[16];
@@ -1292,8 +1312,15 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
         int ns = 0;  // records of the tile so far (wave-uniform)
         if constexpr (!PAIRS) {
             const int fb0 = fb[0];
-            const float rinv = ulen > 0 ? 1.0f / (float)ulen : 0.0f;
-            const float ginv = total > 0 ? (float)nr / (float)total : 0.0f;
+            const float rinv = (!LEAN && ulen > 0) ? 1.0f / (float)ulen : 0.0f;
+            // LEAN forms: floor(x / ulen) by one multiply-high (bdx_read_index.h).  The multiplier of the planned read length
+            // comes with the arguments (read here, see kargs); a tile of another length works its own out
+            uint32_t rmul = 0u;
+            if (LEAN && ulen > 0) {
+                const KArgs ka = kargs();
+                rmul = ka->max_len == ulen ? ka->rix_mul : bdx_read_index_mul((uint32_t)ulen);
+            }
+            const float ginv = (total > 0 && !(LEAN && ulen > 0)) ? (float)nr / (float)total : 0.0f;  // (only mixed-length tiles use it)
             for (int k0 = 0; k0 < nh; k0 += 64) {
                 const int k = k0 + lane;
                 int new0 = -1, new1 = -1;  // record slots this lane opened
@@ -1314,6 +1341,11 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                         t = (int)(((uint32_t)(pos >> 4) * (uint32_t)a.vps_inv) >> 16);
                         ok = t < nr;
                         t = ok ? t : 0;
+                    } else if (LEAN && ulen > 0) {
+                        // (x < 0, a position in the head padding, is a huge unsigned x: t >= nr, like a position behind the last read)
+                        const uint32_t tu = bdx_mul_hi((uint32_t)(pos - fb0), rmul);
+                        ok = tu < (uint32_t)nr;
+                        t = ok ? (int)tu : 0;
                     } else if (ulen > 0) {
                         const int x = pos - fb0;
                         t = (int)((float)x * rinv);
@@ -1932,7 +1964,8 @@ void fill_args(WaveArgs &a, const BdxDevCfg &cfg, const BdxWavePlan &wp, int his
     a.slot = 0;
     a.vps = 1;
     a.vps_inv = 65536;
-    a.max_len = 0;
+    a.max_len = wp.read_len_hint;
+    a.rix_mul = bdx_read_index_mul((uint32_t)(wp.read_len_hint > 0 ? wp.read_len_hint : 0));
     a.win_sfe = a.win_efe = a.win_so = a.win_eo = 0;
     a.cpr = 1;
     a.cpr_inv = 65536;

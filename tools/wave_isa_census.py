@@ -10,7 +10,9 @@ Prints the resource lines (VGPRs, SGPRs, scratch), the loops of the function (fo
 static v_readlane / v_writelane inside the per-tile loop (all of them, and those on the registers the compiler spills
 SGPRs into: the VGPRs some v_writelane writes), and the VALU counts of the seed scan's round loop (the trips of a round
 are unrolled in it: five in the headline form, one round per tile), of the loops nested in it (the hit append, once per
-round) and of the first sweep loop.  Static counts: what one pass through a loop's body issues; how often each body runs
+round) and of the first sweep loop.  Per loop, and for the tile loop's own body, it also counts the cheap-class VALU
+instructions (v_and / or / xor / add / sub / lshrrev) that take a scalar register or a 32-bit literal as a source: the dearer
+operand classes of tools/ubench_ops.hip (columns +sgpr, +lit).  Static counts: what one pass through a loop's body issues; how often each body runs
 depends on the data (the per-round lines show it for L layers / hits of the fullest lane over the round).
 """
 from __future__ import annotations
@@ -64,6 +66,38 @@ def is_valu(l: str) -> bool:
 
 def is_salu(l: str) -> bool:
     return re.match(r"\s+s_(?!waitcnt|nop|branch|cbranch|setprio|barrier|sleep)", l) is not None
+
+
+# The cheap class of tools/ubench_ops.hip: 2.4 clk with vector-register operands, 3.5 with a literal, 4.3 with a scalar register
+CHEAP = ("v_and_b32", "v_or_b32", "v_xor_b32", "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_lshrrev_b32")
+
+
+def dear_operand(l: str):
+    """"sgpr" / "lit" if the line is a cheap-class VALU instruction with a scalar-register or a 32-bit literal source operand
+    (inline constants -16 .. 64 are neither), else None."""
+    m = re.match(r"\s+(v_\w+?)(?:_e32|_e64)?\s+(.*)", l)
+    if not m or m.group(1) not in CHEAP:
+        return None
+    kind = None
+    for op in m.group(2).split(";")[0].split(",")[1:]:
+        op = op.strip()
+        if re.match(r"(s\d+|s\[|vcc|exec|ttmp|m0)", op):
+            return "sgpr"
+        if re.match(r"-?(0x[0-9a-fA-F]+|\d+)$", op) and not -16 <= int(op, 0) <= 64:
+            kind = "lit"
+    return kind
+
+
+def count_dear(body, a, b, skip=()):
+    """(cheap-class VALU with a scalar-register operand, with a literal operand) of lines a..b, without the ranges in skip."""
+    s = t = 0
+    for i in range(a, b + 1):
+        if any(x <= i <= y for x, y in skip):
+            continue
+        k = dear_operand(body[i])
+        s += k == "sgpr"
+        t += k == "lit"
+    return s, t
 
 
 def loops(body):
@@ -136,12 +170,20 @@ def main() -> None:
     trip = min(trips, key=lambda x: x[1] - x[0]) if trips else None
     layer = [x for x in nested(trip) if not nested(x) and (x == wr or has(x, r"v_mbcnt_lo"))] if trip else []
     print()
-    print("%-12s %13s  %5s %5s %4s" % ("loop", "lines", "VALU", "SALU", "LDS"))
+    # +sgpr / +lit: cheap-class VALU (v_and / or / xor / add / sub / lshrrev) of the loop's own body with a scalar-register / a
+    # 32-bit literal source operand — the dearer operand classes of tools/ubench_ops.hip
+    print("%-12s %13s  %5s %5s %4s %5s %4s" % ("loop", "lines", "VALU", "SALU", "LDS", "+sgpr", "+lit"))
     for x in inner:
         depth = sum(1 for y in inner if y[0] <= x[0] and x[1] <= y[1] and y != x)
-        v, s_, d = count(body, x[0], x[1], [(y[0], y[1]) for y in nested(x)])
+        skip = [(y[0], y[1]) for y in nested(x)]
+        v, s_, d = count(body, x[0], x[1], skip)
+        ds, dl = count_dear(body, x[0], x[1], skip)
         tag = "scan round" if x == trip else ("append, per layer" if x in layer else "")
-        print("%-12s %6d-%-6d  %5d %5d %4d  %s%s" % (x[2], x[0], x[1], v, s_, d, "  " * depth, tag))
+        print("%-12s %6d-%-6d  %5d %5d %4d %5d %4d  %s%s" % (x[2], x[0], x[1], v, s_, d, ds, dl, "  " * depth, tag))
+    # the tile loop's own body (transcode, per-tile tables, verdicts: everything outside the loops above)
+    ds, dl = count_dear(body, tile[0], tile[1], [(y[0], y[1]) for y in nested(tile)])
+    v, s_, d = count(body, tile[0], tile[1], [(y[0], y[1]) for y in nested(tile)])
+    print("%-12s %6d-%-6d  %5d %5d %4d %5d %4d  tile loop, own body" % (tile[2], tile[0], tile[1], v, s_, d, ds, dl))
     if trip:
         tv, ts, _ = count(body, trip[0], trip[1], [(y[0], y[1]) for y in layer])
         per = [count(body, y[0], y[1]) for y in layer]
