@@ -854,6 +854,14 @@ int64_t bdx_last_list_reads(bdx_ctx *ctx) {
     return (int64_t)v;
 }
 
+int64_t bdx_last_mid_reads(bdx_ctx *ctx) {
+    if (!ctx || !ctx->d_maxlen.p) return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return -1;
+    unsigned int v = 0;
+    if (hipMemcpy(&v, &ctx->scratch(true)->mid_count, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return (int64_t)v;
+}
+
 int64_t bdx_rejected_windows(bdx_ctx *ctx) {
     if (!ctx || !ctx->d_dbg.p) return 0;
     unsigned int rej[2] = {0, 0};  // [0] refused by the exact kernel, [1] found unwritten by the poison checker

@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     "bdx_get_reduced_counts",
     # DemuxStats histograms (summary = true), collected on the device
     "bdx_stats_shape", "bdx_get_stats",
-    "bdx_window_uploads", "bdx_band_launches", "bdx_wave_launches", "bdx_pair_launches", "bdx_pipelined_calls", "bdx_staged_downloads", "bdx_last_list_reads", "bdx_rejected_windows",
+    "bdx_window_uploads", "bdx_band_launches", "bdx_wave_launches", "bdx_pair_launches", "bdx_pipelined_calls", "bdx_staged_downloads", "bdx_last_list_reads", "bdx_last_mid_reads", "bdx_rejected_windows",
     "bdx_debug_rejected_windows_total", "bdx_last_launches",
     # device FASTQ pipeline (bdx_fastq.hip)
     "bdx_fq_index_device", "bdx_fq_pack_device", "bdx_fq_gather_device",
@@ -231,6 +231,8 @@ def load_library(path: Optional[str] = None):
     L.bdx_staged_downloads.argtypes = [vp]
     L.bdx_last_list_reads.restype = C.c_int64
     L.bdx_last_list_reads.argtypes = [vp]
+    L.bdx_last_mid_reads.restype = C.c_int64
+    L.bdx_last_mid_reads.argtypes = [vp]
     L.bdx_rejected_windows.restype = C.c_int64
     L.bdx_rejected_windows.argtypes = [vp]
     L.bdx_debug_rejected_windows_total.restype = C.c_int64
@@ -513,6 +515,11 @@ class HipClassifier:
     def last_list_reads(self) -> int:
         """Reads the first filter launch of the last classify call handed on through its device-side list."""
         return int(self.lib.bdx_last_list_reads(self.h))
+
+    @property
+    def last_mid_reads(self) -> int:
+        """Reads the pairs mode of the last classify call handed on through its own device-side list."""
+        return int(self.lib.bdx_last_mid_reads(self.h))
 
     @property
     def staged_downloads(self) -> int:

@@ -384,6 +384,11 @@ int64_t bdx_staged_downloads(const bdx_ctx *ctx);
  * -1: the device could not be read. */
 int64_t bdx_last_list_reads(bdx_ctx *ctx);
 
+/* Reads the pairs mode of the LAST classify call handed on through its own device-side list (tier 1's list is its input):
+ * the length of the list the full-budget stage walks behind it.  Synchronises the context's stream; a test-visibility
+ * counter like bdx_last_list_reads.  -1: the device could not be read. */
+int64_t bdx_last_mid_reads(bdx_ctx *ctx);
+
 /* Hand-over windows the exact kernel refused because they do not end inside the read ("not a window": defence in
  * depth behind the filter kernels, classification.jl:238-445 then runs over the whole pass window).  A correct
  * producer / consumer pair never leaves one: the counter must read 0 (synchronises the stream); the test-suite runs

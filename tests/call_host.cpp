@@ -101,8 +101,10 @@ static void report_call(int i, int rc, const std::string &err, const CallPlan &p
 // The launches a plan holds, one line per classify kernel in the order of the stages: family, then blocks, threads, tile and
 // list flag as the plan states them (the launchers take the grid from the plan; tests/golden/call_plans.json holds these lines
 // as the launchers of the commit before computed them), then the template arguments the plan decides
-//   bitpar: R SEED DIAG NW WL | wave, pairs: RW SPLIT KEND WINM | generic: BS reg_rows clean uniform_m band_roll (the ladder of
-//   bdx_launch_generic spells the instantiation from these: tests/kernel_lattice.py generic_name)
+//   bitpar: R SEED DIAG NW WL | generic: BS reg_rows clean uniform_m band_roll (the ladder of bdx_launch_generic spells the
+//   instantiation from these: tests/kernel_lattice.py generic_name) | wave, pairs: RW SPLIT KEND WINM, then what the dispatch
+//   ladders of bdx_wave_kernel.h and the leaves in bdx_wave.hip / bdx_wave_win.hip / bdx_pairs.hip read: q track_from span_cap slot
+//   gen (split ? ranged : dual || ranged) pairs_kb nw groups (tests/kernel_lattice.py wave_name / pairs_name)
 static void report_launches(int i, const CallPlan &p, const BdxPlanOut &po) {
     int j = 0;
     const auto line = [&](const char *family, long long blocks, int threads, int tile, int list, int a, int b, int c, int d, int e) {
@@ -114,8 +116,13 @@ static void report_launches(int i, const CallPlan &p, const BdxPlanOut &po) {
         line("bitpar", b.grid, 256, b.reads_per_block, list, b.reads_per_block, sp.enabled != 0, diag, diag && b.diag_nw > 5 ? 10 : 5,
              b.word_bytes == 8 ? 1 : b.word_bytes == 16 ? 2 : 0);
     };
-    const auto wave = [&](const BdxWavePlan &w) { line("wave", w.grid, 64 * w.waves, w.rw, 0, w.rw, w.split, w.kend, w.winm, 0); };
-    const auto pairs = [&](const BdxWavePlan &w, int list) { line("pairs", w.grid, 64 * w.waves, 16, list, 16, w.split, w.kend, 0, 0); };
+    const auto seeded = [&](const char *family, const BdxWavePlan &w, int tile, int list, int winm) {
+        const int gen = w.split ? w.ranged != 0 : (po.dev.is_dual || w.ranged != 0);
+        printf("c%d.launch%d %s %lld %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d\n", i, j++, family, w.grid, 64 * w.waves, tile, list, tile, w.split, w.kend, winm, w.q,
+               w.track_from, w.span_cap, w.slot, gen, w.pairs_kb, w.nw, w.groups);
+    };
+    const auto wave = [&](const BdxWavePlan &w) { seeded("wave", w, w.rw, 0, w.winm); };
+    const auto pairs = [&](const BdxWavePlan &w, int list) { seeded("pairs", w, 16, list, 0); };
     const auto generic = [&](long long blocks, int list) {
         line("generic", blocks, po.plan.threads, po.plan.threads, list, po.plan.threads, po.plan.reg_rows, po.plan.clean, po.plan.uniform_m, po.plan.band_roll);
     };

@@ -10,8 +10,9 @@ planner took the grids over from the launchers, whose formulas that commit's dri
 ASan / UBSan (no Python process loads sanitised code).  The band fields (c<i>.band_t1 / .band_exact) were recorded before the
 planner held them, from that commit's band_cfg formula (enqueue, bdx_abi.cpp) in a scratch copy of this driver fed from that
 commit's plans.  The last four arguments of the `generic` launch lines (reg_rows, clean, uniform_m, band_roll: what the ladder of
-bdx_launch_generic spells the instantiation from) were added later from the create-time plan; every other value of the file is
-as it was recorded.
+bdx_launch_generic spells the instantiation from) were added later from the create-time plan, and so were the arguments of the
+`wave` and `pairs` launch lines behind RW SPLIT KEND WINM (q track_from span_cap slot gen pairs_kb nw groups: what the dispatch
+ladders of bdx_wave_kernel.h read); every other value of the file is as it was recorded.
 
 The same driver answers for the two other host-only pieces of a call: the read length of a batch (bdx_batch_len), held against
 the rule written out below over its whole input lattice, and the turn of the scratch halves (BdxScratchTurn), held against
