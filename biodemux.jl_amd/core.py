@@ -196,7 +196,7 @@ def _close_all(classifiers) -> None:
 def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxConfig], object]] = None,
                            _batch_reads: int = DEFAULT_BATCH_READS, _io: str = "auto", device: int = 0,
                            devices=None, _timings: Optional[dict] = None, _gzip: str = "host", _gunzip: str = "host",
-                           **kw):
+                           _gzip_level: int = 1, **kw):
     """execute_demultiplexing(FASTQ_file, barcode_file, output_directory; kwargs...)      core.jl:500
     execute_demultiplexing(FASTQ_file1, FASTQ_file2, barcode_file, output_directory; ...)  core.jl:360
 
@@ -214,7 +214,9 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
     classify_s_per_device and batches_per_device, classify_s being their sum).
     ``_gzip`` selects who compresses gzip output: "host" (zlib on the writer's threads) or "device" (csrc/bdx_deflate.hip:
     the device pipeline deflates each batch's blocks and downloads finished gzip members; needs ``_io="device"``, inert
-    when the output is not gzip; _timings then also holds deflate_s, plain_bytes and compressed_bytes).
+    when the output is not gzip; _timings then also holds deflate_s, plain_bytes, compressed_bytes and gzip_level).
+    ``_gzip_level`` (1 or 2, with ``_gzip="device"`` only) is the device encoder's level: 1 is the fast one, 2 finds
+    better matches and writes smaller files (bdx_fq_deflate_level_device).
     ``_gunzip`` selects who inflates a ``.gz`` input: "host" (zlib on host threads, csrc/bdx_io.cpp) or "device"
     (csrc/bdx_inflate.hip: the device pipeline uploads the compressed members and inflates them on the GPU, checking
     every member's CRC-32 and ISIZE there; needs ``_io="device"``; inert for a plain input; a ``.gz`` input must be a
@@ -235,6 +237,10 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         raise ValueError("_gzip must be 'host' or 'device'")
     if _gzip == "device" and _io != "device":  # (no silent fallback to the host deflate)
         raise ValueError("_gzip='device' compresses inside the device FASTQ pipeline: it needs _io='device'")
+    if isinstance(_gzip_level, bool) or _gzip_level not in (1, 2):
+        raise ValueError("_gzip_level must be 1 or 2")
+    if _gzip_level != 1 and _gzip != "device":  # (the host writers have one level)
+        raise ValueError("_gzip_level selects a level of the device encoder: it needs _gzip='device'")
     if _gunzip not in ("host", "device"):
         raise ValueError("_gunzip must be 'host' or 'device'")
     if _gunzip == "device" and _io != "device":  # (no silent fallback to the host inflate)
@@ -313,7 +319,8 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
             _timings["pre_s"] = (_dt.datetime.now() - start_time).total_seconds()  # everything before the first batch can be read
         if _io == "device":
             deviceio.demux_device(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers[0], _batch_reads,
-                                  _timings, gzip_device=_gzip == "device", gunzip_device=_gunzip == "device")
+                                  _timings, gzip_device=_gzip == "device", gunzip_device=_gunzip == "device",
+                                  gzip_level=int(_gzip_level))
         elif use_native:
             t_call = _dt.datetime.now()
             nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers, _batch_reads,

@@ -11,7 +11,7 @@ Batches of ``batch_reads`` records flow through three overlapped stages:
 Same files, bytes, counters and reports as nativeio.demux_native.
 
 With ``gzip_device`` (``execute_demultiplexing(..., _gzip="device")``) and gzip output the calling thread also deflates
-the batch's blocks on the device (csrc/bdx_deflate.hip, bdx_fq_deflate_device): only finished gzip members come back
+the batch's blocks on the device (csrc/bdx_deflate.hip, bdx_fq_deflate_level_device): only finished gzip members come back
 and the writer appends them verbatim (bdx_fq_write_blocks_raw); the files then gunzip to the same bytes.
 
 With ``gunzip_device`` (``execute_demultiplexing(..., _gunzip="device")``) a ``.gz`` input that is a chain of size-tagged
@@ -295,14 +295,14 @@ class _Slots:
 
 def _deflate(classifier, d_out: _DevBuf, d_gz: _DevBuf, blocks, n_classes: int, busy: dict):
     """The batch's gathered blocks in d_out (the streams' blocks are one run of n_classes * len(blocks) blocks: one
-    deflate call) -> finished gzip members in d_gz; -> (their blocks, their bytes)"""
+    deflate call, at the level in busy["gzip_level"]) -> finished gzip members in d_gz; -> (their blocks, their bytes)"""
     t_z = time.perf_counter()
     lib = classifier.lib
     cb_all = np.concatenate([cb for _, cb, _ in blocks])
     d_gz.ensure(int(lib.bdx_fq_deflate_bound(cb_all.ctypes.data, len(cb_all))))
     zb = np.zeros(len(cb_all), dtype=np.int64)
-    classifier._check(lib.bdx_fq_deflate_device(classifier.h, d_out.p, cb_all.ctypes.data, len(cb_all), d_gz.p, d_gz.cap,
-                                                zb.ctypes.data))
+    classifier._check(lib.bdx_fq_deflate_level_device(classifier.h, busy["gzip_level"], d_out.p, cb_all.ctypes.data, len(cb_all),
+                                                      d_gz.p, d_gz.cap, zb.ctypes.data))
     busy["plain_bytes"] += int(cb_all.sum())
     zblocks, pos = [], 0
     for k, (_, _, prefix) in enumerate(blocks):
@@ -363,11 +363,12 @@ def _write_loop(q_w, slots: _Slots, errors: list, rt: _Runtime, L, layout: Outpu
 
 def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
                  classifier, batch_reads: int, timings: Optional[dict] = None, gzip_device: bool = False,
-                 gunzip_device: bool = False) -> None:
+                 gunzip_device: bool = False, gzip_level: int = 1) -> None:
     """Device counterpart of nativeio.demux_native (same arguments but ``on_batch``: the HIP classifier keeps the
     summary tables itself).  ``classifier`` must be the HIP classifier.  ``gzip_device``: gzip output is compressed by
     bdx_fq_deflate_device after the gathers, only finished gzip members are downloaded and the writer appends them as
-    they are (inert when the output is not gzip).  ``gunzip_device``: every input whose name ends in .gz is uploaded
+    they are (inert when the output is not gzip), at ``gzip_level`` (1 or 2: bdx_fq_deflate_level_device).
+    ``gunzip_device``: every input whose name ends in .gz is uploaded
     compressed and inflated by bdx_fq_inflate_device (inert for a plain input; ValueError for a .gz that is no chain of
     size-tagged members of at most bdx_fq_inflate_member_max() bytes)."""
     if not hasattr(classifier, "classify_device"):
@@ -385,7 +386,7 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
     n_classes = layout.n_classes
     dev_gz = bool(gzip_device) and bool(layout.gz)
     if dev_gz:
-        busy.update(deflate_s=0.0, plain_bytes=0, compressed_bytes=0)
+        busy.update(deflate_s=0.0, plain_bytes=0, compressed_bytes=0, gzip_level=int(gzip_level))
 
     ins = []
     s_main = s_copy = 0

@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     # device FASTQ pipeline (bdx_fastq.hip)
     "bdx_fq_index_device", "bdx_fq_pack_device", "bdx_fq_gather_device",
     # device DEFLATE of the pipeline's gzip output (bdx_deflate.hip)
-    "bdx_fq_deflate_chunk", "bdx_fq_deflate_bound", "bdx_fq_deflate_device",
+    "bdx_fq_deflate_chunk", "bdx_fq_deflate_bound", "bdx_fq_deflate_device", "bdx_fq_deflate_levels", "bdx_fq_deflate_level_device",
     # device inflate of the pipeline's .gz input (bdx_inflate.hip)
     "bdx_fq_inflate_member_max", "bdx_fq_inflate_device",
 ]
@@ -253,6 +253,10 @@ def load_library(path: Optional[str] = None):
     L.bdx_fq_deflate_bound.argtypes = [vp, C.c_int32]
     L.bdx_fq_deflate_device.restype = C.c_int32
     L.bdx_fq_deflate_device.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int64, vp]
+    L.bdx_fq_deflate_levels.restype = C.c_int32
+    L.bdx_fq_deflate_levels.argtypes = []
+    L.bdx_fq_deflate_level_device.restype = C.c_int32
+    L.bdx_fq_deflate_level_device.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int64, vp]
     L.bdx_fq_inflate_member_max.restype = C.c_int32
     L.bdx_fq_inflate_member_max.argtypes = []
     L.bdx_fq_inflate_device.restype = C.c_int32

@@ -306,11 +306,23 @@ int32_t bdx_fq_gather_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_l
  * bdx_fq_deflate_device: runs on the context's stream and device and synchronises before it returns.  class_cbytes
  * (HOST memory, n_classes entries) receives the bytes of class c's members, which follow one another in class order
  * from d_out[0]; an empty class has no member and 0 bytes.  Fails with BDX_E_INVALID, writing nothing, when
- * out_cap < bdx_fq_deflate_bound(class_bytes, n_classes). */
+ * out_cap < bdx_fq_deflate_bound(class_bytes, n_classes).
+ *
+ * Levels.  bdx_fq_deflate_levels: how many compression levels the encoder has (2); needs no context and no device.
+ * bdx_fq_deflate_level_device: bdx_fq_deflate_device's contract at the given level.  Level 1 writes exactly
+ * bdx_fq_deflate_device's bytes (that entry is level 1).  Level 2 is the stronger and slower one: matches may start
+ * inside the 256-position sub-block being parsed, every hash keeps its 8 most recent positions, a match gives way to a
+ * literal when the next position's is longer, and the block header is run-length coded; chunk size, member framing, one
+ * block per member, the stored fallback (so bdx_fq_deflate_bound serves both levels), CRC and determinism are level 1's.
+ * A level outside 1 .. bdx_fq_deflate_levels() fails with BDX_E_INVALID and a message: nothing is launched and
+ * class_cbytes is zeroed. */
 int32_t bdx_fq_deflate_chunk(void);
 int64_t bdx_fq_deflate_bound(const int64_t *class_bytes, int32_t n_classes);
 int32_t bdx_fq_deflate_device(bdx_ctx *ctx, const uint8_t *d_in, const int64_t *class_bytes, int32_t n_classes,
                               uint8_t *d_out, int64_t out_cap, int64_t *class_cbytes);
+int32_t bdx_fq_deflate_levels(void);
+int32_t bdx_fq_deflate_level_device(bdx_ctx *ctx, int32_t level, const uint8_t *d_in, const int64_t *class_bytes,
+                                    int32_t n_classes, uint8_t *d_out, int64_t out_cap, int64_t *class_cbytes);
 
 /* Device inflate for the pipeline's .gz input (csrc/bdx_inflate.hip): size-tagged gzip members (BGZF, or the 'D','X'
  * members above) already in device memory are decoded, each into a slot of its own in d_out, and every member's CRC-32

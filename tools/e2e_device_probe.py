@@ -2,15 +2,16 @@
 """End-to-end reads/s of execute_demultiplexing on the C2 shape: the native host pipeline (_io="native") against the device
 FASTQ pipeline (_io="device"), each run in a fresh child process (GPU box).
 
-  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device} | --gunzip] [out.json]
+  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device} [--gzip-level 2] | --gunzip] [out.json]
 
 One synthetic FASTQ of N 150 bp reads x 96 barcodes (24 bp), max_error_rate=0.1, on tmpfs (/dev/shm unless E2E_ROOT is
 set); the outputs are checked (total bytes = input bytes).  Prints every run with its stage seconds, then the medians; the
 optional argument receives the same as JSON.
 
 --gzip host: both legs write gzip (gzip_output=True, zlib on the host threads): "native+gz" and "device+gz".  --gzip device
-adds the leg "device+dgz" (_gzip="device": DEFLATE on the GPU) to the same alternating series.  The check then sums the
-ISIZE fields along the members' size tags.  Every leg reports min, median and max wall seconds.
+adds the leg "device+dgz" (_gzip="device": DEFLATE on the GPU) to the same alternating series, and with --gzip-level 2
+the leg "device+dgz2" (_gzip_level=2) as well.  The check then sums the ISIZE fields along the members' size tags.  Every
+leg reports min, median and max wall seconds.
 
 --gunzip: .gz in -> .gz out through the device pipeline only.  The input is written once as 32 KiB 'D','X' members (zlib
 level 1 on host threads) and three legs alternate after one unrecorded warm-up run: "device+gz+hin" (host inflate, host
@@ -101,8 +102,10 @@ def child(mode: str) -> None:
     shutil.rmtree(out, ignore_errors=True)
     tm = {}
     kw = dict(gzip_output=True) if gz else {}
-    if gz == "dgz":
+    if gz in ("dgz", "dgz2"):
         kw["_gzip"] = "device"
+    if gz == "dgz2":
+        kw["_gzip_level"] = 2
     if gin:
         fq += ".gz"
     if gin == "din":
@@ -131,6 +134,11 @@ def main() -> None:
             raise SystemExit("--gzip takes host or device")
         modes = ["native+gz", "device+gz"] + (["device+dgz"] if argv[1] == "device" else [])
         argv = argv[2:]
+        if argv and argv[0] == "--gzip-level":
+            if modes[-1] != "device+dgz" or len(argv) < 2 or argv[1] not in ("1", "2"):
+                raise SystemExit("--gzip-level takes 1 or 2 and goes with --gzip device")
+            modes += ["device+dgz2"] if argv[1] == "2" else []
+            argv = argv[2:]
     gunzip = bool(argv) and argv[0] == "--gunzip"
     if gunzip:
         modes = ["device+gz+hin", "device+dgz+hin", "device+dgz+din"]
