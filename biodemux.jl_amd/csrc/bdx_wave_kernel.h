@@ -499,8 +499,9 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
         const long long r0 = (long long)t * RW;
         g.nr = (int)(n_reads - r0 < RW ? n_reads - r0 : RW);
         const uint32_t ov_lo = (uint32_t)ov, ov_hi = (uint32_t)(ov >> 32);
-        g.span0 = (long long)(((unsigned long long)__builtin_amdgcn_readlane(ov_hi, 0) << 32) | __builtin_amdgcn_readlane(ov_lo, 0));
-        const long long span1 = (long long)(((unsigned long long)__builtin_amdgcn_readlane(ov_hi, g.nr) << 32) | __builtin_amdgcn_readlane(ov_lo, g.nr));
+        // (readlane returns int: the low word goes through uint32_t, or an offset with bit 31 set would sign-extend over the high word)
+        g.span0 = (long long)(((unsigned long long)__builtin_amdgcn_readlane(ov_hi, 0) << 32) | (uint32_t)__builtin_amdgcn_readlane(ov_lo, 0));
+        const long long span1 = (long long)(((unsigned long long)__builtin_amdgcn_readlane(ov_hi, g.nr) << 32) | (uint32_t)__builtin_amdgcn_readlane(ov_lo, g.nr));
         const uintptr_t g0 = (uintptr_t)(a.seq + g.span0);
         g.g0a = g0 & ~(uintptr_t)15;
         g.head = (int)(g0 - g.g0a);

@@ -169,7 +169,26 @@ int32_t bdx_classify_host(bdx_ctx *ctx, const uint8_t *seq_bytes, const int64_t 
  * batch's longest read is measured, the statistics tables may grow), no read-length hint
  * (bdx_set_read_length_hint: the batch is measured), and a batch larger than any before
  * (a hand-over buffer grows: the old one is released with hipFree, which synchronises the
- * device).  Inputs and outputs must stay valid until the stream has passed the call. */
+ * device).  Inputs and outputs must stay valid until the stream has passed the call.
+ * Offsets: d_seq_off[0] may be non-zero and the offsets may lie beyond 2^31 and 2^32; every
+ * address is formed as d_seq_bytes + d_seq_off[i] in 64 bits (d_seq_bytes itself need not
+ * point into the allocation that holds the batch, only the sums must).
+ * Bytes outside [d_seq_off[0], d_seq_off[n_reads]): the kernels fetch read bytes in 16-byte
+ * granules at 16-byte aligned addresses (a tile's or workgroup's contiguous span, a read's
+ * slot or column window), or byte by byte inside a read.  A granule is fetched only when it
+ * holds an address of the closed range d_seq_bytes + [d_seq_off[0], d_seq_off[n_reads]]: up
+ * to 15 bytes in front of the first read and up to 15 behind the last may be LOADED, so
+ * they must be readable — they are whenever the batch lies in a hipMalloc allocation,
+ * whose pages are whole multiples of 16 bytes; for a batch of empty reads the granule of
+ * d_seq_bytes + d_seq_off[0] itself may be loaded, so that must be such an address.  Those bytes
+ * are never INTERPRETED: every position that reaches a seed probe, a sweep or a DP cell is
+ * masked or bounded by its read's own offsets, so what lies around a batch (other reads,
+ * barcode bases, garbage) never changes a result.  Established by reading every fetch site
+ * (geometry / load_bytes, load_scat / scat_geo in bdx_wave_kernel.h; the dense, list and
+ * window-upload forms in bdx_bitpar.hip; the staged span and the unstaged reads in
+ * bdx_device.hip) and held by tests/test_offset_base_gpu.py (hostile surroundings, bases
+ * that cross 2^31 and 2^32).  The same holds for bdx_classify_host's seq_bytes / seq_off,
+ * which uploads only [seq_off[0], seq_off[n_reads]) (or each read's window). */
 int32_t bdx_classify_device(bdx_ctx *ctx, const uint8_t *d_seq_bytes, const int64_t *d_seq_off,
                             int64_t n_reads, const bdx_outputs_t *d_out);
 

@@ -1197,9 +1197,17 @@ def test_host_entry_point_small_batch_forms():
 def test_pipelined_host_upload_equals_the_single_upload(monkeypatch):
     """Large batches of configs with heavier kernels go up in chunks beside the previous chunk's kernels (one classify
     call per chunk on the same context).  Same outputs, counters and statistics as the single upload (BDX_NO_PIPELINE),
-    and a sample against the oracle."""
+    and a sample against the oracle.  The chunked leg classifies the reads where they lie in a sparse host array, at offsets
+    that do not start at 0 and cross 2^32 inside the read in the middle of the batch (every chunk's copy and kernels take
+    seq_off as given, against d_seq - seq_off[0]); the single upload stays at offset 0; the oracle's sample is the 4000 reads
+    around the crossing."""
     bcs = synth.make_barcodes(96, 24)
     seq, off, _ = synth.make_reads(bcs, 1_000_001, 150, seed=651, repeat=dict(frac=0.05))
+    mid = 500_000
+    base = (1 << 32) - int(off[mid]) - 7
+    big = np.empty(base + len(seq) + 64, dtype=np.uint8)  # (pages outside the batch are never touched)
+    big[base: base + len(seq)] = seq
+    assert off[mid] + base < (1 << 32) < off[mid + 1] + base
     for kw in (dict(max_error_rate=0.2, summary=True, min_delta=0.05), dict(max_error_rate=0.2, trim_side=5)):
         cfg = _c2_config(bcs, **kw)
         res = {}
@@ -1209,7 +1217,7 @@ def test_pipelined_host_upload_equals_the_single_upload(monkeypatch):
             else:
                 monkeypatch.setenv("BDX_NO_PIPELINE", "1")
             with H.bdx.HipClassifier(cfg, want_pass=True) as hc:
-                out = hc.classify(seq, off)
+                out = hc.classify(big, off + base) if piped else hc.classify(seq, off)
                 res[piped] = (out, hc.counts.copy(), hc.stats_tables() if cfg.summary else None)
                 # the chunked path really ran (or really did not): a changed threshold must not turn this test into a
                 # comparison of the single upload with itself
@@ -1222,9 +1230,9 @@ def test_pipelined_host_upload_equals_the_single_upload(monkeypatch):
             for p_ in res[True][2]:
                 for name in res[True][2][p_]:
                     assert np.array_equal(res[True][2][p_][name][0], res[False][2][p_][name][0]), (kw, name)
-        k = 4000
-        exp = H.orc.OracleClassifier(cfg, nthreads=16).classify(seq[:off[k]], off[:k + 1])
-        fuzz.assert_same({kk: (v[:k] if v.shape[0] == 1_000_001 else v[:2 * k]) for kk, v in res[True][0].items()}, exp, str(kw))
+        lo, hi = mid - 2000, mid + 2000
+        exp = H.orc.OracleClassifier(cfg, nthreads=16).classify(seq[off[lo]:off[hi]], off[lo:hi + 1] - off[lo])
+        fuzz.assert_same({kk: (v[lo:hi] if v.shape[0] == 1_000_001 else v[2 * lo:2 * hi]) for kk, v in res[True][0].items()}, exp, str(kw))
 
 
 def test_large_result_downloads_all_forms(monkeypatch):
