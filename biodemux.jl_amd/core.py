@@ -217,12 +217,19 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
     when the output is not gzip; _timings then also holds deflate_s, plain_bytes, compressed_bytes and gzip_level).
     ``_gzip_level`` (1 or 2, with ``_gzip="device"`` only) is the device encoder's level: 1 is the fast one, 2 finds
     better matches and writes smaller files (bdx_fq_deflate_level_device).
-    ``_gunzip`` selects who inflates a ``.gz`` input: "host" (zlib on host threads, csrc/bdx_io.cpp) or "device"
+    ``_gunzip`` selects who inflates a ``.gz`` input: "host" (zlib on host threads, csrc/bdx_io.cpp), "device" or
+    "device-stream".  "device" is for chains of small tagged members
     (csrc/bdx_inflate.hip: the device pipeline uploads the compressed members and inflates them on the GPU, checking
     every member's CRC-32 and ISIZE there; needs ``_io="device"``; inert for a plain input; a ``.gz`` input must be a
     chain of size-tagged gzip members — BGZF, or what ``_gzip="device"`` writes — of at most 64 KiB each, anything else
     is a ValueError; _timings then also holds inflate_s, compressed_in_bytes and plain_in_bytes, and upload_s covers
-    compressed bytes only).
+    compressed bytes only).  "device-stream" (csrc/bdx_inflate_stream.hip) takes an ORDINARY ``.gz`` input — one gzip
+    member or a few, of any size, tagged or not: the whole compressed file is uploaded and inflated on the GPU from
+    speculative block starts before the first batch, the text stays resident in device memory (the compressed bytes
+    plus three times the plain bytes at the peak; a file that does not fit is a BdxError that says so) and the batches
+    are windows into it; needs ``_io="device"``; inert for a plain input; a ``.gz`` input that does not begin with a
+    gzip header is a ValueError; _timings then holds inflate_s, compressed_in_bytes, plain_in_bytes and the counters
+    stream_members, stream_chunks, stream_confirmed, stream_discarded, stream_no_candidate and stream_longest_segment.
     Returns the DemuxStats scalar counters (the reference returns nothing)."""
     if len(args) == 3:
         fastq1, barcode_file, output_directory = args
@@ -241,10 +248,10 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         raise ValueError("_gzip_level must be 1 or 2")
     if _gzip_level != 1 and _gzip != "device":  # (the host writers have one level)
         raise ValueError("_gzip_level selects a level of the device encoder: it needs _gzip='device'")
-    if _gunzip not in ("host", "device"):
-        raise ValueError("_gunzip must be 'host' or 'device'")
-    if _gunzip == "device" and _io != "device":  # (no silent fallback to the host inflate)
-        raise ValueError("_gunzip='device' inflates inside the device FASTQ pipeline: it needs _io='device'")
+    if _gunzip not in ("host", "device", "device-stream"):
+        raise ValueError("_gunzip must be 'host', 'device' or 'device-stream'")
+    if _gunzip != "host" and _io != "device":  # (no silent fallback to the host inflate)
+        raise ValueError(f"_gunzip='{_gunzip}' inflates inside the device FASTQ pipeline: it needs _io='device'")
 
     defaults = dict(
         barcode_file2=None, gzip_output=None, max_error_rate=0.2, min_delta=0.0, match=0, mismatch=1, indel=1,
@@ -275,6 +282,8 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
 
     if _gunzip == "device":  # an input the device inflate cannot take: refused before the output directory is touched
         deviceio.check_gunzip_inputs([fastq1, fastq2] if paired else [fastq1], load_library())
+    elif _gunzip == "device-stream":  # ... or that is no gzip file at all
+        deviceio.check_stream_inputs([fastq1, fastq2] if paired else [fastq1])
 
     if not os.path.isdir(output_directory):  # core.jl:410-412
         os.mkdir(output_directory)
@@ -320,7 +329,7 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         if _io == "device":
             deviceio.demux_device(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers[0], _batch_reads,
                                   _timings, gzip_device=_gzip == "device", gunzip_device=_gunzip == "device",
-                                  gzip_level=int(_gzip_level))
+                                  gzip_level=int(_gzip_level), gunzip_stream=_gunzip == "device-stream")
         elif use_native:
             t_call = _dt.datetime.now()
             nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers, _batch_reads,

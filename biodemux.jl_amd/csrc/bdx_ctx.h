@@ -9,7 +9,7 @@
 
 #define BDX_FQ_SCRATCH 12  // scratch buffers of the device FASTQ pipeline (bdx_fastq.hip)
 #define BDX_DFL_SCRATCH 4  // scratch buffers of the device DEFLATE encoder (bdx_deflate.hip)
-#define BDX_INF_SCRATCH 2  // scratch buffers of the device inflate (bdx_inflate.hip)
+#define BDX_INF_SCRATCH 6  // scratch buffers of the device inflate (bdx_inflate.hip: 2) and of the stream inflate (bdx_inflate_stream.hip: 4)
 
 // An allocation that frees itself: move-only, so a block has one owner (the context, or a local that retires it).
 template <hipError_t (*Free)(void *)>
@@ -135,7 +135,8 @@ struct bdx_ctx : BdxPlanChoice {  // (tiered, tier_q, tier_cap_fixed, pairs_tier
     DevBuf counts_sum;
     DevBuf fq[BDX_FQ_SCRATCH];  // scratch of the device FASTQ pipeline (bdx_fastq.hip)
     DevBuf dfl[BDX_DFL_SCRATCH];  // scratch of the device DEFLATE encoder (bdx_deflate.hip): chunk table, member sizes / offsets, tokens, slots
-    DevBuf inf[BDX_INF_SCRATCH];  // scratch of the device inflate (bdx_inflate.hip): member table, member status
+    DevBuf inf[BDX_INF_SCRATCH];  // scratch of the device inflate (bdx_inflate.hip): member table, member status; of the stream inflate
+                                  // (bdx_inflate_stream.hip): chunk records, segment list, result, the 16-bit staging image
     std::string err;
     std::string launch_log;      // the classify kernels the last classify call enqueued (bdx_last_launches; a host call: all of its device calls)
     int64_t launches = 0;

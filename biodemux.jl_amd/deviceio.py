@@ -19,6 +19,12 @@ gzip members (BGZF, or this library's own output) is not inflated on the host: t
 members that cover the batch's byte window and the calling thread inflates them on the device right before the line
 index (csrc/bdx_inflate.hip, bdx_fq_inflate_device, which checks every member's CRC-32 and ISIZE).  The cursor stays in
 plain-text coordinates; the member at a batch's end is simply inflated again by the next batch.
+
+With ``gunzip_stream`` (``execute_demultiplexing(..., _gunzip="device-stream")``) a ``.gz`` input is an ORDINARY gzip file
+(members of any size, no tags): before the first batch the whole compressed file is uploaded and inflated by
+bdx_fq_inflate_stream_device (csrc/bdx_inflate_stream.hip: speculative block starts, every CRC-32 and ISIZE checked),
+the compressed copy is freed and the text stays RESIDENT in device memory.  A batch's window is then a pointer into it:
+nothing is uploaded per batch.  Peak device memory: the compressed bytes plus three times the plain bytes.
 """
 from __future__ import annotations
 
@@ -88,10 +94,10 @@ class _DevBuf:
     def __init__(self, rt: _Runtime):
         self.rt, self.p, self.cap = rt, 0, 0
 
-    def ensure(self, nbytes: int) -> int:
+    def ensure(self, nbytes: int, exact: bool = False) -> int:
         if nbytes > self.cap:
             self.free()
-            want = max(256, int(nbytes * 1.25))  # (room for the next batches' slightly longer windows)
+            want = max(256, nbytes if exact else int(nbytes * 1.25))  # (room for the next batches' slightly longer windows)
             p = C.c_void_p()
             self.rt.check(self.rt.hipMalloc(C.byref(p), want), f"hipMalloc({want})")
             self.p, self.cap = p.value, want
@@ -147,17 +153,38 @@ def check_gunzip_inputs(paths, lib) -> None:
             open_members(p, lib).close()
 
 
+def check_stream_inputs(paths) -> None:
+    """execute_demultiplexing calls this before it makes the output directory: a .gz input of the stream inflate
+    begins with a gzip header"""
+    for p in paths:
+        if _is_gz(p):
+            with open(p, "rb") as f:
+                head = f.read(3)
+            if head != b"\x1f\x8b\x08":
+                raise ValueError(f"_gunzip='device-stream' cannot take {p}: it does not begin with a gzip header (1f 8b 08)")
+
+
+STREAM_CHUNK = 0  # chunk_bytes of the stream inflate (0: bdx_fq_inflate_stream_chunk()); tools/e2e_device_probe.py sweeps it
+_STREAM_INFO = ("stream_members", "stream_chunks", "stream_confirmed", "stream_discarded", "stream_no_candidate",
+                "stream_longest_segment")
+_E_SPACE = -5  # BDX_E_SPACE
+
+
 class _Input:
     """One FASTQ input: its host bytes (mapped, or inflated in the background; or, for the device inflate, the mapped
     COMPRESSED members and their table) and its device side (two byte windows, the line table of the current batch).
     ``io_lib`` is libbdx_io.so, ``classifier`` the context whose stream the inflate and the index run on, ``busy`` the
-    run's counters."""
+    run's counters.  ``resident``: the stream inflate puts the whole text into device memory once (inflate_resident);
+    the windows are then places in it."""
 
-    def __init__(self, path: str, rt: _Runtime, io_lib, classifier, busy: dict, batch_reads: int, members=None):
+    def __init__(self, path: str, rt: _Runtime, io_lib, classifier, busy: dict, batch_reads: int, members=None,
+                 resident: bool = False):
         self.path = path
         self.rt, self.L, self.cl, self.busy, self.batch_reads = rt, io_lib, classifier, busy, batch_reads
         self.gz = members  # nativeio.GzMembers: this input is inflated on the device
-        self.f = nativeio.FastqFile(path) if members is None else None
+        self.res = _DevBuf(rt) if resident else None  # the resident text and its length
+        self.res_len = 0
+        self.f = nativeio.FastqFile(path) if members is None and not resident else None
         self.comp = [_DevBuf(rt), _DevBuf(rt)]  # compressed form: the members of the window
         self.wmem = [(0, 0), (0, 0)]            # ... which ones: [first, last)
         self.d_text = [0, 0]                    # where the window's text starts on the device
@@ -178,7 +205,11 @@ class _Input:
         t0 = time.perf_counter()
         # (the current device belongs to the thread: the upload thread has to choose it as well)
         self.rt.check(self.rt.hipSetDevice(int(getattr(self.cl, "device", 0))), "hipSetDevice")
-        if self.gz is not None:
+        if self.res is not None:  # resident: a window is a place in the text (64 bytes of slack follow its end)
+            end = min(self.res_len, self.cursor + want)
+            self.win[slot] = (max(0, end - self.cursor), end >= self.res_len)
+            self.d_text[slot] = self.res.p + self.cursor
+        elif self.gz is not None:
             self.upload_members(s_copy, slot, want)
         else:
             self.upload_text(s_copy, slot, want)
@@ -218,6 +249,51 @@ class _Input:
             self.busy["compressed_in_bytes"] += nbytes
         self.wmem[slot] = (m0, m1)
         self.win[slot] = (max(0, int(po[m1]) - self.cursor), m1 == n)
+
+    def inflate_resident(self, s_copy: int):
+        """The whole .gz file -> the resident text, on the context's stream (the calling thread, before the first
+        batch): the compressed bytes go up, bdx_fq_inflate_stream_device is called with a guessed capacity and once
+        more with the exact one when that was too small, the compressed copy is freed."""
+        rt, lib, h = self.rt, self.cl.lib, self.cl.h
+        g = nativeio.GzMembers(self.path, int(lib.bdx_fq_inflate_member_max()))  # (maps any .gz; its table is not used)
+        comp = _DevBuf(rt)
+        try:
+            size = int(g.size)
+            plen, info = C.c_int64(0), np.zeros(8, dtype=np.int64)
+            t_u = time.perf_counter()
+            try:
+                comp.ensure(size, exact=True)
+                if size:
+                    rt.check(rt.hipMemcpyAsync(comp.p, g.data, size, _H2D, s_copy), "hipMemcpyAsync (upload)")
+                    rt.check(rt.hipStreamSynchronize(s_copy), "hipStreamSynchronize (upload)")
+                self.busy["upload_s"] += time.perf_counter() - t_u
+                t_i = time.perf_counter()
+                cap = 4 * size  # FASTQ deflates 3 .. 5 x: usually one call
+                for _ in range(2):
+                    self.res.free()
+                    self.res.ensure(cap + 64, exact=True)
+                    rc = lib.bdx_fq_inflate_stream_device(h, comp.p, size, int(STREAM_CHUNK), self.res.p, cap, C.byref(plen),
+                                                          info.ctypes.data)
+                    if rc != _E_SPACE:
+                        break
+                    cap = int(plen.value)
+            except BdxError as e:  # (an allocation of this module)
+                raise BdxError(f"{self.path}: the stream inflate keeps the compressed bytes ({size}) and three times the plain "
+                               f"bytes ({int(plen.value) or 'not known yet'}) in device memory: {e}") from None
+            if rc == -2:  # BDX_E_DEVICE: the staging image (twice the plain bytes) did not fit
+                raise BdxError(f"{self.path}: the stream inflate needs {size} compressed + 3 x {int(plen.value)} plain bytes of device "
+                               f"memory ({lib.bdx_last_error(h).decode()})")
+            if rc != 0:
+                raise BdxError(f"{self.path}: refused by the device stream inflate: {lib.bdx_last_error(h).decode()}")
+            self.res_len = int(plen.value)
+            self.busy["compressed_in_bytes"] += size
+            self.busy["plain_in_bytes"] += self.res_len
+            for name, v in zip(_STREAM_INFO, info.tolist()):
+                self.busy[name] = max(v, self.busy.get(name, 0)) if name == "stream_longest_segment" else self.busy.get(name, 0) + v
+            self.busy["inflate_s"] += time.perf_counter() - t_i
+        finally:
+            comp.free()
+            g.close()
 
     def inflate(self, slot: int):
         """comp[slot] -> text[slot] on the context's stream (the calling thread); the window's text starts at the
@@ -267,6 +343,8 @@ class _Input:
 
     def release(self):
         """everything below the cursor is uploaded: the host pages can go"""
+        if self.res is not None:
+            return
         if self.gz is None:
             self.f.release(self.cursor)
         elif len(self.gz):
@@ -274,7 +352,7 @@ class _Input:
             self.gz.release(int(self.gz.comp_off[m]))
 
     def close(self):
-        for b in (*self.text, *self.comp, self.d_off, self.d_len):
+        for b in (*self.text, *self.comp, self.d_off, self.d_len, *([self.res] if self.res is not None else [])):
             b.free()
         for f in (self.f, self.gz):
             if f is not None:
@@ -363,14 +441,16 @@ def _write_loop(q_w, slots: _Slots, errors: list, rt: _Runtime, L, layout: Outpu
 
 def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
                  classifier, batch_reads: int, timings: Optional[dict] = None, gzip_device: bool = False,
-                 gunzip_device: bool = False, gzip_level: int = 1) -> None:
+                 gunzip_device: bool = False, gzip_level: int = 1, gunzip_stream: bool = False) -> None:
     """Device counterpart of nativeio.demux_native (same arguments but ``on_batch``: the HIP classifier keeps the
     summary tables itself).  ``classifier`` must be the HIP classifier.  ``gzip_device``: gzip output is compressed by
     bdx_fq_deflate_device after the gathers, only finished gzip members are downloaded and the writer appends them as
     they are (inert when the output is not gzip), at ``gzip_level`` (1 or 2: bdx_fq_deflate_level_device).
     ``gunzip_device``: every input whose name ends in .gz is uploaded
     compressed and inflated by bdx_fq_inflate_device (inert for a plain input; ValueError for a .gz that is no chain of
-    size-tagged members of at most bdx_fq_inflate_member_max() bytes)."""
+    size-tagged members of at most bdx_fq_inflate_member_max() bytes).  ``gunzip_stream``: every input whose name ends
+    in .gz is an ordinary gzip file: uploaded whole, inflated by bdx_fq_inflate_stream_device before the first batch
+    and kept resident (inert for a plain input; BdxError naming the file when a member is refused)."""
     if not hasattr(classifier, "classify_device"):
         raise ValueError("the device FASTQ pipeline (_io='device') needs the HIP classifier")
     t_wall = time.perf_counter()
@@ -401,15 +481,18 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
         for path in (fastq1, fastq2) if paired else (fastq1,):  # (each input judged on its own)
             members = open_members(path, lib) if gunzip_device and _is_gz(path) else None
             try:
-                ins.append(_Input(path, rt, L, classifier, busy, batch_reads, members))
+                ins.append(_Input(path, rt, L, classifier, busy, batch_reads, members, resident=gunzip_stream and _is_gz(path)))
             except BaseException:
                 if members is not None:
                     members.close()
                 raise
-        if any(inp.gz is not None for inp in ins):
+        if any(inp.gz is not None or inp.res is not None for inp in ins):
             busy.update(inflate_s=0.0, compressed_in_bytes=0, plain_in_bytes=0)
         s_main, s_copy = rt.stream(), rt.stream()
         classifier.set_stream(s_main)
+        for inp in ins:
+            if inp.res is not None:
+                inp.inflate_resident(s_copy)
         d_seq, d_seq_off, d_out, d_gz = _DevBuf(rt), _DevBuf(rt), _DevBuf(rt), _DevBuf(rt)
         d_v = {k: _DevBuf(rt) for k in ("bc1", "bc2", "keep_start", "keep_end")}
         dbufs = [d_seq, d_seq_off, d_out, d_gz, *d_v.values()]

@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     "bdx_fq_deflate_chunk", "bdx_fq_deflate_bound", "bdx_fq_deflate_device", "bdx_fq_deflate_levels", "bdx_fq_deflate_level_device",
     # device inflate of the pipeline's .gz input (bdx_inflate.hip)
     "bdx_fq_inflate_member_max", "bdx_fq_inflate_device",
+    # stream inflate of an ordinary .gz input (bdx_inflate_stream.hip)
+    "bdx_fq_inflate_stream_chunk", "bdx_fq_inflate_stream_device",
 ]
 STATS_WHICH = {"pos": 0, "len": 1, "raw": 2}
 BDX_COMM_ID_BYTES = 128
@@ -261,6 +263,10 @@ def load_library(path: Optional[str] = None):
     L.bdx_fq_inflate_member_max.argtypes = []
     L.bdx_fq_inflate_device.restype = C.c_int32
     L.bdx_fq_inflate_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_int64, vp]
+    L.bdx_fq_inflate_stream_chunk.restype = C.c_int32
+    L.bdx_fq_inflate_stream_chunk.argtypes = []
+    L.bdx_fq_inflate_stream_device.restype = C.c_int32
+    L.bdx_fq_inflate_stream_device.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int64, vp, vp]
     if path is None:
         _lib = L
     return L

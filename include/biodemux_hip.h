@@ -36,6 +36,7 @@ extern "C" {
 #define BDX_E_DEVICE (-2)    /* HIP runtime error (no GPU, OOM, launch failure) */
 #define BDX_E_STATE (-3)     /* call sequence error */
 #define BDX_E_COMM (-4)      /* RCCL not available / a collective failed */
+#define BDX_E_SPACE (-5)     /* an output buffer is too small; the needed size is reported */
 
 /* DemuxConfig.matching_algorithm (classification.jl:57): :semiglobal / :hamming / :exact */
 #define BDX_ALG_SEMIGLOBAL 0
@@ -364,6 +365,30 @@ int32_t bdx_fq_inflate_member_max(void);
 int32_t bdx_fq_inflate_device(bdx_ctx *ctx, const uint8_t *d_comp, const int64_t *comp_off, const int32_t *comp_len,
                               const int64_t *plain_off, const int32_t *plain_len, int32_t n_members, uint8_t *d_out,
                               int64_t out_cap, int32_t *status);
+
+/* Stream inflate for an ORDINARY .gz input (csrc/bdx_inflate_stream.hip): d_comp[0, comp_len) is a whole .gz file in
+ * device memory, one or more gzip members of any size back to back, tagged or not (tags are ignored).  The file is cut
+ * at multiples of chunk_bytes; every chunk guesses a block start (a dynamic block's header is redundant enough to be
+ * recognised) and decodes from there, the guesses a confirmed decoder arrives at are chained, and what a match copies
+ * from the unknown 32 KiB in front of a guess is resolved afterwards.  Exactness never rests on a guess: a wrong or
+ * missing one costs speed only.  Accepts a file exactly when zlib accepts every member; what follows the last member
+ * and does not begin with 1f 8b is ignored, as zlib's gzread ignores it.
+ *
+ * bdx_fq_inflate_stream_chunk: the default chunk_bytes; needs no context and no device.
+ *
+ * bdx_fq_inflate_stream_device: chunk_bytes is 0 (the default) or 64 .. 2^24.  The arguments are checked before
+ * anything is launched (BDX_E_INVALID).  Runs on the context's stream and synchronises before it returns.
+ *   BDX_OK         d_out[0, *plain_len) holds the plain bytes of all members, every CRC-32 and ISIZE verified
+ *   BDX_E_SPACE    out_cap is too small: *plain_len is the size needed (known before any output byte exists: d_out is
+ *                  untouched)
+ *   BDX_E_INVALID  a member is refused: bdx_last_error names the member, the compressed byte offset and one of the
+ *                  eleven reasons of bdx_fq_inflate_device; d_out[0, out_cap) is unspecified
+ * info (HOST memory, 8 entries, may be NULL) receives: members, chunks, segments confirmed at a guessed start,
+ * candidates discarded, chunks without a candidate, the compressed bytes of the longest segment, 0, 0.
+ * Device memory taken for the call: 2 * *plain_len bytes (released before it returns) and 32 bytes per chunk. */
+int32_t bdx_fq_inflate_stream_chunk(void);
+int32_t bdx_fq_inflate_stream_device(bdx_ctx *ctx, const uint8_t *d_comp, int64_t comp_len, int32_t chunk_bytes,
+                                     uint8_t *d_out, int64_t out_cap, int64_t *plain_len, int64_t *info);
 
 /* Introspection for bench/tests: name of the kernel path a classify call will take, and numbers of the
  * last launch.  "generic": exact kernel only; "bitpar+verify": bit-vector sweep of every pair, then the exact

@@ -1,0 +1,136 @@
+// The stream inflate of csrc/bdx_inflate_stream_core.h compiled as plain C++: every kernel of csrc/bdx_inflate_stream.hip
+// is a loop over its workgroups here, in the order of the launches.  tests/test_device_gunzip_stream_cpu.py loads it as
+// a library and holds it to the cases of tests/inflate_stream_cases.py; with -DINFS_HOST_MAIN it is the stand-alone
+// driver that tests/test_device_gunzip_stream_sanitize.py runs under AddressSanitizer.  The file, the staging image
+// and the output are exact-size heap blocks: one byte beside any of them is the sanitizer's to report.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../biodemux.jl_amd/csrc/bdx_inflate_stream_core.h"
+
+static InfsShared X;
+
+extern "C" int32_t infs_host_chunk_default(void) { return INFS_CHUNK_DEFAULT; }
+extern "C" int32_t infs_host_shared_bytes(void) { return (int32_t)sizeof(InfsShared); }
+
+// comp[0, comp_len) -> out[0, *plain_len).  Returns 0, a status INF_E_* (member and at say where), or -5 when out_cap
+// is too small (*plain_len is what is needed; out is untouched).  seg_room: the first room of the segment list (a
+// small one makes the chain run twice).
+extern "C" int32_t infs_host_inflate(const uint8_t *comp_in, int64_t comp_len, int32_t chunk, uint8_t *out_user, int64_t out_cap,
+                                     int64_t *plain_len, int64_t *info, int32_t *member, int64_t *at, int64_t seg_room) {
+    if (chunk == 0) chunk = INFS_CHUNK_DEFAULT;
+    INF_PHASE(inf_ph_tables(X.S, t))
+    uint8_t *comp = (uint8_t *)malloc(comp_len > 0 ? (size_t)comp_len : 1);
+    if (comp_len > 0) memcpy(comp, comp_in, (size_t)comp_len);
+    const int64_t n_chunks = (comp_len + chunk - 1) / chunk;
+    std::vector<InfsRecord> rec((size_t)n_chunks + 1);
+    for (int64_t k = 0; k < n_chunks; ++k) infs_scan_chunk(X, comp, comp_len, chunk, k, &rec[(size_t)k]);
+    std::vector<InfsSegment> seg((size_t)(seg_room > 0 ? seg_room : 1));
+    InfsResult res;
+    memset(&res, 0, sizeof res);
+    infs_chain(X, comp, comp_len, chunk, rec.data(), n_chunks, seg.data(), (int64_t)seg.size(), &res);
+    if (res.status == INF_OK && res.n_seg > seg.size()) {
+        seg.resize((size_t)res.n_seg);
+        infs_chain(X, comp, comp_len, chunk, rec.data(), n_chunks, seg.data(), (int64_t)seg.size(), &res);
+    }
+    int32_t rc = (int32_t)res.status;
+    if (rc == INF_OK) {
+        *plain_len = (int64_t)res.total;
+        if (info) memcpy(info, res.info, sizeof res.info);
+        if ((int64_t)res.total > out_cap) rc = -5;
+    }
+    if (rc == INF_OK) {
+        const int64_t n_seg = (int64_t)res.n_seg;
+        uint16_t *stage = (uint16_t *)malloc(res.total ? (size_t)res.total * 2 : 2);
+        uint8_t *out = (uint8_t *)malloc(res.total ? (size_t)res.total : 1);
+        for (int64_t i = 0; i < n_seg; ++i) infs_decode_segment(X, comp, comp_len, &seg[(size_t)i], stage);
+        infs_tails(seg.data(), n_seg, stage, out);
+        for (int64_t i = 0; i < n_seg; ++i) infs_rest_segment(X, &seg[(size_t)i], stage, out);
+        INF_PHASE(infs_ph_verdict(X, seg.data(), n_seg, &res, t))
+        rc = (int32_t)res.status;
+        if (rc == INF_OK && res.total) memcpy(out_user, out, (size_t)res.total);
+        free(out);
+        free(stage);
+    }
+    if (rc > 0) {
+        if (member) *member = (int32_t)res.member;
+        if (at) *at = (int64_t)res.at;
+    }
+    free(comp);
+    return rc;
+}
+
+#ifdef INFS_HOST_MAIN
+static std::vector<uint8_t> slurp(const std::string &path) {
+    std::vector<uint8_t> all;
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path.c_str());
+        exit(3);
+    }
+    uint8_t buf[65536];
+    for (size_t got; (got = fread(buf, 1, sizeof buf, f)) > 0;) all.insert(all.end(), buf, buf + got);
+    fclose(f);
+    return all;
+}
+
+// exact sizes again: the output is exactly as large as the plain text
+static int32_t run(const std::vector<uint8_t> &comp, size_t clen, int32_t chunk, size_t cap, std::vector<uint8_t> *got) {
+    uint8_t *in = (uint8_t *)malloc(clen ? clen : 1);
+    uint8_t *out = (uint8_t *)malloc(cap ? cap : 1);
+    if (clen) memcpy(in, comp.data(), clen);
+    int64_t plen = 0;
+    const int32_t st = infs_host_inflate(in, (int64_t)clen, chunk, out, (int64_t)cap, &plen, nullptr, nullptr, nullptr, 3);
+    if (got) got->assign(out, out + (st == 0 ? (size_t)plen : 0));
+    free(out);
+    free(in);
+    return st;
+}
+
+// <dir> <cases>: case_K.gz, case_K.plain, case_K.info ("<1: good> <chunk> <chunk> ...")
+int main(int argc, char **argv) {
+    if (argc != 3) return 2;
+    const std::string dir = argv[1];
+    const int cases = atoi(argv[2]);
+    long good = 0, bad = 0, cut = 0, mangled = 0;
+    uint64_t rng = 88172645463325252ull;
+    for (int k = 0; k < cases; ++k) {
+        const std::string stem = dir + "/case_" + std::to_string(k);
+        const std::vector<uint8_t> comp = slurp(stem + ".gz"), want = slurp(stem + ".plain"), info = slurp(stem + ".info");
+        std::vector<int> words;
+        std::string line(info.begin(), info.end());
+        for (char *p = strtok(&line[0], " \n"); p; p = strtok(nullptr, " \n")) words.push_back(atoi(p));
+        if (words.size() < 2) return 4;
+        const bool is_good = words[0] != 0;
+        const size_t room = is_good ? want.size() : (size_t)1 << 17;  // (a bad one: room to get to its fault)
+        for (size_t c = 1; c < words.size(); ++c) {
+            std::vector<uint8_t> got;
+            const int32_t st = run(comp, comp.size(), words[c], room, &got);
+            if (is_good ? (st != 0 || got != want) : st <= 0) {
+                fprintf(stderr, "case %d chunk %d: status %d\n", k, words[c], st);
+                return 5;
+            }
+        }
+        (is_good ? good : bad)++;
+        if (comp.size() > 1500) continue;
+        for (size_t c = 0; c < comp.size(); ++c, ++cut) (void)run(comp, c, 64, room, nullptr);  // every prefix
+        for (int r = 0; r < 150; ++r, ++mangled) {  // corrupted bytes anywhere; outputs too small and too large
+            std::vector<uint8_t> c = comp;
+            for (int j = 0; j < 1 + r % 3; ++j) {
+                rng ^= rng << 13;
+                rng ^= rng >> 7;
+                rng ^= rng << 17;
+                c[rng % c.size()] ^= (uint8_t)(1u << ((rng >> 32) & 7));
+            }
+            const size_t cap = r % 5 == 0 ? room / 2 : r % 7 == 0 ? room + 100 : room;
+            (void)run(c, c.size(), r % 2 ? 64 : 256, cap, nullptr);
+        }
+    }
+    printf("stream inflate driver ok: %ld good, %ld bad, %ld cut, %ld mangled\n", good, bad, cut, mangled);
+    return 0;
+}
+#endif

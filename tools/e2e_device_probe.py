@@ -2,7 +2,7 @@
 """End-to-end reads/s of execute_demultiplexing on the C2 shape: the native host pipeline (_io="native") against the device
 FASTQ pipeline (_io="device"), each run in a fresh child process (GPU box).
 
-  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device} [--gzip-level 2] | --gunzip] [out.json]
+  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device} [--gzip-level 2] | --gunzip | --gunzip-stream] [out.json]
 
 One synthetic FASTQ of N 150 bp reads x 96 barcodes (24 bp), max_error_rate=0.1, on tmpfs (/dev/shm unless E2E_ROOT is
 set); the outputs are checked (total bytes = input bytes).  Prints every run with its stage seconds, then the medians; the
@@ -16,7 +16,13 @@ leg reports min, median and max wall seconds.
 --gunzip: .gz in -> .gz out through the device pipeline only.  The input is written once as 32 KiB 'D','X' members (zlib
 level 1 on host threads) and three legs alternate after one unrecorded warm-up run: "device+gz+hin" (host inflate, host
 gzip), "device+dgz+hin" (host inflate, device gzip) and "device+dgz+din" (_gunzip="device": inflate on the GPU, device
-gzip)."""
+gzip).
+
+--gunzip-stream: an ORDINARY .gz in -> plain out through the device pipeline.  The input is written once as ONE gzip member
+(zlib level 6; slices compressed side by side and joined with sync flushes, as pigz does) and two legs alternate after one
+unrecorded warm-up run: "device++hsin" (_gunzip="host": one zlib thread) and "device++sin" (_gunzip="device-stream").
+Before that, one run of the stream leg per chunk size of 16, 32, 64 and 128 KiB ("sweep").  REPS=5 is what the
+repository's figures use; every leg reports min, median and max wall seconds and the plain GB/s they amount to."""
 import json
 import os
 import shutil
@@ -78,6 +84,37 @@ def make_gz_input(root: str, member: int = 32768) -> None:
             f.write(m)
 
 
+def make_stream_gz_input(root: str, slices: int = 64) -> None:
+    """synthetic.stream.fastq.gz beside synthetic.fastq: one ordinary gzip member, zlib level 6"""
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+
+    import numpy as np
+
+    fq = os.path.join(root, "synthetic.fastq")
+    if os.path.exists(fq[:-6] + ".stream.fastq.gz"):
+        return
+    d = np.memmap(fq, dtype=np.uint8, mode="r")
+    step = -(-len(d) // slices)
+
+    def one(k):
+        part = bytes(d[k * step:(k + 1) * step])
+        z = zlib.compressobj(6, zlib.DEFLATED, -15)
+        return z.compress(part) + z.flush(zlib.Z_FINISH if k == slices - 1 else zlib.Z_SYNC_FLUSH), zlib.crc32(part), len(part)
+
+    with ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0)))) as ex, open(fq[:-6] + ".stream.fastq.gz", "wb") as f:
+        f.write(b"\x1f\x8b\x08\0\0\0\0\0\0\xff")
+        crc = 0
+        for body, c, n in ex.map(one, range(slices)):
+            f.write(body)
+            crc = zlib.crc32_combine(crc, c, n) if hasattr(zlib, "crc32_combine") else None
+        if crc is None:
+            crc = 0
+            for o in range(0, len(d), 1 << 26):
+                crc = zlib.crc32(d[o:o + (1 << 26)], crc)
+        f.write(crc.to_bytes(4, "little") + (len(d) & 0xFFFFFFFF).to_bytes(4, "little"))
+
+
 def gz_sizes(path: str):
     """(compressed, uncompressed) bytes of a file made of size-tagged gzip members"""
     import numpy as np
@@ -106,7 +143,15 @@ def child(mode: str) -> None:
         kw["_gzip"] = "device"
     if gz == "dgz2":
         kw["_gzip_level"] = 2
-    if gin:
+    if gin in ("hsin", "sin"):
+        from biodemux_jl_amd import deviceio
+
+        fq = fq[:-6] + ".stream.fastq.gz"
+        kw.update(gzip_output=False, output_prefix="synthetic")
+        if gin == "sin":
+            kw["_gunzip"] = "device-stream"
+            deviceio.STREAM_CHUNK = int(os.environ.get("E2E_STREAM_CHUNK", "0"))
+    elif gin:
         fq += ".gz"
     if gin == "din":
         kw["_gunzip"] = "device"
@@ -143,6 +188,10 @@ def main() -> None:
     if gunzip:
         modes = ["device+gz+hin", "device+dgz+hin", "device+dgz+din"]
         argv = argv[1:]
+    stream = bool(argv) and argv[0] == "--gunzip-stream"
+    if stream:
+        modes = ["device++hsin", "device++sin"]
+        argv = argv[1:]
     n = int(os.environ.get("N", "10000000"))
     reps = int(os.environ.get("REPS", "3"))
     root = os.environ.get("E2E_ROOT") or "/dev/shm/bdx_e2e_device_probe"
@@ -153,11 +202,25 @@ def main() -> None:
     if gunzip:
         make_gz_input(root)
         gz_bytes = os.path.getsize(os.path.join(root, "synthetic.fastq.gz"))
+    if stream:
+        make_stream_gz_input(root)
+        gz_bytes = os.path.getsize(os.path.join(root, "synthetic.stream.fastq.gz"))
     gen_s = time.perf_counter() - t0
     env = dict(os.environ, E2E_ROOT=root, N=str(n))
     runs = []
+    sweep = []
     try:
-        for rep in range(-1 if gunzip else 0, reps):  # (rep -1: the warm-up run, not recorded)
+        for kib in (16, 32, 64, 128) if stream else ():  # one run per chunk size
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "device++sin"],
+                               env=dict(env, E2E_STREAM_CHUNK=str(kib * 1024)), capture_output=True, text=True, timeout=300)
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+            if p.returncode != 0 or not line:
+                sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
+                raise SystemExit(f"sweep run at {kib} KiB failed (rc {p.returncode})")
+            r = json.loads(line[0][7:])
+            sweep.append({"chunk_kib": kib, "seconds": r["seconds"], "inflate_s": r["stages"].get("inflate_s"), "stages": r["stages"]})
+            print(f"SWEEP chunk {kib:4d} KiB  {r['seconds']:.4f} s  inflate_s {r['stages'].get('inflate_s')}", flush=True)
+        for rep in range(-1 if gunzip or stream else 0, reps):  # (rep -1: the warm-up run, not recorded)
             for mode in modes[:1] if rep < 0 else modes:
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode], env=env, capture_output=True,
                                    text=True, timeout=600)
@@ -174,7 +237,7 @@ def main() -> None:
                 keys = ("index_s", "pack_s", "classify_s", "write_s") if mode.startswith("native") else ("upload_s", "device_s", "download_s", "write_s")
                 if "+dgz" in mode:
                     keys += ("deflate_s",)
-                if mode.endswith("+din"):
+                if mode.endswith(("+din", "+sin")):
                     keys += ("inflate_s", "compressed_in_bytes", "plain_in_bytes")
                 print(f"RUN {rep} {mode:10s} {r['seconds']:.4f} s  {r['reads_per_s'] / 1e6:6.1f} M reads/s  "
                       + "  ".join(f"{k} {st.get(k, 0):.4f}" for k in keys) + f"  batches {st.get('batches')}", flush=True)
@@ -183,12 +246,16 @@ def main() -> None:
     summary = {"reads": n, "fastq_gb": n * 319 / 1e9, "where": root, "generate_s": round(gen_s, 2), "runs": runs}
     if gz_bytes is not None:
         summary["input_gz_bytes"] = gz_bytes
+    if stream:
+        summary["chunk_sweep"] = sweep
     for mode in modes:
         rs = [r for r in runs if r["mode"] == mode]
         med = statistics.median(r["reads_per_s"] for r in rs)
         secs = sorted(r["seconds"] for r in rs)
         stages = {k: statistics.median(r["stages"][k] for r in rs) for k in rs[0]["stages"] if isinstance(rs[0]["stages"][k], (int, float))}
         summary[mode] = {"median_reads_per_s": med, "median_stage_s": stages, "seconds_min_median_max": [secs[0], statistics.median(secs), secs[-1]]}
+        if stream:  # the leg's plain text per wall second (the host leg: what one zlib thread sustains under the pipeline)
+            summary[mode]["plain_gb_per_s_min_median_max"] = [n * 319 / 1e9 / x for x in (secs[-1], statistics.median(secs), secs[0])]
         print(f"MEDIAN {mode:10s} {med / 1e6:.1f} M reads/s  wall s min {secs[0]:.4f} median {statistics.median(secs):.4f} max {secs[-1]:.4f}  " + "  ".join(f"{k} {v:.4f}" for k, v in sorted(stages.items())))
     if argv:
         with open(argv[0], "w") as f:
