@@ -43,7 +43,11 @@
 #define INFS_CHUNK_MIN 64
 #define INFS_CHUNK_MAX (1 << 24)
 #define INFS_WINDOW 32768u
+#ifndef INFS_REBASE  // (a test build sets a small one: the rebasing is then reached by files of a few hundred KB)
 #define INFS_REBASE (1u << 30)
+#endif
+// one phase consumes at most a stored block of 65 535 bytes and its header, and lists at most 65 535 bytes
+static_assert(INFS_REBASE >= (1u << 17) && INFS_REBASE <= (1u << 30), "INFS_REBASE: a phase's bytes fit the view, the view fits 31 bits");
 #define INFS_TAIL_THREADS 1024
 #define INFS_NONE (~(uint64_t)0)
 #define INFS_E_INTERNAL 12  // a segment decoded to something else than it counted to (cannot happen)

@@ -484,13 +484,16 @@ def small_files():
 
 
 # ---- the core as plain C++ (tests/inflate_stream_host.cpp) ----
-def build_host(directory):
+def build_host(directory, flags=(), name="libinfs_host.so"):
+    """flags: further compiler flags (another INFS_REBASE, say), for a second library beside the first: give it a `name`"""
     import ctypes as C
     import subprocess
 
-    so = os.path.join(str(directory), "libinfs_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(HERE, "inflate_stream_host.cpp")])
+    so = os.path.join(str(directory), name)
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", *flags, "-o", so, os.path.join(HERE, "inflate_stream_host.cpp")])
     L = C.CDLL(so)
+    L.infs_host_set_launch.restype = None
+    L.infs_host_set_launch.argtypes = [C.c_int, C.c_int]
     L.infs_host_inflate.restype = C.c_int32
     L.infs_host_inflate.argtypes = [C.c_char_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int64]
@@ -505,4 +508,5 @@ def build_host(directory):
         return rc, (out[:used].tobytes() if rc == 0 else None), plen.value, info.tolist(), member.value, at.value, bool((out[used:] == 0xC5).all())
 
     inflate.chunk_default = int(L.infs_host_chunk_default())
+    inflate.set_launch = L.infs_host_set_launch  # (fill, grid): how a workgroup starts, see inflate_stream_host.cpp; (-1, 0) is the default
     return inflate
