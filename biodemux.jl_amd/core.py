@@ -196,7 +196,7 @@ def _close_all(classifiers) -> None:
 def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxConfig], object]] = None,
                            _batch_reads: int = DEFAULT_BATCH_READS, _io: str = "auto", device: int = 0,
                            devices=None, _timings: Optional[dict] = None, _gzip: str = "host", _gunzip: str = "host",
-                           _gzip_level: int = 1, **kw):
+                           _gzip_level: int = 1, _gunzip_window: Optional[int] = None, **kw):
     """execute_demultiplexing(FASTQ_file, barcode_file, output_directory; kwargs...)      core.jl:500
     execute_demultiplexing(FASTQ_file1, FASTQ_file2, barcode_file, output_directory; ...)  core.jl:360
 
@@ -217,8 +217,8 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
     when the output is not gzip; _timings then also holds deflate_s, plain_bytes, compressed_bytes and gzip_level).
     ``_gzip_level`` (1 or 2, with ``_gzip="device"`` only) is the device encoder's level: 1 is the fast one, 2 finds
     better matches and writes smaller files (bdx_fq_deflate_level_device).
-    ``_gunzip`` selects who inflates a ``.gz`` input: "host" (zlib on host threads, csrc/bdx_io.cpp), "device" or
-    "device-stream".  "device" is for chains of small tagged members
+    ``_gunzip`` selects who inflates a ``.gz`` input: "host" (zlib on host threads, csrc/bdx_io.cpp), "device",
+    "device-stream" or "device-window".  "device" is for chains of small tagged members
     (csrc/bdx_inflate.hip: the device pipeline uploads the compressed members and inflates them on the GPU, checking
     every member's CRC-32 and ISIZE there; needs ``_io="device"``; inert for a plain input; a ``.gz`` input must be a
     chain of size-tagged gzip members — BGZF, or what ``_gzip="device"`` writes — of at most 64 KiB each, anything else
@@ -230,6 +230,16 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
     are windows into it; needs ``_io="device"``; inert for a plain input; a ``.gz`` input that does not begin with a
     gzip header is a ValueError; _timings then holds inflate_s, compressed_in_bytes, plain_in_bytes and the counters
     stream_members, stream_chunks, stream_confirmed, stream_discarded, stream_no_candidate and stream_longest_segment.
+    "device-window" (bdx_fq_inflate_window_*, csrc/bdx_inflate_window_core.h) takes the same ordinary ``.gz`` input
+    of ANY size: the compressed file goes through the GPU in windows of ``_gunzip_window`` compressed bytes (an int of
+    1024 .. 2^28, rounded up to a multiple of the chunk size; default deviceio.WINDOW_BYTES), each inflated from the
+    state the one before ended in while the next one is uploaded, and the text is handed to the batches as it appears:
+    device memory follows the window, not the file (deviceio's docstring has the bound).  A member's CRC-32 is known at
+    its end only: a refused member raises BdxError naming the file, the member, the compressed offset and the reason
+    AFTER the batches of the windows before it were written, as with ``_gunzip="host"`` — not before the first batch,
+    as "device-stream" does.  Needs ``_io="device"``; inert for a plain input; a ``.gz`` input that does not begin with
+    a gzip header is a ValueError; _timings holds what "device-stream" reports, summed over the windows
+    (stream_longest_segment: the maximum), and stream_windows, stream_window_bytes and stream_text_peak_bytes.
     Returns the DemuxStats scalar counters (the reference returns nothing)."""
     if len(args) == 3:
         fastq1, barcode_file, output_directory = args
@@ -248,10 +258,14 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         raise ValueError("_gzip_level must be 1 or 2")
     if _gzip_level != 1 and _gzip != "device":  # (the host writers have one level)
         raise ValueError("_gzip_level selects a level of the device encoder: it needs _gzip='device'")
-    if _gunzip not in ("host", "device", "device-stream"):
-        raise ValueError("_gunzip must be 'host', 'device' or 'device-stream'")
+    if _gunzip not in ("host", "device", "device-stream", "device-window"):
+        raise ValueError("_gunzip must be 'host', 'device', 'device-stream' or 'device-window'")
     if _gunzip != "host" and _io != "device":  # (no silent fallback to the host inflate)
         raise ValueError(f"_gunzip='{_gunzip}' inflates inside the device FASTQ pipeline: it needs _io='device'")
+    if _gunzip_window is not None:
+        if _gunzip != "device-window":
+            raise ValueError("_gunzip_window is the window of _gunzip='device-window'")
+        _gunzip_window = deviceio.window_bytes(_gunzip_window)  # (ValueError: not an int of 1024 .. 2^28)
 
     defaults = dict(
         barcode_file2=None, gzip_output=None, max_error_rate=0.2, min_delta=0.0, match=0, mismatch=1, indel=1,
@@ -282,8 +296,8 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
 
     if _gunzip == "device":  # an input the device inflate cannot take: refused before the output directory is touched
         deviceio.check_gunzip_inputs([fastq1, fastq2] if paired else [fastq1], load_library())
-    elif _gunzip == "device-stream":  # ... or that is no gzip file at all
-        deviceio.check_stream_inputs([fastq1, fastq2] if paired else [fastq1])
+    elif _gunzip in ("device-stream", "device-window"):  # ... or that is no gzip file at all
+        deviceio.check_stream_inputs([fastq1, fastq2] if paired else [fastq1], _gunzip)
 
     if not os.path.isdir(output_directory):  # core.jl:410-412
         os.mkdir(output_directory)
@@ -329,7 +343,8 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         if _io == "device":
             deviceio.demux_device(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers[0], _batch_reads,
                                   _timings, gzip_device=_gzip == "device", gunzip_device=_gunzip == "device",
-                                  gzip_level=int(_gzip_level), gunzip_stream=_gunzip == "device-stream")
+                                  gzip_level=int(_gzip_level), gunzip_stream=_gunzip == "device-stream",
+                                  gunzip_window=(_gunzip_window or deviceio.WINDOW_BYTES) if _gunzip == "device-window" else 0)
         elif use_native:
             t_call = _dt.datetime.now()
             nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers, _batch_reads,

@@ -226,19 +226,15 @@ INF_FN void infs_ph_record(InfsShared &X, InfsRecord *rec, int t) {
     rec->status = X.S.state == INF_BAD ? X.S.status : INF_OK;
     rec->final = X.S.state == INF_END;
 }
-// chunk k of the file -> its record.  Called by all threads of the workgroup, after inf_ph_tables.
-INF_FN void infs_scan_chunk(InfsShared &X, const uint8_t *comp, int64_t comp_len, int64_t chunk_bytes, int64_t k, InfsRecord *rec) {
-    const uint64_t from = (uint64_t)k * (uint64_t)chunk_bytes * 8, next = from + (uint64_t)chunk_bytes * 8;
-    const uint64_t end = next < (uint64_t)comp_len * 8 ? next : (uint64_t)comp_len * 8;
-    if (k == 0) {
-        INF_PHASE(infs_ph_first_header(X, comp, comp_len, t))
-    } else {
-        INF_PHASE(infs_ph_search_init(X, from, t))
-        while (X.found == INFS_NONE && X.pos < end) {
-            INF_PHASE(infs_ph_probe(X, comp, comp_len, end, t))
-            INF_PHASE(infs_ph_confirm(X, comp, comp_len, t))
-        }
+// the two halves of a chunk's work: the first candidate at or behind bit `from` (X.found), and the count from X.found
+INF_FN void infs_scan_search(InfsShared &X, const uint8_t *comp, int64_t comp_len, uint64_t from, uint64_t end) {
+    INF_PHASE(infs_ph_search_init(X, from, t))
+    while (X.found == INFS_NONE && X.pos < end) {
+        INF_PHASE(infs_ph_probe(X, comp, comp_len, end, t))
+        INF_PHASE(infs_ph_confirm(X, comp, comp_len, t))
     }
+}
+INF_FN void infs_scan_count(InfsShared &X, const uint8_t *comp, int64_t comp_len, uint64_t next, InfsRecord *rec) {
     if (X.found != INFS_NONE) {
         INF_PHASE(infs_ph_start(X, X.found, t))
         for (;;) {
@@ -247,6 +243,17 @@ INF_FN void infs_scan_chunk(InfsShared &X, const uint8_t *comp, int64_t comp_len
         }
     }
     INF_PHASE(infs_ph_record(X, rec, t))
+}
+// chunk k of the file -> its record.  Called by all threads of the workgroup, after inf_ph_tables.
+INF_FN void infs_scan_chunk(InfsShared &X, const uint8_t *comp, int64_t comp_len, int64_t chunk_bytes, int64_t k, InfsRecord *rec) {
+    const uint64_t from = (uint64_t)k * (uint64_t)chunk_bytes * 8, next = from + (uint64_t)chunk_bytes * 8;
+    const uint64_t end = next < (uint64_t)comp_len * 8 ? next : (uint64_t)comp_len * 8;
+    if (k == 0) {
+        INF_PHASE(infs_ph_first_header(X, comp, comp_len, t))
+    } else {
+        infs_scan_search(X, comp, comp_len, from, end);
+    }
+    infs_scan_count(X, comp, comp_len, next, rec);
 }
 
 // ---- chain ----
@@ -419,8 +426,9 @@ INF_FN void infs_decode_segment(InfsShared &X, const uint8_t *comp, int64_t comp
 }
 
 // ---- tails and rest: staged values -> final bytes ----
-// staged value at plain position g.off + p -> its byte; the source of a marker is final already (a tail in front)
-INF_FN void infs_resolve(InfsSegment *g, const uint16_t *stage, uint8_t *out, uint64_t p) {
+// staged value at plain position g.off + p -> its byte; the source of a marker is final already (a tail in front).
+// hist (the windowed form, bdx_inflate_window_core.h; else NULL): the 32 KiB in front of out[0], hist[32767] the nearest
+INF_FN void infs_resolve(InfsSegment *g, const uint16_t *stage, uint8_t *out, uint64_t p, const uint8_t *hist = nullptr) {
     const uint32_t v = stage[g->off + p];
     uint8_t byte = (uint8_t)v;
     if (v & 0x8000u) {
@@ -428,6 +436,8 @@ INF_FN void infs_resolve(InfsSegment *g, const uint16_t *stage, uint8_t *out, ui
         if (g->off - g->member_first < back) {
             g->status = INF_E_DISTANCE;  // (every lane that finds one stores the same word)
             byte = 0;
+        } else if (hist && back > g->off) {
+            byte = hist[INFS_WINDOW - (back - g->off)];
         } else {
             byte = out[g->off - back];
         }
@@ -436,14 +446,14 @@ INF_FN void infs_resolve(InfsSegment *g, const uint16_t *stage, uint8_t *out, ui
 }
 INF_FN uint64_t infs_tail_from(const InfsSegment *g) { return g->n > INFS_WINDOW ? g->n - INFS_WINDOW : 0; }
 // ONE workgroup, the segments in order
-INF_FN void infs_tails(InfsSegment *seg, int64_t n_seg, const uint16_t *stage, uint8_t *out) {
+INF_FN void infs_tails(InfsSegment *seg, int64_t n_seg, const uint16_t *stage, uint8_t *out, const uint8_t *hist = nullptr) {
     for (int64_t i = 0; i < n_seg; ++i) {
-        INFS_PHASE_WG(for (uint64_t p = infs_tail_from(seg + i) + (uint64_t)t; p < seg[i].n; p += (uint64_t)nt) infs_resolve(seg + i, stage, out, p))
+        INFS_PHASE_WG(for (uint64_t p = infs_tail_from(seg + i) + (uint64_t)t; p < seg[i].n; p += (uint64_t)nt) infs_resolve(seg + i, stage, out, p, hist))
     }
 }
-INF_FN void infs_ph_rest(InfsSegment *g, const uint16_t *stage, uint8_t *out, int t) {
+INF_FN void infs_ph_rest(InfsSegment *g, const uint16_t *stage, uint8_t *out, const uint8_t *hist, int t) {
     const uint64_t to = infs_tail_from(g);
-    for (uint64_t p = (uint64_t)t; p < to; p += INF_THREADS) infs_resolve(g, stage, out, p);
+    for (uint64_t p = (uint64_t)t; p < to; p += INF_THREADS) infs_resolve(g, stage, out, p, hist);
 }
 INF_FN void infs_ph_crc_init(InfsShared &X, int t) {
     if (t == 0) X.crc = X.S.crc = 0;
@@ -477,8 +487,8 @@ INF_FN void infs_ph_crc_store(const InfsShared &X, InfsSegment *g, int t) {
     if (t == 0) g->crc = X.crc;
 }
 // one wave per segment, after infs_tails
-INF_FN void infs_rest_segment(InfsShared &X, InfsSegment *g, const uint16_t *stage, uint8_t *out) {
-    INF_PHASE(infs_ph_rest(g, stage, out, t))
+INF_FN void infs_rest_segment(InfsShared &X, InfsSegment *g, const uint16_t *stage, uint8_t *out, const uint8_t *hist = nullptr) {
+    INF_PHASE(infs_ph_rest(g, stage, out, hist, t))
     INF_PHASE(infs_ph_crc_init(X, t))
     const uint64_t n = g->n;
     for (uint64_t at = 0; at < n; at += INFS_REBASE) {

@@ -25,6 +25,19 @@ With ``gunzip_stream`` (``execute_demultiplexing(..., _gunzip="device-stream")``
 bdx_fq_inflate_stream_device (csrc/bdx_inflate_stream.hip: speculative block starts, every CRC-32 and ISIZE checked),
 the compressed copy is freed and the text stays RESIDENT in device memory.  A batch's window is then a pointer into it:
 nothing is uploaded per batch.  Peak device memory: the compressed bytes plus three times the plain bytes.
+
+With ``gunzip_window`` (``execute_demultiplexing(..., _gunzip="device-window")``) the same ordinary gzip file, of ANY
+size, goes through the device in WINDOWS of that many compressed bytes (bdx_fq_inflate_window_*, csrc/
+bdx_inflate_window_core.h): the upload thread copies the next window's compressed bytes while the calling thread works
+on the current batch; the calling thread feeds a window, on the context's stream, whenever the text behind the cursor
+is shorter than the batch wants; what a window left unconsumed (a block and a header at most, as a rule) is put in
+front of the next one by a device-to-device copy; new text goes behind the text no batch has taken yet.  Peak device
+memory of an input: two windows of compressed bytes (each with a reserve in front for the remainder), three times the
+largest single window's text (the text and, during the call, its 16-bit image), and twice the text one batch holds —
+whatever the file's size.  A window that holds no complete block is offered again twice as long, up to 2^28 bytes.
+A member's CRC-32 and ISIZE are known at its end only: a refused member raises BdxError after the batches of the
+windows before it were written, as with the host inflate; "refused before the first batch" holds for the resident
+mode alone.
 """
 from __future__ import annotations
 
@@ -153,21 +166,33 @@ def check_gunzip_inputs(paths, lib) -> None:
             open_members(p, lib).close()
 
 
-def check_stream_inputs(paths) -> None:
+def check_stream_inputs(paths, mode: str = "device-stream") -> None:
     """execute_demultiplexing calls this before it makes the output directory: a .gz input of the stream inflate
-    begins with a gzip header"""
+    (resident or windowed) begins with a gzip header"""
     for p in paths:
         if _is_gz(p):
             with open(p, "rb") as f:
                 head = f.read(3)
             if head != b"\x1f\x8b\x08":
-                raise ValueError(f"_gunzip='device-stream' cannot take {p}: it does not begin with a gzip header (1f 8b 08)")
+                raise ValueError(f"_gunzip='{mode}' cannot take {p}: it does not begin with a gzip header (1f 8b 08)")
 
 
 STREAM_CHUNK = 0  # chunk_bytes of the stream inflate (0: bdx_fq_inflate_stream_chunk()); tools/e2e_device_probe.py sweeps it
 _STREAM_INFO = ("stream_members", "stream_chunks", "stream_confirmed", "stream_discarded", "stream_no_candidate",
                 "stream_longest_segment")
 _E_SPACE = -5  # BDX_E_SPACE
+# compressed bytes per window of _gunzip="device-window": the largest, and the fastest of 16, 64 and 256 MiB on the 10 M read
+# file (a 16 MiB window costs some 0.14 s beyond its share of the inflate; profiles/r09_e2e_gunzip_window.json)
+WINDOW_BYTES = 1 << 28
+WINDOW_MIN, WINDOW_MAX = 1024, 1 << 28
+_WINDOW_LEAD = 1 << 20  # room in front of a window's fresh bytes for what the window before left (or the window's size, if smaller)
+
+
+def window_bytes(v) -> int:
+    """_gunzip_window as execute_demultiplexing takes it: an int of 1024 .. 2^28 (ValueError otherwise)"""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not WINDOW_MIN <= int(v) <= WINDOW_MAX:
+        raise ValueError(f"_gunzip_window must be an int of {WINDOW_MIN} .. {WINDOW_MAX} (2^28) compressed bytes, got {v!r}")
+    return int(v)
 
 
 class _Input:
@@ -175,16 +200,20 @@ class _Input:
     COMPRESSED members and their table) and its device side (two byte windows, the line table of the current batch).
     ``io_lib`` is libbdx_io.so, ``classifier`` the context whose stream the inflate and the index run on, ``busy`` the
     run's counters.  ``resident``: the stream inflate puts the whole text into device memory once (inflate_resident);
-    the windows are then places in it."""
+    the windows are then places in it.  ``window`` (compressed bytes, 0: not this mode): the windowed stream inflate —
+    the file is mapped, its text appears in ``res`` a window at a time (feed) and leaves it batch by batch."""
 
     def __init__(self, path: str, rt: _Runtime, io_lib, classifier, busy: dict, batch_reads: int, members=None,
-                 resident: bool = False):
+                 resident: bool = False, window: int = 0):
         self.path = path
         self.rt, self.L, self.cl, self.busy, self.batch_reads = rt, io_lib, classifier, busy, batch_reads
         self.gz = members  # nativeio.GzMembers: this input is inflated on the device
-        self.res = _DevBuf(rt) if resident else None  # the resident text and its length
+        self.res = _DevBuf(rt) if resident or window else None  # the resident text and its length
         self.res_len = 0
-        self.f = nativeio.FastqFile(path) if members is None and not resident else None
+        self.f = nativeio.FastqFile(path) if members is None and not resident and not window else None
+        self.w = None  # the windowed mode: the window object, the mapped file, where it stands
+        if window:
+            self.open_window(int(window))
         self.comp = [_DevBuf(rt), _DevBuf(rt)]  # compressed form: the members of the window
         self.wmem = [(0, 0), (0, 0)]            # ... which ones: [first, last)
         self.d_text = [0, 0]                    # where the window's text starts on the device
@@ -198,14 +227,18 @@ class _Input:
         self.d_len.ensure(4 * batch_reads * 4)
 
     def want_bytes(self) -> int:
-        return int(self.batch_reads * self.avg_record * 1.05) + 65536
+        # (the windowed mode keeps what it asks for in device memory: a small allowance; index() doubles it when it was short)
+        return int(self.batch_reads * self.avg_record * 1.05) + (4096 if self.w is not None else 65536)
 
     def upload(self, s_copy: int, slot: int, want: int):
         """bytes [cursor, cursor + want) of the input (what is there of them) -> the device window `slot`"""
         t0 = time.perf_counter()
         # (the current device belongs to the thread: the upload thread has to choose it as well)
         self.rt.check(self.rt.hipSetDevice(int(getattr(self.cl, "device", 0))), "hipSetDevice")
-        if self.res is not None:  # resident: a window is a place in the text (64 bytes of slack follow its end)
+        if self.w is not None:  # windowed: the next window's compressed bytes, beside the current batch's kernels
+            if self.pending is None and self.f_up < self.wsize:
+                self.fetch(s_copy, self.wbytes)
+        elif self.res is not None:  # resident: a window is a place in the text (64 bytes of slack follow its end)
             end = min(self.res_len, self.cursor + want)
             self.win[slot] = (max(0, end - self.cursor), end >= self.res_len)
             self.d_text[slot] = self.res.p + self.cursor
@@ -295,6 +328,145 @@ class _Input:
             comp.free()
             g.close()
 
+    # ---- the windowed stream inflate ----
+    def open_window(self, window: int):
+        lib, h = self.cl.lib, self.cl.h
+        chunk = int(STREAM_CHUNK) or int(lib.bdx_fq_inflate_stream_chunk())
+        self.wbytes = min(WINDOW_MAX, -(-window // chunk) * chunk)  # a multiple of the chunk size
+        self.lead = min(self.wbytes, _WINDOW_LEAD)
+        self.wmap = nativeio.GzMembers(self.path, int(lib.bdx_fq_inflate_member_max()))  # (maps any .gz; its table is not used)
+        self.wsize = int(self.wmap.size)
+        w = C.c_void_p()
+        try:
+            self.cl._check(lib.bdx_fq_inflate_window_open(h, int(STREAM_CHUNK), C.byref(w)))
+        except BaseException:
+            self.wmap.close()
+            raise
+        self.w = w
+        self.f_up = 0        # the file's bytes below it have gone up
+        self.pos = 0         # where the window object stands: the sum of what it consumed
+        self.released = 0    # the host pages below it were let go
+        self.pending = None  # the window that went up and was not fed yet: [buffer, first byte, end, offset in the buffer]
+        self.cur = None      # the window fed last, likewise: the file's bytes [pos, end) of it are the remainder
+        self.ended = False   # the last window is through
+        self.t_base = 0      # the plain offset of res[0]; res_len bytes of text follow it
+        self.ratio = 4.5     # plain bytes per compressed byte, learned from the windows so far
+        self.busy.setdefault("stream_windows", 0)
+        self.busy["stream_window_bytes"] = self.wbytes
+        self.busy.setdefault("stream_text_peak_bytes", 0)
+
+    def fetch(self, s_copy: int, n: int):
+        """the file's next n bytes (what is there of them) -> the device buffer the current window is not in, behind
+        its reserve (the upload thread; the calling thread when it needs a window at once)"""
+        rt = self.rt
+        i = 1 - self.cur[0] if self.cur is not None else 0
+        n = min(n, self.wsize - self.f_up, WINDOW_MAX - self.lead)  # (with the remainder in front still a window the entry takes)
+        dst = self.comp[i].ensure(self.lead + n, exact=True)
+        if n:
+            rt.check(rt.hipMemcpyAsync(dst + self.lead, self.wmap.data + self.f_up, n, _H2D, s_copy), "hipMemcpyAsync (upload)")
+            rt.check(rt.hipStreamSynchronize(s_copy), "hipStreamSynchronize (upload)")
+        self.pending = [i, self.f_up, self.f_up + n, self.lead]
+        self.f_up += n
+        self.busy["compressed_in_bytes"] += n
+
+    def _d2d(self, dst: int, src: int, n: int):
+        if n:
+            self.rt.check(self.rt.hipMemcpyAsync(dst, src, n, 3, self.s_main), "hipMemcpyAsync (device to device)")
+
+    def feed(self, s_copy: int, grow: int = 0):
+        """One more window through the window object, on the context's stream: the remainder of the window before goes
+        in front of the pending one (fetched here when the upload thread has not brought one; `grow`: at least that
+        many fresh bytes, after a window without progress), the text behind the text no batch has taken yet.
+        -> True when the object made progress"""
+        rt, lib = self.rt, self.cl.lib
+        t_i = time.perf_counter()
+        if self.pending is None:
+            t_u = time.perf_counter()
+            self.fetch(s_copy, max(grow, self.wbytes))
+            self.busy["upload_s"] += time.perf_counter() - t_u
+            t_i += time.perf_counter() - t_u
+        nxt, self.pending = self.pending, None
+        if self.cur is not None:
+            i, f0, f1, off = self.cur
+            rem = f1 - self.pos
+            src = self.comp[i].p + off + (self.pos - f0)
+            if rem > nxt[3]:  # more than the reserve holds: a buffer for both, nothing goes up again
+                both = _DevBuf(rt)
+                both.ensure(rem + (nxt[2] - nxt[1]) + 64, exact=True)
+                self._d2d(both.p, src, rem)
+                self._d2d(both.p + rem, self.comp[nxt[0]].p + nxt[3], nxt[2] - nxt[1])
+                rt.check(rt.hipStreamSynchronize(self.s_main), "hipStreamSynchronize")
+                self.comp[nxt[0]].free()
+                self.comp[nxt[0]] = both
+                nxt[3] = rem
+            else:
+                self._d2d(self.comp[nxt[0]].p + nxt[3] - rem, src, rem)
+            nxt[1], nxt[3] = self.pos, nxt[3] - rem
+        self.cur = nxt
+        i, f0, f1, off = nxt
+        flen = min(f1 - f0, WINDOW_MAX)
+        last = int(f0 + flen == self.wsize)
+        used, plen, info = C.c_int64(0), C.c_int64(0), np.zeros(8, dtype=np.int64)
+        need = int(flen * self.ratio * 1.1) + 4096
+        for attempt in range(2):
+            self.text_room(need)
+            room = self.res.cap - self.res_len - 64
+            rc = lib.bdx_fq_inflate_window_feed(self.w, self.comp[i].p + off, flen, last, self.res.p + self.res_len, room, C.byref(used),
+                                                C.byref(plen), info.ctypes.data)
+            if rc != _E_SPACE:
+                break
+            need = int(plen.value)  # the room it asked for: the same call again, once
+        if rc != 0:
+            raise BdxError(f"{self.path}: refused by the device stream inflate in the window at compressed byte {self.pos}: "
+                           f"{lib.bdx_last_error(self.cl.h).decode()}")
+        self.pos += int(used.value)
+        self.res_len += int(plen.value)
+        self.ended = bool(last)
+        if plen.value and flen:
+            self.ratio = max(1.0, plen.value / max(1, used.value))
+        self.busy["plain_in_bytes"] += int(plen.value)
+        self.busy["stream_windows"] += 1
+        for name, v in zip(_STREAM_INFO, info.tolist()):
+            self.busy[name] = max(v, self.busy.get(name, 0)) if name == "stream_longest_segment" else self.busy.get(name, 0) + v
+        self.busy["inflate_s"] += time.perf_counter() - t_i
+        return bool(used.value or plen.value or last)
+
+    def text_room(self, need: int):
+        """room for `need` more bytes of text (and 64 of slack) behind res_len: the text no batch has taken yet moves to
+        the front when it does not overlap itself there, else into a larger buffer.  On the context's stream: ordered
+        behind the gathers of the batch before, which read the old places."""
+        keep = self.t_base + self.res_len - self.cursor
+        front = self.cursor - self.t_base
+        if self.res.cap - self.res_len - 64 >= need:
+            return
+        if front >= keep and self.res.cap - keep - 64 >= need:
+            self._d2d(self.res.p, self.res.p + front, keep)
+        else:
+            new = _DevBuf(self.rt)
+            new.ensure(keep + need + 64, exact=True)
+            self._d2d(new.p, self.res.p + front, keep)
+            self.rt.check(self.rt.hipStreamSynchronize(self.s_main), "hipStreamSynchronize")
+            self.res.free()
+            self.res = new
+            self.busy["stream_text_peak_bytes"] = max(self.busy["stream_text_peak_bytes"], new.cap)
+        self.t_base, self.res_len = self.cursor, keep
+
+    def fill(self, s_copy: int, slot: int, want: int):
+        """windows until `want` bytes of text lie behind the cursor or the file has ended -> the batch's window"""
+        grow = 0
+        while not self.ended and self.t_base + self.res_len - self.cursor < want:
+            if self.feed(s_copy, grow):
+                grow = 0
+                continue
+            have = self.cur[2] - self.pos  # no progress: no complete block in it — twice as long, to the file's end
+            if have >= WINDOW_MAX or (self.cur[2] >= self.wsize):
+                raise BdxError(f"{self.path}: a deflate block at compressed byte {self.pos} does not fit a window of {WINDOW_MAX} bytes")
+            grow = min(max(have, self.wbytes), WINDOW_MAX - have)
+        avail = self.t_base + self.res_len - self.cursor
+        nbytes = min(avail, want)
+        self.win[slot] = (nbytes, self.ended and avail <= want)
+        self.d_text[slot] = self.res.p + (self.cursor - self.t_base)
+
     def inflate(self, slot: int):
         """comp[slot] -> text[slot] on the context's stream (the calling thread); the window's text starts at the
         cursor, somewhere inside the first member"""
@@ -330,6 +502,8 @@ class _Input:
         while True:
             if self.gz is not None:
                 self.inflate(slot)
+            if self.w is not None:  # the windowed mode feeds, it uploads nothing again
+                self.fill(s_copy, slot, want)
             nbytes, final = self.win[slot]
             n, nxt = C.c_int64(0), C.c_int64(0)
             self.cl._check(self.cl.lib.bdx_fq_index_device(self.cl.h, self.d_text[slot], nbytes, int(final), self.batch_reads,
@@ -337,12 +511,19 @@ class _Input:
             if n.value >= self.batch_reads or final:
                 return n.value, nxt.value
             want = 2 * max(want, nbytes)  # a record did not fit: a larger window
+            if self.w is not None:
+                continue
             t_up = time.perf_counter()
             self.upload(s_copy, slot, want)
             self.busy["device_s"] -= time.perf_counter() - t_up  # (upload_s has it; the driver counts this whole call)
 
     def release(self):
         """everything below the cursor is uploaded: the host pages can go"""
+        if self.w is not None:
+            if self.pos > self.released:  # (once a window, not once a batch: dropping pages the runtime may still have pinned is not free)
+                self.wmap.release(self.pos)
+                self.released = self.pos
+            return
         if self.res is not None:
             return
         if self.gz is None:
@@ -357,6 +538,10 @@ class _Input:
         for f in (self.f, self.gz):
             if f is not None:
                 f.close()
+        if self.w is not None:
+            self.cl.lib.bdx_fq_inflate_window_close(self.w)
+            self.wmap.close()
+            self.w = None
 
 
 class _Slots:
@@ -441,7 +626,7 @@ def _write_loop(q_w, slots: _Slots, errors: list, rt: _Runtime, L, layout: Outpu
 
 def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
                  classifier, batch_reads: int, timings: Optional[dict] = None, gzip_device: bool = False,
-                 gunzip_device: bool = False, gzip_level: int = 1, gunzip_stream: bool = False) -> None:
+                 gunzip_device: bool = False, gzip_level: int = 1, gunzip_stream: bool = False, gunzip_window: int = 0) -> None:
     """Device counterpart of nativeio.demux_native (same arguments but ``on_batch``: the HIP classifier keeps the
     summary tables itself).  ``classifier`` must be the HIP classifier.  ``gzip_device``: gzip output is compressed by
     bdx_fq_deflate_device after the gathers, only finished gzip members are downloaded and the writer appends them as
@@ -450,7 +635,9 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
     compressed and inflated by bdx_fq_inflate_device (inert for a plain input; ValueError for a .gz that is no chain of
     size-tagged members of at most bdx_fq_inflate_member_max() bytes).  ``gunzip_stream``: every input whose name ends
     in .gz is an ordinary gzip file: uploaded whole, inflated by bdx_fq_inflate_stream_device before the first batch
-    and kept resident (inert for a plain input; BdxError naming the file when a member is refused)."""
+    and kept resident (inert for a plain input; BdxError naming the file when a member is refused).
+    ``gunzip_window`` (compressed bytes; 0: not this mode): every such input goes through a window object of its own in
+    windows of that size (the module docstring has the flow, the memory bound and when a refusal is raised)."""
     if not hasattr(classifier, "classify_device"):
         raise ValueError("the device FASTQ pipeline (_io='device') needs the HIP classifier")
     t_wall = time.perf_counter()
@@ -481,7 +668,8 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
         for path in (fastq1, fastq2) if paired else (fastq1,):  # (each input judged on its own)
             members = open_members(path, lib) if gunzip_device and _is_gz(path) else None
             try:
-                ins.append(_Input(path, rt, L, classifier, busy, batch_reads, members, resident=gunzip_stream and _is_gz(path)))
+                ins.append(_Input(path, rt, L, classifier, busy, batch_reads, members, resident=gunzip_stream and _is_gz(path),
+                                  window=int(gunzip_window) if gunzip_window and _is_gz(path) else 0))
             except BaseException:
                 if members is not None:
                     members.close()
@@ -491,7 +679,9 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
         s_main, s_copy = rt.stream(), rt.stream()
         classifier.set_stream(s_main)
         for inp in ins:
-            if inp.res is not None:
+            if inp.w is not None:
+                inp.s_main = s_main
+            elif inp.res is not None:
                 inp.inflate_resident(s_copy)
         d_seq, d_seq_off, d_out, d_gz = _DevBuf(rt), _DevBuf(rt), _DevBuf(rt), _DevBuf(rt)
         d_v = {k: _DevBuf(rt) for k in ("bc1", "bc2", "keep_start", "keep_end")}

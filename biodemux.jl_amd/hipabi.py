@@ -44,6 +44,8 @@ ABI_SYMBOLS = [
     "bdx_fq_inflate_member_max", "bdx_fq_inflate_device",
     # stream inflate of an ordinary .gz input (bdx_inflate_stream.hip)
     "bdx_fq_inflate_stream_chunk", "bdx_fq_inflate_stream_device",
+    # the same in windows, from a carried state (bdx_inflate_window_core.h)
+    "bdx_fq_inflate_window_open", "bdx_fq_inflate_window_feed", "bdx_fq_inflate_window_close",
 ]
 STATS_WHICH = {"pos": 0, "len": 1, "raw": 2}
 BDX_COMM_ID_BYTES = 128
@@ -267,6 +269,12 @@ def load_library(path: Optional[str] = None):
     L.bdx_fq_inflate_stream_chunk.argtypes = []
     L.bdx_fq_inflate_stream_device.restype = C.c_int32
     L.bdx_fq_inflate_stream_device.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int64, vp, vp]
+    L.bdx_fq_inflate_window_open.restype = C.c_int32
+    L.bdx_fq_inflate_window_open.argtypes = [vp, C.c_int32, vp]
+    L.bdx_fq_inflate_window_feed.restype = C.c_int32
+    L.bdx_fq_inflate_window_feed.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int64, vp, vp, vp]
+    L.bdx_fq_inflate_window_close.restype = C.c_int32
+    L.bdx_fq_inflate_window_close.argtypes = [vp]
     if path is None:
         _lib = L
     return L

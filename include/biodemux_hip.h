@@ -390,6 +390,36 @@ int32_t bdx_fq_inflate_stream_chunk(void);
 int32_t bdx_fq_inflate_stream_device(bdx_ctx *ctx, const uint8_t *d_comp, int64_t comp_len, int32_t chunk_bytes,
                                      uint8_t *d_out, int64_t out_cap, int64_t *plain_len, int64_t *info);
 
+/* The stream inflate in WINDOWS (csrc/bdx_inflate_window_core.h): the same file, of any size, goes through the device
+ * a bounded window at a time.  A window object carries what the next window needs: where the position is (a block
+ * start at a bit of the next byte, a member's trailer, between members, trailing bytes), the member's index, CRC-32 and
+ * size so far, and the last 32 KiB of plain text (about 64 KiB of device memory).  Several objects may share a context;
+ * the scratch of a call is the context's and is not kept between calls.
+ *
+ * bdx_fq_inflate_window_open: chunk_bytes as for bdx_fq_inflate_stream_device.  The object stands at byte 0 of a file.
+ * Its state is initialised when open returns (it synchronises): the object may be fed on any stream the context is given later.
+ * bdx_fq_inflate_window_feed: d_comp[0, comp_len) are the file's bytes from the absolute offset the object stands at,
+ * the sum of every *consumed so far; comp_len <= 2^28; last != 0 says that they end with the file.  Runs on the
+ * context's stream and synchronises (after the chain, after the verdict) before it returns.
+ *   BDX_OK         d_out[0, *plain_len) is the text of everything consumed; *consumed whole bytes are done with (the
+ *                  byte that holds the next block's first bit is not among them); every member that ended in the
+ *                  window has had its CRC-32 and ISIZE checked.  The window stops at the last block end, trailer or
+ *                  member boundary up to which every bit it needed lay in the buffer.  *consumed == 0 and
+ *                  *plain_len == 0 with last == 0: the buffer holds no complete block — feed a longer one from the same
+ *                  offset.  With last != 0 everything is consumed, or ignored as trailing bytes, or refused.
+ *   BDX_E_SPACE    out_cap is too small: *plain_len is the room needed; nothing is consumed, the object is unchanged
+ *                  and d_out is untouched: the same call with that room succeeds
+ *   BDX_E_INVALID  a member is refused: bdx_last_error names its index in the file, the absolute compressed byte and
+ *                  one of the eleven reasons.  The object is dead: every later feed returns BDX_E_STATE.
+ * info as for bdx_fq_inflate_stream_device, per call; its first entry counts the members that ended in the window.
+ * Device memory taken for a call: 2 * *plain_len bytes (released before it returns) and 32 bytes per chunk.
+ * bdx_fq_inflate_window_close: waits for the context's stream and frees the object (NULL is allowed). */
+typedef struct bdx_fq_inflate_window bdx_fq_inflate_window;
+int32_t bdx_fq_inflate_window_open(bdx_ctx *ctx, int32_t chunk_bytes, bdx_fq_inflate_window **w);
+int32_t bdx_fq_inflate_window_feed(bdx_fq_inflate_window *w, const uint8_t *d_comp, int64_t comp_len, int32_t last,
+                                   uint8_t *d_out, int64_t out_cap, int64_t *consumed, int64_t *plain_len, int64_t *info);
+int32_t bdx_fq_inflate_window_close(bdx_fq_inflate_window *w);
+
 /* Introspection for bench/tests: name of the kernel path a classify call will take, and numbers of the
  * last launch.  "generic": exact kernel only; "bitpar+verify": bit-vector sweep of every pair, then the exact
  * stage; "qgram+bitpar+verify": single-piece q-gram seeds in front of the sweep; "qgram2+bitpar+verify":

@@ -2,7 +2,7 @@
 """End-to-end reads/s of execute_demultiplexing on the C2 shape: the native host pipeline (_io="native") against the device
 FASTQ pipeline (_io="device"), each run in a fresh child process (GPU box).
 
-  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device} [--gzip-level 2] | --gunzip | --gunzip-stream] [out.json]
+  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device} [--gzip-level 2] | --gunzip | --gunzip-stream | --gunzip-window] [out.json]
 
 One synthetic FASTQ of N 150 bp reads x 96 barcodes (24 bp), max_error_rate=0.1, on tmpfs (/dev/shm unless E2E_ROOT is
 set); the outputs are checked (total bytes = input bytes).  Prints every run with its stage seconds, then the medians; the
@@ -22,7 +22,13 @@ gzip).
 (zlib level 6; slices compressed side by side and joined with sync flushes, as pigz does) and two legs alternate after one
 unrecorded warm-up run: "device++hsin" (_gunzip="host": one zlib thread) and "device++sin" (_gunzip="device-stream").
 Before that, one run of the stream leg per chunk size of 16, 32, 64 and 128 KiB ("sweep").  REPS=5 is what the
-repository's figures use; every leg reports min, median and max wall seconds and the plain GB/s they amount to."""
+repository's figures use; every leg reports min, median and max wall seconds and the plain GB/s they amount to.
+
+--gunzip-window: the same input and the same two legs, and a third, "device++win" (_gunzip="device-window").  Before the
+series, one run of the windowed leg per window size of 16, 64 and 256 MiB (2^28 bytes, the largest) ("sweep"); the series
+then runs the windowed leg at the sweep's fastest size (E2E_WINDOW overrides it), which is reported as "window_bytes".  The
+stream and windowed legs also report "device_peak_bytes": the largest drop of the device's free memory (hipMemGetInfo, sampled
+every 10 ms by a thread of the child; other processes on the device would show in it too) below its value at the start."""
 import json
 import os
 import shutil
@@ -129,6 +135,41 @@ def gz_sizes(path: str):
     return len(d), plain
 
 
+class FreeMemory:
+    """samples the device's free memory from a thread of its own; stop() -> the largest drop below the first sample"""
+
+    def __init__(self, period: float = 0.01):
+        import ctypes as C
+        import threading
+
+        from biodemux_jl_amd.hipabi import load_library
+
+        lib = load_library()
+        lib.hipMemGetInfo.restype = C.c_int
+        lib.hipMemGetInfo.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        self.done = threading.Event()
+
+        def free():
+            f, t = C.c_size_t(0), C.c_size_t(0)
+            return f.value if lib.hipMemGetInfo(C.byref(f), C.byref(t)) == 0 else None
+
+        self.first = self.low = free()
+
+        def loop():
+            while not self.done.wait(period):
+                f = free()
+                if f is not None and self.low is not None:
+                    self.low = min(self.low, f)
+
+        self.thread = threading.Thread(target=loop, name="bdx-probe-free-memory", daemon=True)
+        self.thread.start()
+
+    def stop(self):
+        self.done.set()
+        self.thread.join()
+        return None if self.first is None else int(self.first - self.low)
+
+
 def child(mode: str) -> None:
     import biodemux_jl_amd as bdx
 
@@ -143,7 +184,8 @@ def child(mode: str) -> None:
         kw["_gzip"] = "device"
     if gz == "dgz2":
         kw["_gzip_level"] = 2
-    if gin in ("hsin", "sin"):
+    sampler = None
+    if gin in ("hsin", "sin", "win"):
         from biodemux_jl_amd import deviceio
 
         fq = fq[:-6] + ".stream.fastq.gz"
@@ -151,6 +193,12 @@ def child(mode: str) -> None:
         if gin == "sin":
             kw["_gunzip"] = "device-stream"
             deviceio.STREAM_CHUNK = int(os.environ.get("E2E_STREAM_CHUNK", "0"))
+        if gin == "win":
+            kw["_gunzip"] = "device-window"
+            if os.environ.get("E2E_WINDOW"):
+                kw["_gunzip_window"] = int(os.environ["E2E_WINDOW"])
+        if gin != "hsin":
+            sampler = FreeMemory()
     elif gin:
         fq += ".gz"
     if gin == "din":
@@ -158,6 +206,8 @@ def child(mode: str) -> None:
     t = time.perf_counter()
     bdx.execute_demultiplexing(fq, bc, out, max_error_rate=0.1, _io=io, _timings=tm, **kw)
     dt = time.perf_counter() - t
+    if sampler is not None:
+        tm["device_peak_bytes"] = sampler.stop()
     files = [os.path.join(out, f) for f in os.listdir(out)]
     if gz:
         sizes = [gz_sizes(f) for f in files]
@@ -192,6 +242,11 @@ def main() -> None:
     if stream:
         modes = ["device++hsin", "device++sin"]
         argv = argv[1:]
+    window = bool(argv) and argv[0] == "--gunzip-window"
+    if window:
+        stream = False
+        modes = ["device++hsin", "device++sin", "device++win"]
+        argv = argv[1:]
     n = int(os.environ.get("N", "10000000"))
     reps = int(os.environ.get("REPS", "3"))
     root = os.environ.get("E2E_ROOT") or "/dev/shm/bdx_e2e_device_probe"
@@ -202,7 +257,7 @@ def main() -> None:
     if gunzip:
         make_gz_input(root)
         gz_bytes = os.path.getsize(os.path.join(root, "synthetic.fastq.gz"))
-    if stream:
+    if stream or window:
         make_stream_gz_input(root)
         gz_bytes = os.path.getsize(os.path.join(root, "synthetic.stream.fastq.gz"))
     gen_s = time.perf_counter() - t0
@@ -220,7 +275,23 @@ def main() -> None:
             r = json.loads(line[0][7:])
             sweep.append({"chunk_kib": kib, "seconds": r["seconds"], "inflate_s": r["stages"].get("inflate_s"), "stages": r["stages"]})
             print(f"SWEEP chunk {kib:4d} KiB  {r['seconds']:.4f} s  inflate_s {r['stages'].get('inflate_s')}", flush=True)
-        for rep in range(-1 if gunzip or stream else 0, reps):  # (rep -1: the warm-up run, not recorded)
+        for mib in (16, 64, 256) if window else ():  # one run per window size
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "device++win"],
+                               env=dict(env, E2E_WINDOW=str(mib << 20)), capture_output=True, text=True, timeout=300)
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+            if p.returncode != 0 or not line:
+                sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
+                raise SystemExit(f"sweep run at {mib} MiB failed (rc {p.returncode})")
+            r = json.loads(line[0][7:])
+            sweep.append({"window_mib": mib, "seconds": r["seconds"], "inflate_s": r["stages"].get("inflate_s"), "stages": r["stages"]})
+            print(f"SWEEP window {mib:4d} MiB  {r['seconds']:.4f} s  inflate_s {r['stages'].get('inflate_s')}  windows "
+                  f"{r['stages'].get('stream_windows')}  text peak {r['stages'].get('stream_text_peak_bytes')}  device peak "
+                  f"{r['stages'].get('device_peak_bytes')}", flush=True)
+        if window:
+            best = int(os.environ.get("E2E_WINDOW") or min(sweep, key=lambda x: x["seconds"])["window_mib"] << 20)
+            env["E2E_WINDOW"] = str(best)
+            print(f"SERIES window {best} bytes", flush=True)
+        for rep in range(-1 if gunzip or stream or window else 0, reps):  # (rep -1: the warm-up run, not recorded)
             for mode in modes[:1] if rep < 0 else modes:
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode], env=env, capture_output=True,
                                    text=True, timeout=600)
@@ -237,7 +308,7 @@ def main() -> None:
                 keys = ("index_s", "pack_s", "classify_s", "write_s") if mode.startswith("native") else ("upload_s", "device_s", "download_s", "write_s")
                 if "+dgz" in mode:
                     keys += ("deflate_s",)
-                if mode.endswith(("+din", "+sin")):
+                if mode.endswith(("+din", "+sin", "+win")):
                     keys += ("inflate_s", "compressed_in_bytes", "plain_in_bytes")
                 print(f"RUN {rep} {mode:10s} {r['seconds']:.4f} s  {r['reads_per_s'] / 1e6:6.1f} M reads/s  "
                       + "  ".join(f"{k} {st.get(k, 0):.4f}" for k in keys) + f"  batches {st.get('batches')}", flush=True)
@@ -248,13 +319,16 @@ def main() -> None:
         summary["input_gz_bytes"] = gz_bytes
     if stream:
         summary["chunk_sweep"] = sweep
+    if window:
+        summary["window_sweep"] = sweep
+        summary["window_bytes"] = int(env["E2E_WINDOW"])
     for mode in modes:
         rs = [r for r in runs if r["mode"] == mode]
         med = statistics.median(r["reads_per_s"] for r in rs)
         secs = sorted(r["seconds"] for r in rs)
         stages = {k: statistics.median(r["stages"][k] for r in rs) for k in rs[0]["stages"] if isinstance(rs[0]["stages"][k], (int, float))}
         summary[mode] = {"median_reads_per_s": med, "median_stage_s": stages, "seconds_min_median_max": [secs[0], statistics.median(secs), secs[-1]]}
-        if stream:  # the leg's plain text per wall second (the host leg: what one zlib thread sustains under the pipeline)
+        if stream or window:  # the leg's plain text per wall second (the host leg: what one zlib thread sustains under the pipeline)
             summary[mode]["plain_gb_per_s_min_median_max"] = [n * 319 / 1e9 / x for x in (secs[-1], statistics.median(secs), secs[0])]
         print(f"MEDIAN {mode:10s} {med / 1e6:.1f} M reads/s  wall s min {secs[0]:.4f} median {statistics.median(secs):.4f} max {secs[-1]:.4f}  " + "  ".join(f"{k} {v:.4f}" for k, v in sorted(stages.items())))
     if argv:
