@@ -16,6 +16,18 @@
 // matches no barcode row), OR-ed onto the group's dword of 4-bit codes.
 BDX_COL_FN uint32_t bdx_col_junk(const int nv) { return nv >= 8 ? 0u : (nv <= 0 ? 0x44444444u : (0x44444444u << (4 * nv))); }
 
+// bdx_col_junk for word u (0..3) of a block of 32 columns of which `rem` (any value) lie inside the window: the count of
+// the word's valid columns clamped to 0..8, and the low word of a 64-bit shift (eight valid columns shift everything out).
+BDX_COL_FN uint32_t bdx_col_junk_word(const int rem, const int u) {
+    int nv = rem - 8 * u;
+    nv = nv < 0 ? 0 : (nv > 8 ? 8 : nv);
+    return (uint32_t)(0x44444444ull << (4 * nv));
+}
+
+// Pv in front of a sweep's first column for a top-aligned barcode of m rows, 1 <= m <= 32 (the planner admits no other
+// length): ones in the top m bits, which is ((1 << m) - 1) << (32 - m) without the special case for m = 32.
+BDX_COL_FN uint32_t bdx_col_pv0(const int m) { return 0xFFFFFFFFu << ((32 - m) & 31); }
+
 // A dword of eight 4-bit codes 0..4 (column k in nibble k) -> two words of byte fields, each 4 x code = the byte offset of
 // the code's word in a barcode's peq row: ev holds columns 0, 2, 4, 6 and od columns 1, 3, 5, 7, column k in byte k >> 1.
 // `mask` is BDX_COL_FIELD_MASK (an argument: the kernel keeps it in a register).

@@ -196,6 +196,46 @@ __device__ __forceinline__ void pack16(const u32x4 v, uint32_t &p2, uint32_t &nl
     p2 = lo | hi;
 }
 
+// pack16 of the LEAN forms (DOT, masks in registers), run by every lane of the wave: no lane sits the fast path out, so it
+// needs no exec-mask region of its own and `sad` reaches the ballot as a plain register.  `live` (the lane holds a vector of
+// the tile; a lane beyond it holds stale bytes, stores nothing and must not call for the exact pack) joins the ballot's
+// predicate instead.  The exact pack — rare: some live lane has a byte that is not its index's letter — corrects the 4-bit
+// codes in place from the fast path's `e`; the 2-bit codes come from `sel` alone and are gathered behind it, next to the
+// stores.  Same p2 / nlo / nhi as pack16<false> followed by pack16<true> for the lanes with sad != 0.
+__device__ __forceinline__ void pack16_lean(const u32x4 v, const bool live, uint32_t &p2, uint32_t &nlo, uint32_t &nhi, const uint32_t m7, const uint32_t m3) {
+    constexpr uint32_t CODE_LO = 0x03020100u, CODE_HI = 0x04040404u;
+    constexpr uint32_t EXP_LO = 0x47544341u, EXP_HI = 0x4E000000u;
+    uint32_t sel[4], n4[4], e[4], sad = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        sel[w] = (v[w] >> 1) & m7;
+        n4[w] = __builtin_amdgcn_perm(CODE_HI, CODE_LO, sel[w]);
+        e[w] = __builtin_amdgcn_perm(EXP_HI, EXP_LO, sel[w]);
+        sad = __builtin_amdgcn_sad_u8(v[w], e[w], sad);
+    }
+    const bool bad = live && sad != 0;
+    if (__builtin_amdgcn_ballot_w64(bad)) {
+        if (bad) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t d = v[w] ^ e[w];
+                const uint32_t y = (((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u;  // 0x80 in every byte that differs
+                const uint32_t m = (y >> 7) * 0xFFu;
+                n4[w] = (n4[w] & ~m) | (m & 0x04040404u);
+            }
+        }
+    }
+    uint32_t u[4], t2[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        u[w] = n4[w] | (n4[w] >> 4);
+        t2[w] = __builtin_amdgcn_udot4(sel[w] & m3, 0x40100401u, 0u, false);
+    }
+    nlo = __builtin_amdgcn_perm(u[1], u[0], 0x06040200u);
+    nhi = __builtin_amdgcn_perm(u[3], u[2], 0x06040200u);
+    p2 = __builtin_amdgcn_perm(t2[1], t2[0], 0x0C0C0400u) | __builtin_amdgcn_perm(t2[3], t2[2], 0x04000C0Cu);
+}
+
 // 32 columns of one sweep; columns [0, TF) cannot end an alignment within any barcode's budget (the score after
 // j + 1 columns is >= m - (j + 1)), so the score is first needed at column TF, where it is popcount(Pv) -
 // popcount(Mv): D[m][j] = D[0][j] + the vertical deltas, D[0][j] = 0 (free start), the virtual rows below the
@@ -483,10 +523,11 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
     // bytes of tile k + 1 are requested while tile k is worked on, its offsets one tile earlier still, so the HBM
     // latency of neither is ever at the head of a tile.
     const int nwaves = (int)(gridDim.x * (blockDim.x >> 6));  // (32-bit: tile numbers stay in scalar registers)
-    // (Workgroup major: the tiles of the last, partial round go to every wave of the first few workgroups.  Dealt with the wave
-    // index major — wave x workgroups + workgroup — they would go to a wave or two of every workgroup; measured, the step is
-    // 0.6 % faster by the medians and the run sets overlap: DESIGN.md §4, round 12.)
-    int tile = (int)(blockIdx.x * (blockDim.x >> 6)) + wv;
+    // The LEAN forms number the waves with the wave index major — wave x workgroups + workgroup — so that the tiles of the
+    // last, partial round go to a wave or two of every workgroup (spread over every compute unit) instead of to every wave of
+    // the first few workgroups; every other form keeps the workgroup-major numbering.  Either way wave w of the grid walks
+    // the tiles w + k x waves.  Measured in alternating runs against the workgroup-major deal: DESIGN.md §4, round 13.
+    int tile = LEAN ? wv * (int)gridDim.x + (int)blockIdx.x : (int)(blockIdx.x * (blockDim.x >> 6)) + wv;
     // geometry of a tile's span from its offsets (lanes 0 .. nr hold off[r0 + lane]); everything wave-uniform
     struct Geo {
         long long span0;
@@ -711,9 +752,14 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
             const int k = 64 * u + lane;
             if (64 * u < nvec) {  // wave-uniform
                 uint32_t p2 = 0, nlo = 0, nhi = 0, sad = 0;
-                if (k < nvec && !BDX_DBG(32)) pack16<false, LEAN>(v[u], p2, nlo, nhi, sad, m7, m3);
-                if (__builtin_amdgcn_ballot_w64(sad != 0)) {  // some byte is neither A, C, G, T nor N (rare)
-                    if (sad != 0) pack16<true, LEAN>(v[u], p2, nlo, nhi, sad, m7, m3);
+                if constexpr (LEAN) {
+                    // (every lane packs; the lanes beyond the tile's last vector pack stale bytes and store nothing)
+                    if (!BDX_DBG(32)) pack16_lean(v[u], k < nvec, p2, nlo, nhi, m7, m3);
+                } else {
+                    if (k < nvec && !BDX_DBG(32)) pack16<false, LEAN>(v[u], p2, nlo, nhi, sad, m7, m3);
+                    if (__builtin_amdgcn_ballot_w64(sad != 0)) {  // some byte is neither A, C, G, T nor N (rare)
+                        if (sad != 0) pack16<true, LEAN>(v[u], p2, nlo, nhi, sad, m7, m3);
+                    }
                 }
                 if (k < nvec) {
                     img2_lane[64 * u] = p2;
@@ -771,12 +817,13 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
 
         // ---- sweeps: lane = one record = one (read, barcode, window) ----
         // (a lambda: split mode runs it a second time for the reads whose tables overflowed, below)
-        const auto sweep_lane = [&](bool valid, const int t, const int b, const int lo, const int hi) __attribute__((always_inline)) {
-            const uint32_t mt = meta[b];
+        // (mt_in: meta[b] where the caller has read it already — the LEAN forms take it from there instead of reading it again)
+        const auto sweep_lane = [&](bool valid, const int t, const int b, const int lo, const int hi, const uint32_t mt_in) __attribute__((always_inline)) {
+            const uint32_t mt = LEAN ? mt_in : meta[b];
             const int mm = (int)(mt & 255u), kk = (int)((mt >> 8) & 255u);
             valid = valid && hi > lo && !BDX_DBG(2);
             const int ncol = valid ? hi - lo : 0;
-            uint32_t Pv = mm >= 32 ? 0xFFFFFFFFu : (((1u << mm) - 1u) << (32 - mm));
+            uint32_t Pv = LEAN ? bdx_col_pv0(mm) : (mm >= 32 ? 0xFFFFFFFFu : (((1u << mm) - 1u) << (32 - mm)));
             uint32_t Mv = 0;
             int score = mm, best = 0x7FFFFFFF;
             // Known-trim class, trim_side = 3 passes: the sweep runs RIGHT TO LEFT over the window with the reversed barcode.  After
@@ -820,13 +867,24 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) A[u] = rev ? R[u] : A[u];
                 }
+                // columns beyond the window become "other" symbols: they match no barcode row, and a column that
+                // matches nothing never lowers the running minimum (D[i][j] >= D[i][j-1] for every row)
+                if constexpr (LEAN) {
+                    // The usual first block — every lane with a record has 24 columns or more (a lane without one has nothing to
+                    // lose: its sweep is dropped) — ends in word 3 in every lane: one mask instead of four (wave-uniform test)
+                    if (!__builtin_amdgcn_ballot_w64(valid && rem < 24)) {
+                        A[3] |= bdx_col_junk_word(rem, 3);
+                    } else {
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    // columns beyond the window become "other" symbols: they match no barcode row, and a column that
-                    // matches nothing never lowers the running minimum (D[i][j] >= D[i][j-1] for every row)
-                    const int nv = rem - 8 * u;
-                    const uint32_t junk = nv >= 8 ? 0u : (nv <= 0 ? 0x44444444u : (0x44444444u << (4 * nv)));
-                    A[u] |= junk;
+                        for (int u = 0; u < 4; ++u) A[u] |= bdx_col_junk_word(rem, u);
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int nv = rem - 8 * u;
+                        const uint32_t junk = nv >= 8 ? 0u : (nv <= 0 ? 0x44444444u : (0x44444444u << (4 * nv)));
+                        A[u] |= junk;
+                    }
                 }
                 uint32_t inm = 0u, inm2 = 0u;
                 // the columns some lane still needs, LEAN forms: to the column, else in groups of eight (the tail block of a 33..48-column window is mostly junk)
@@ -916,7 +974,7 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                 const int wlo = win_lo(t, b >= a.B0), whi = win_hi(t, b >= a.B0, n);
                 lo = lo < wlo ? wlo : lo;
                 hi = hi > whi ? whi : hi;
-                sweep_lane(valid, t, b, lo, hi);
+                sweep_lane(valid, t, b, lo, hi, mt);
             }
             nhq = 0;
             WAVE_SYNC();
@@ -1454,8 +1512,10 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
             valid = valid && id != 0u && dmk != 0u;
             const int t = (int)(rslot / RCAP), b = valid ? (int)(id & 0xFFFFu) - 1 : 0;
             int lo = 0, hi = 0;  // [lo, hi): 0-based columns of the sweep
+            uint32_t mt_rec = 0u;  // (LEAN forms: the record's meta word goes on to the sweep)
             if (valid) {
                 const uint32_t mt = meta[b];
+                if (LEAN) mt_rec = mt;
                 const int mm = (int)(mt & 255u), kk = (int)((mt >> 8) & 255u);
                 const int d0 = (int)(id >> 16) - 64;
                 const int dmin = d0 + __builtin_ctz(dmk) - kk, dmax = d0 + (31 - __builtin_clz(dmk)) - kk;
@@ -1473,7 +1533,7 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                 lo = lo < wlo ? wlo : lo;
                 hi = hi > whi ? whi : hi;
             }
-            sweep_lane(valid, t, b, lo, hi);
+            sweep_lane(valid, t, b, lo, hi, mt_rec);
         }
         WAVE_SYNC();
         if (SPLIT || !PAIRS) {
@@ -1504,7 +1564,7 @@ __global__ BDX_WAVE_BOUNDS void bdx_wave_kernel(const WaveArgs a) {
                 for (int b0 = 0; b0 < B; b0 += 64) {
                     const int b = b0 + lane < B ? b0 + lane : 0;
                     const bool valid = b0 + lane < B && ((meta[b] >> 8) & 255u) != 255u;  // (255: the barcode can never be recorded)
-                    sweep_lane(valid, t, b, win_lo(t, b >= a.B0), win_hi(t, b >= a.B0, n));
+                    sweep_lane(valid, t, b, win_lo(t, b >= a.B0), win_hi(t, b >= a.B0, n), LEAN ? meta[b] : 0u);
                 }
                 WAVE_SYNC();
             }
