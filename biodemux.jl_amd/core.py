@@ -165,7 +165,8 @@ def _device_list(device: int, devices, io: str) -> List[int]:
         # the device pipeline finds batch k + 1's first record only after batch k's index ran on the device: dealing
         # batches over contexts needs another design, and falling back to the host pipeline would hide that
         raise ValueError("_io='device' drives one device context: batch boundaries are found on the device, so batches "
-                         "cannot be dealt over several devices; use _io='native' (or 'auto') with devices=")
+                         "cannot be dealt over several devices; use _io='native' (or 'auto') with devices=, or "
+                         "_io='device-deal', which deals byte spans of a single-end input over the contexts")
     return devs
 
 
@@ -196,7 +197,8 @@ def _close_all(classifiers) -> None:
 def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxConfig], object]] = None,
                            _batch_reads: int = DEFAULT_BATCH_READS, _io: str = "auto", device: int = 0,
                            devices=None, _timings: Optional[dict] = None, _gzip: str = "host", _gunzip: str = "host",
-                           _gzip_level: int = 1, _gunzip_window: Optional[int] = None, **kw):
+                           _gzip_level: int = 1, _gunzip_window: Optional[int] = None, _span_bytes: Optional[int] = None,
+                           **kw):
     """execute_demultiplexing(FASTQ_file, barcode_file, output_directory; kwargs...)      core.jl:500
     execute_demultiplexing(FASTQ_file1, FASTQ_file2, barcode_file, output_directory; ...)  core.jl:360
 
@@ -204,6 +206,14 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
     ``_io`` selects the host-side reader/writer: "native" (csrc/bdx_io.cpp, threads), "python" (the
     plain reference implementation below), "auto" (native when the library was built) or "device" (index, pack,
     split by output file and gather on the GPU, deviceio.py: needs the HIP classifier).
+    ``_io="device-deal"`` is the device pipeline dealt over the contexts of ``devices`` by byte spans (deviceio.
+    demux_device_dealt): the input is cut into spans of ``_span_bytes`` bytes (an int of at least 16; default
+    ``_batch_reads`` x 330 bytes rounded up to 64 KiB, whatever the number of contexts), a record belongs to the span its
+    first line starts in, every context takes the next span and runs the whole device pipeline on it, one writer
+    appends the blocks in span order.  Same files, counters and reports as ``_io="device"``.  Single-end input only,
+    plain or a ``.gz`` inflated by the host (``_gunzip="host"``); ``_gzip="device"`` works at both levels; ``_timings``
+    then also holds spans, spans_per_device, span_bytes, devices and phase_wait_s, the busy seconds summed over the contexts.
+    (The ValueError for an unknown ``_io`` keeps its earlier wording and does not list "device-deal"; it is a valid value.)
     ``_classifier_factory`` is a test seam: the parity tests on CPU pass the oracle here to
     check this file contract; the product default is the HIP classifier and nothing else.
     ``devices`` (a sequence of HIP device indices, None = ``[device]``): one device context per entry — repeated entries
@@ -252,7 +262,7 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         raise TypeError("execute_demultiplexing takes 3 (single-end) or 4 (paired-end) positional arguments")
     if _gzip not in ("host", "device"):
         raise ValueError("_gzip must be 'host' or 'device'")
-    if _gzip == "device" and _io != "device":  # (no silent fallback to the host deflate)
+    if _gzip == "device" and _io not in ("device", "device-deal"):  # (no silent fallback to the host deflate)
         raise ValueError("_gzip='device' compresses inside the device FASTQ pipeline: it needs _io='device'")
     if isinstance(_gzip_level, bool) or _gzip_level not in (1, 2):
         raise ValueError("_gzip_level must be 1 or 2")
@@ -260,12 +270,23 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         raise ValueError("_gzip_level selects a level of the device encoder: it needs _gzip='device'")
     if _gunzip not in ("host", "device", "device-stream", "device-window"):
         raise ValueError("_gunzip must be 'host', 'device', 'device-stream' or 'device-window'")
+    if _gunzip != "host" and _io == "device-deal":  # (their text, or the state they carry, lives on one device)
+        raise ValueError(f"_io='device-deal' takes a plain input or a .gz the host inflates: _gunzip must be 'host', not '{_gunzip}'")
     if _gunzip != "host" and _io != "device":  # (no silent fallback to the host inflate)
         raise ValueError(f"_gunzip='{_gunzip}' inflates inside the device FASTQ pipeline: it needs _io='device'")
     if _gunzip_window is not None:
         if _gunzip != "device-window":
             raise ValueError("_gunzip_window is the window of _gunzip='device-window'")
         _gunzip_window = deviceio.window_bytes(_gunzip_window)  # (ValueError: not an int of 1024 .. 2^28)
+    if _span_bytes is not None:
+        if _io != "device-deal":
+            raise ValueError("_span_bytes is the span of _io='device-deal'")
+        _span_bytes = deviceio.span_bytes(_span_bytes)  # (ValueError: not an int of at least 16)
+    if _io == "device-deal":
+        if paired:  # (the two files' spans do not hold the same record ranges)
+            raise ValueError("_io='device-deal' takes single-end input: a second FASTQ file needs _io='device' or 'native'")
+        if _classifier_factory is not None:  # (no silent fallback to the host pipeline)
+            raise ValueError("_io='device-deal': the device FASTQ pipeline needs the HIP classifier (no _classifier_factory)")
 
     defaults = dict(
         barcode_file2=None, gzip_output=None, max_error_rate=0.2, min_delta=0.0, match=0, mismatch=1, indel=1,
@@ -335,7 +356,7 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
             hist.add_pass_outputs(out, float(config.min_delta))
 
     try:
-        if _io not in ("auto", "native", "python", "device"):
+        if _io not in ("auto", "native", "python", "device", "device-deal"):
             raise ValueError("_io must be 'auto', 'native', 'python' or 'device'")
         use_native = _io == "native" or (_io == "auto" and nativeio.available())
         if _timings is not None:
@@ -345,6 +366,9 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
                                   _timings, gzip_device=_gzip == "device", gunzip_device=_gunzip == "device",
                                   gzip_level=int(_gzip_level), gunzip_stream=_gunzip == "device-stream",
                                   gunzip_window=(_gunzip_window or deviceio.WINDOW_BYTES) if _gunzip == "device-window" else 0)
+        elif _io == "device-deal":
+            deviceio.demux_device_dealt(fastq1, config, output_directory, prefix1, classifiers, _batch_reads, _timings,
+                                        gzip_device=_gzip == "device", gzip_level=int(_gzip_level), span_bytes=_span_bytes)
         elif use_native:
             t_call = _dt.datetime.now()
             nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers, _batch_reads,
@@ -361,7 +385,7 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         counts = np.sum([np.asarray(c.counts, dtype=np.int64) for c in classifiers], axis=0)
         tables = (merge_stats_tables([c.stats_tables() for c in classifiers]) if (config.summary and device_stats)
                   else None)
-        if multi and _timings is not None:
+        if (multi or _io == "device-deal") and _timings is not None:
             _timings["devices"] = list(devs)
     finally:
         t_close = _dt.datetime.now()

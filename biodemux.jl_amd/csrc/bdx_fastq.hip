@@ -225,6 +225,48 @@ __global__ void index_tail_kernel(const uint8_t *t, int64_t len, int32_t final, 
     res[1] = cur;
 }
 
+// ---- index of one span (bdx_fq_index_span_device) -------------------------------------------------------------------------
+// per workgroup: newlines of its tile in t[0, len) -> blk, those of them in front of byte `lim` (<= len) -> blk_lim
+template <bool kAligned>
+__global__ void __launch_bounds__(FQ_THREADS) span_count_kernel(const uint8_t *t, int64_t len, int64_t lim, long long *blk,
+                                                                long long *blk_lim) {
+    long long c = 0, cl = 0;
+    for (int s = 0; s < FQ_STEPS; ++s) {
+        const int64_t p = (int64_t)blockIdx.x * FQ_TILE + ((int64_t)s * FQ_THREADS + threadIdx.x) * FQ_LANE_BYTES;
+        const uint32_t m = newline_mask16<kAligned>(t, len, p);
+        const int64_t room = lim - p;  // bytes of this lane's 16 that lie in front of lim
+        c += __popc(m);
+        cl += room >= FQ_LANE_BYTES ? __popc(m) : room > 0 ? __popc(m & ((1u << room) - 1u)) : 0;
+    }
+    long long tot, tot_lim;
+    (void)block_excl_scan(c, &tot);
+    (void)block_excl_scan(cl, &tot_lim);
+    if (threadIdx.x == 0) {
+        blk[blockIdx.x] = tot;
+        blk_lim[blockIdx.x] = tot_lim;
+    }
+}
+
+// Table entry k is line first + k of the window, line i being the bytes between newline i - 1 (or the window's start)
+// and newline i.  Of the window's `total` newlines nl holds the first min(total, first + nlines).  Line `total` is the
+// text's unterminated rest, the lines behind it pad a truncated record (the caller hands such lines out only with `final`).
+__global__ void __launch_bounds__(FQ_THREADS) span_lines_kernel(const uint8_t *t, int64_t len, const long long *nl,
+                                                                int64_t total, int64_t first, int64_t nlines,
+                                                                int64_t *line_off, int32_t *line_len) {
+    for (int64_t k = (int64_t)blockIdx.x * FQ_THREADS + threadIdx.x; k < nlines; k += (int64_t)gridDim.x * FQ_THREADS) {
+        const int64_t i = first + k;
+        int64_t s = len, ln = 0;
+        if (i <= total) {
+            s = i ? nl[i - 1] + 1 : 0;
+            const int64_t e = i < total ? nl[i] : len;
+            ln = e - s;
+            if (ln > 0 && t[e - 1] == '\r') ln -= 1;
+        }
+        line_off[k] = s;
+        line_len[k] = (int32_t)ln;
+    }
+}
+
 // ---- pack -----------------------------------------------------------------------------------------------------------------
 struct SeqLen {
     const int32_t *line_len;
@@ -485,6 +527,95 @@ int32_t bdx_fq_index_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_le
     HIP_TRY(ctx, read_back(ctx, small, res, 16));
     *n_records = res[0];
     *next = res[1];
+    return BDX_OK;
+}
+
+int32_t bdx_fq_count_lines_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t len, int64_t *n_newlines) {
+    if (!ctx) return BDX_E_INVALID;
+    if (!n_newlines) return bdx_fail(ctx, BDX_E_INVALID, "n_newlines is NULL");
+    *n_newlines = 0;
+    if (len < 0) return bdx_fail(ctx, BDX_E_INVALID, "len is negative");
+    if (len == 0) return BDX_OK;
+    if (!d_text) return bdx_fail(ctx, BDX_E_INVALID, "NULL device pointer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t nb = (len + FQ_TILE - 1) / FQ_TILE;
+    HIP_TRY(ctx, ctx->fq[FQ_BLK].ensure((size_t)(nb + 1) * 8));
+    long long *blk = (long long *)ctx->fq[FQ_BLK].p;
+    if (((uintptr_t)d_text & 15) == 0)
+        nl_count_kernel<true><<<dim3((unsigned)nb), dim3(FQ_THREADS), 0, ctx->stream>>>(d_text, len, blk);
+    else
+        nl_count_kernel<false><<<dim3((unsigned)nb), dim3(FQ_THREADS), 0, ctx->stream>>>(d_text, len, blk);
+    scan_small_kernel<<<dim3(1), dim3(FQ_THREADS), 0, ctx->stream>>>(blk, nb);
+    HIP_TRY(ctx, hipGetLastError());
+    long long total = 0;
+    HIP_TRY(ctx, read_back(ctx, blk + nb, &total, 8));
+    *n_newlines = total;
+    return BDX_OK;
+}
+
+int32_t bdx_fq_index_span_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_len, int64_t span_len, int32_t phase,
+                                 int32_t starts_line, int32_t final, int64_t max_reads, int64_t *d_line_off,
+                                 int32_t *d_line_len, int64_t *n_records, int32_t *complete) {
+    if (!ctx) return BDX_E_INVALID;
+    if (!n_records || !complete) return bdx_fail(ctx, BDX_E_INVALID, "n_records / complete is NULL");
+    *n_records = 0;
+    *complete = 1;
+    if (text_len < 0 || span_len < 0 || max_reads < 0)
+        return bdx_fail(ctx, BDX_E_INVALID, "text_len / span_len / max_reads is negative");
+    if (span_len > text_len)
+        return bdx_fail(ctx, BDX_E_INVALID, "span_len (%lld) is larger than text_len (%lld)", (long long)span_len, (long long)text_len);
+    if (phase < 0 || phase > 3) return bdx_fail(ctx, BDX_E_INVALID, "phase must be 0 .. 3 (got %d)", (int)phase);
+    if (max_reads > ((int64_t)1 << 40)) return bdx_fail(ctx, BDX_E_INVALID, "max_reads is too large");
+    if (span_len == 0) return BDX_OK;  // (no line starts in front of byte 0)
+    if (!d_text || !d_line_off || !d_line_len) return bdx_fail(ctx, BDX_E_INVALID, "NULL device pointer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t nb = (text_len + FQ_TILE - 1) / FQ_TILE;
+    HIP_TRY(ctx, ctx->fq[FQ_BLK].ensure((size_t)(nb + 1) * 8));
+    HIP_TRY(ctx, ctx->fq[FQ_PART].ensure((size_t)(nb + 1) * 8));
+    long long *blk = (long long *)ctx->fq[FQ_BLK].p;
+    long long *blk_lim = (long long *)ctx->fq[FQ_PART].p;
+    const bool aligned = ((uintptr_t)d_text & 15) == 0;
+    // a line that starts in the span at byte s > 0 follows a newline in front of byte span_len - 1
+    if (aligned)
+        span_count_kernel<true><<<dim3((unsigned)nb), dim3(FQ_THREADS), 0, ctx->stream>>>(d_text, text_len, span_len - 1, blk, blk_lim);
+    else
+        span_count_kernel<false><<<dim3((unsigned)nb), dim3(FQ_THREADS), 0, ctx->stream>>>(d_text, text_len, span_len - 1, blk, blk_lim);
+    scan_small_kernel<<<dim3(1), dim3(FQ_THREADS), 0, ctx->stream>>>(blk, nb);
+    scan_small_kernel<<<dim3(1), dim3(FQ_THREADS), 0, ctx->stream>>>(blk_lim, nb);
+    HIP_TRY(ctx, hipGetLastError());
+    long long total = 0, in_span = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&in_span, blk_lim + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, read_back(ctx, blk + nb, &total, 8));
+    // window line i (i newlines in front of it) has the global number phase + i; lines 0 .. in_span start in the span,
+    // line 0 only with starts_line
+    int64_t first = (4 - phase) % 4;
+    if (first == 0 && !starts_line) first = 4;
+    if (first > in_span) return BDX_OK;
+    const int64_t nrec = (in_span - first) / 4 + 1;
+    *n_records = nrec;
+    if (nrec > max_reads)
+        return bdx_fail(ctx, BDX_E_SPACE, "%lld records start in the span, the line table holds %lld", (long long)nrec, (long long)max_reads);
+    const int64_t nlines = 4 * nrec;
+    if (first + nlines > total && !final) {  // the last record's fourth line ends behind the window
+        *complete = 0;
+        return BDX_OK;
+    }
+    const int64_t cap = std::min<int64_t>(total, first + nlines);
+    HIP_TRY(ctx, ctx->fq[FQ_NL].ensure((size_t)std::max<int64_t>(cap, 1) * 8));
+    long long *nl = (long long *)ctx->fq[FQ_NL].p;
+    HIP_TRY(ctx, poison(ctx, nl, (size_t)cap * 8));
+    HIP_TRY(ctx, poison(ctx, d_line_off, (size_t)nlines * 8));
+    HIP_TRY(ctx, poison(ctx, d_line_len, (size_t)nlines * 4));
+    if (cap > 0) {
+        if (aligned)
+            nl_scatter_kernel<true><<<dim3((unsigned)nb), dim3(FQ_THREADS), 0, ctx->stream>>>(d_text, text_len, blk, nl, cap);
+        else
+            nl_scatter_kernel<false><<<dim3((unsigned)nb), dim3(FQ_THREADS), 0, ctx->stream>>>(d_text, text_len, blk, nl, cap);
+    }
+    span_lines_kernel<<<dim3(grid_for(nlines, FQ_THREADS)), dim3(FQ_THREADS), 0, ctx->stream>>>(d_text, text_len, nl, total, first,
+                                                                                                nlines, d_line_off, d_line_len);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return BDX_OK;
 }
 

@@ -38,6 +38,12 @@ whatever the file's size.  A window that holds no complete block is offered agai
 A member's CRC-32 and ISIZE are known at its end only: a refused member raises BdxError after the batches of the
 windows before it were written, as with the host inflate; "refused before the first batch" holds for the resident
 mode alone.
+
+``execute_demultiplexing(..., _io="device-deal", devices=[...])`` is demux_device_dealt, at the end of this file: the same
+device steps on several contexts.  The reference frames records by line count alone, so the text is cut into byte spans,
+(newlines in front of a span) mod 4 tells which of its lines begin a record, and the spans' counts chain with one
+addition each (_SpanChain); nothing waits for the index of the span before.  Single-end input, plain or inflated by the
+host.
 """
 from __future__ import annotations
 
@@ -781,3 +787,380 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
         timings.update(busy)
     if errors:
         raise errors[0]
+
+
+# ---- the device pipeline dealt over several contexts by byte spans (_io="device-deal") ----------------------------------
+SPAN_MIN = 16
+_SPAN_TAIL = 1 << 16  # the first tail behind a span; doubled while a record that starts in the span ends behind it
+_AVG_RECORD = 330     # _Input.avg_record's start value
+
+
+def default_span_bytes(batch_reads: int) -> int:
+    """the span of a run that names none: what ``batch_reads`` records of 330 bytes take, rounded up to 64 KiB.  It never
+    depends on the number of contexts: an input and a span size give the same spans, whatever they are dealt over."""
+    return -(-(max(1, int(batch_reads)) * _AVG_RECORD) // 65536) * 65536
+
+
+def span_bytes(v) -> int:
+    """_span_bytes as execute_demultiplexing takes it: an int of at least 16 (ValueError otherwise)"""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < SPAN_MIN:
+        raise ValueError(f"_span_bytes must be an int of at least {SPAN_MIN} bytes, got {v!r}")
+    return int(v)
+
+
+class _ChainFailed(Exception):
+    """raised in a thread that waits on a _SpanChain another thread has failed (never the run's first error)"""
+
+
+class _SpanChain:
+    """What the threads of demux_device_dealt share, and nothing of HIP: the span counter, the phase chain and the
+    reorder step in front of the writer.
+
+    Span k is the input's bytes [kS, (k + 1)S).  Its phase is (newlines in front of it) mod 4: phase(0) = 0,
+    phase(k + 1) = phase(k) + count(k).  A worker take()s a span, publish()es its newline count as soon as it has it,
+    wait_phase()s for its own phase and hand_over()s the span's blocks (None for a span without a record start); the
+    writer takes them with next_in_order(), in span order.  end_at(k): span k starts at or behind the input's end.
+
+    No deadlock.  A worker blocks in two places only: in wait_phase, and on one of its own download slots (which the
+    writer hands back once the span that holds it is written).  It publishes its span's count BEFORE either.  Let m be
+    the lowest span that is not written.  Spans are taken in ascending order, so if nobody holds m nobody holds a
+    later span either and every worker is free to take it.  Otherwise its worker waits for nothing later than m:
+    phase(m) needs the counts of the spans below m, which are written and therefore published; the slots of that
+    worker are held by spans it took before m, which are written, so the writer has handed them back.  Span m reaches
+    the writer, and m grows.  Workers with later spans may wait on count(m), which m's worker publishes before it can
+    block.  The reorder map holds at most the spans that hold a slot (two a context) and the empty ones between them.
+
+    fail(exc) records the first error and wakes every waiter: take and wait_phase raise _ChainFailed, next_in_order
+    returns None."""
+
+    def __init__(self):
+        self.cv = threading.Condition()
+        self.errors: list = []
+        self._next = 0
+        self._end = None      # the input's spans, once a worker has met its end
+        self._phase = [0]     # _phase[k], as far as the published counts chain
+        self._counts = {}     # counts published ahead of a lower span's
+        self._done = {}       # handed over, not yet the writer's turn
+        self._written = 0
+
+    def take(self):
+        """-> the next span's number; None when the input is known to end in front of it"""
+        with self.cv:
+            if self.errors:
+                raise _ChainFailed()
+            if self._end is not None and self._next >= self._end:
+                return None
+            self._next += 1
+            return self._next - 1
+
+    def end_at(self, k: int) -> None:
+        with self.cv:
+            self._end = k if self._end is None else min(self._end, k)
+            self.cv.notify_all()
+
+    def publish(self, k: int, count: int) -> None:
+        with self.cv:
+            self._counts[k] = int(count)
+            while len(self._phase) - 1 in self._counts:
+                j = len(self._phase) - 1
+                self._phase.append((self._phase[j] + self._counts.pop(j)) % 4)
+            self.cv.notify_all()
+
+    def wait_phase(self, k: int) -> int:
+        with self.cv:
+            while len(self._phase) <= k and not self.errors:
+                self.cv.wait()
+            if self.errors:
+                raise _ChainFailed()
+            return self._phase[k]
+
+    def hand_over(self, k: int, item) -> None:
+        with self.cv:
+            self._done[k] = item
+            self.cv.notify_all()
+
+    def next_in_order(self):
+        """-> (k, item) of the lowest span not yet written; None when every span is through, or after fail()"""
+        with self.cv:
+            while True:
+                if self.errors:
+                    return None
+                if self._written in self._done:
+                    self._written += 1
+                    return self._written - 1, self._done.pop(self._written - 1)
+                if self._end is not None and self._written >= self._end:
+                    return None
+                self.cv.wait()
+
+    def ended(self) -> bool:
+        """a worker has met the input's end"""
+        with self.cv:
+            return self._end is not None
+
+    def fail(self, exc: BaseException) -> None:
+        with self.cv:
+            if not isinstance(exc, _ChainFailed) or not self.errors:
+                self.errors.append(exc)
+            self.cv.notify_all()
+
+
+class _DealWorker:
+    """One context of demux_device_dealt: its streams, device buffers and two pinned download slots, and the thread that
+    takes spans from the chain until the input ends."""
+
+    def __init__(self, k: int, run: "_DealRun", classifier):
+        self.k, self.run, self.cl = k, run, classifier
+        self.rt = run.rt
+        self.busy = {"upload_s": 0.0, "device_s": 0.0, "phase_wait_s": 0.0, "batches": 0}
+        if run.dev_gz:
+            self.busy.update(deflate_s=0.0, plain_bytes=0, compressed_bytes=0, gzip_level=run.gzip_level)
+        self.spans = 0
+        self.s_main = self.s_copy = 0
+        self.slots = None
+        self.bufs = {}
+        self.max_reads = 0
+        self.thread = threading.Thread(target=self.loop, name=f"bdx-deal-{k}")
+
+    def buf(self, name: str) -> _DevBuf:
+        if name not in self.bufs:
+            self.bufs[name] = _DevBuf(self.rt)
+        return self.bufs[name]
+
+    def open(self):
+        rt = self.rt
+        rt.check(rt.hipSetDevice(int(getattr(self.cl, "device", 0))), "hipSetDevice")
+        self.s_main, self.s_copy = rt.stream(), rt.stream()
+        self.cl.set_stream(self.s_main)
+        self.slots = _Slots(rt)
+
+    def tables(self, max_reads: int):
+        self.max_reads = max_reads
+        self.buf("off").ensure(4 * max_reads * 8)
+        self.buf("len").ensure(4 * max_reads * 4)
+
+    def upload(self, start: int, want: int):
+        """bytes [start, start + want) of the input (what is there of them) -> (bytes, final); None behind its end"""
+        run, rt, L = self.run, self.rt, self.run.L
+        t0 = time.perf_counter()
+        avail, fin = C.c_int64(0), C.c_int32(0)
+        if L.bdx_fq_wait(run.f.h, start + want, C.byref(avail), C.byref(fin)) != 0:
+            raise OSError(L.bdx_io_last_error().decode())
+        if avail.value <= start:
+            return None
+        end = min(avail.value, start + want)
+        nbytes = end - start
+        dst = self.buf("text").ensure(nbytes + 64)
+        rt.check(rt.hipMemcpyAsync(dst, L.bdx_fq_data(run.f.h) + start, nbytes, _H2D, self.s_copy), "hipMemcpyAsync (upload)")
+        rt.check(rt.hipStreamSynchronize(self.s_copy), "hipStreamSynchronize (upload)")
+        self.busy["upload_s"] += time.perf_counter() - t0
+        return nbytes, bool(fin.value) and end >= avail.value
+
+    def span(self, k: int) -> bool:
+        """span k through this context -> False when the input ends in front of it"""
+        run, chain, cl, lib = self.run, self.run.chain, self.cl, self.cl.lib
+        S, layout = run.S, run.layout
+        start, tail = k * S, _SPAN_TAIL
+        up = self.upload(start, S + tail)
+        if up is None:
+            chain.end_at(k)
+            return False
+        self.spans += 1
+        nbytes, final = up
+        span_len = min(S, nbytes)
+        starts_line = 1 if start == 0 else int(C.c_ubyte.from_address(run.L.bdx_fq_data(run.f.h) + start - 1).value == 10)
+        t0 = time.perf_counter()
+        d_text = self.buf("text").p
+        count = C.c_int64(0)
+        cl._check(lib.bdx_fq_count_lines_device(cl.h, d_text, span_len, C.byref(count)))
+        chain.publish(k, count.value)  # at once: the spans behind this one wait for nothing else of it
+        t1 = time.perf_counter()
+        phase = chain.wait_phase(k)
+        t2 = time.perf_counter()
+        self.busy["phase_wait_s"] += t2 - t1
+        waited = t2 - t1
+        n, complete = C.c_int64(0), C.c_int32(1)
+        while True:
+            rc = lib.bdx_fq_index_span_device(cl.h, d_text, nbytes, span_len, phase, starts_line, int(final), self.max_reads,
+                                              self.buf("off").p, self.buf("len").p, C.byref(n), C.byref(complete))
+            if rc == _E_SPACE:  # more records than the tables hold: the call has said how many
+                self.tables(int(n.value) + (int(n.value) >> 3))
+                continue
+            cl._check(rc)
+            if complete.value:
+                break
+            tail *= 2  # a record that starts in the span ends behind the window: a longer tail
+            t_up = time.perf_counter()
+            nbytes, final = self.upload(start, S + tail)
+            waited += time.perf_counter() - t_up
+            d_text = self.buf("text").p
+        n = int(n.value)
+        if n == 0:  # a line longer than the span, or no line of it begins a record: the writer passes it
+            self.busy["device_s"] += time.perf_counter() - t0 - waited
+            chain.hand_over(k, None)
+            return True
+        d_off, d_len, d_seq, d_seq_off, d_out = (self.buf(b) for b in ("off", "len", "seq", "seq_off", "out"))
+        d_v = {b: self.buf(b) for b in ("bc1", "bc2", "keep_start", "keep_end")}
+        d_seq.ensure(nbytes + 64)
+        d_seq_off.ensure((n + 1) * 8)
+        for b in d_v.values():
+            b.ensure(n * 4)
+        cl._check(lib.bdx_fq_pack_device(cl.h, d_text, nbytes, d_off.p, d_len.p, n, d_seq.p, d_seq.cap, d_seq_off.p, None))
+        cl.classify_device(d_seq.p, d_seq_off.p, n, **{b: v.p for b, v in d_v.items()})
+        d_out.ensure(sum(nbytes + 64 for _ in layout.streams))
+        blocks, pos = [], 0
+        for _, prefix, trim in layout.streams:
+            cb = np.zeros(layout.n_classes, dtype=np.int64)
+            cl._check(lib.bdx_fq_gather_device(cl.h, d_text, nbytes, d_off.p, d_len.p, n, d_v["bc1"].p, d_v["bc2"].p, layout.stride,
+                                               layout.n_classes, d_v["keep_start"].p, d_v["keep_end"].p, int(bool(trim)),
+                                               d_out.p + pos, d_out.cap - pos, cb.ctypes.data))
+            blocks.append((pos, cb, prefix))
+            pos += int(cb.sum())
+        d_src = d_out
+        if run.dev_gz:
+            blocks, pos = _deflate(cl, d_out, self.buf("gz"), blocks, layout.n_classes, self.busy)
+            d_src = self.buf("gz")
+        self.busy["device_s"] += time.perf_counter() - t0 - waited
+        self.busy["batches"] += 1
+        hs = _download(self.rt, self.s_main, self.slots, chain.errors, d_src, pos)
+        if hs is None:
+            raise _ChainFailed()
+        chain.hand_over(k, (self.slots, hs, blocks))
+        return True
+
+    def loop(self):
+        chain = self.run.chain
+        try:
+            self.rt.check(self.rt.hipSetDevice(int(getattr(self.cl, "device", 0))), "hipSetDevice")
+            self.tables(self.run.S // 128 + 64)
+            while True:
+                k = chain.take()
+                if k is None or not self.span(k):
+                    break
+        except BaseException as e:  # noqa: BLE001 - the first one reaches the caller
+            chain.fail(e)
+
+    def close(self):
+        rt = self.rt
+        rt.hipSetDevice(int(getattr(self.cl, "device", 0)))
+        if self.s_main:
+            rt.hipStreamSynchronize(self.s_main)
+            self.cl.set_stream(None)
+        for b in self.bufs.values():
+            b.free()
+        for e in (self.slots.events if self.slots is not None else ()):
+            rt.hipEventDestroy(e)
+        for s in (self.s_main, self.s_copy):
+            if s:
+                rt.hipStreamDestroy(s)
+
+
+class _DealRun:
+    """what the workers and the writer of one demux_device_dealt call share"""
+
+    def __init__(self, rt, L, f, layout, S: int, dev_gz: bool, gzip_level: int):
+        self.rt, self.L, self.f, self.layout, self.S = rt, L, f, layout, S
+        self.dev_gz, self.gzip_level = dev_gz, gzip_level
+        self.chain = _SpanChain()
+
+
+def _write_dealt(run: _DealRun, T: int, busy: dict):
+    """The writer thread: takes the spans in span order, waits for each one's download and appends one block per file;
+    hands the pinned slot back to the span's context."""
+    chain, rt, L, layout = run.chain, run.rt, run.L, run.layout
+    try:
+        for k, item in iter(chain.next_in_order, None):
+            busy["spans"] += 1
+            # every span up to k is uploaded; the span behind k still reads the byte in front of it
+            run.f.release(max(0, (k + 1) * run.S - 1))
+            if item is None:
+                continue
+            slots, slot, blocks = item
+            try:
+                t0 = time.perf_counter()
+                rt.check(rt.hipEventSynchronize(slots.events[slot]), "hipEventSynchronize (download)")
+                t1 = time.perf_counter()
+                base = slots.hbuf[slot].ctypes.data
+                for off, cb, prefix in blocks:
+                    paths = layout.c_paths(prefix, np.flatnonzero(cb))
+                    if run.dev_gz:
+                        rc = L.bdx_fq_write_blocks_raw(base + off, cb.ctypes.data, layout.n_classes, paths, T)
+                    else:
+                        rc = L.bdx_fq_write_blocks(base + off, cb.ctypes.data, layout.n_classes, paths, layout.gz, T)
+                    if rc != 0:
+                        raise OSError(L.bdx_io_last_error().decode())
+                busy["download_s"] += t1 - t0
+                busy["write_s"] += time.perf_counter() - t1
+            finally:
+                slots.free.put(slot)
+    except BaseException as e:  # noqa: BLE001
+        chain.fail(e)
+
+
+def demux_device_dealt(fastq1: str, config, output_directory: str, prefix1: str, classifiers: list, batch_reads: int,
+                       timings: Optional[dict] = None, gzip_device: bool = False, gzip_level: int = 1,
+                       span_bytes: Optional[int] = None) -> None:
+    """The device pipeline of demux_device for ONE single-end input (plain, or a .gz the host inflates), dealt over the
+    contexts ``classifiers`` by byte spans.  The text is cut into spans of ``span_bytes`` bytes (default:
+    default_span_bytes(batch_reads)); a record belongs to the span its first line starts in (bdx_fq_index_span_device
+    has the rule).  One worker thread per context takes the next span, uploads it with a tail, counts its newlines
+    (bdx_fq_count_lines_device) and publishes the count, waits for its phase, then indexes, packs, classifies, gathers,
+    deflates with ``gzip_device`` and gzip output, and starts the download; one writer thread appends the blocks in
+    span order (_SpanChain).  Files, counters and reports are those of demux_device; the gzip members of
+    ``gzip_device`` depend on the input and the span size alone, not on the contexts.  Device memory of a context:
+    the span with its tail three times (text, packed reads, blocks; the members as well with ``gzip_device``), 48 bytes
+    a record of line table and 16 of results, and the context's own scratch."""
+    if not classifiers or not all(hasattr(c, "classify_device") for c in classifiers):
+        raise ValueError("the device FASTQ pipeline (_io='device-deal') needs the HIP classifier")
+    t_wall = time.perf_counter()
+    L = _io()
+    rt = _Runtime(classifiers[0].lib)
+    T = nativeio._threads()
+    S = int(span_bytes) if span_bytes is not None else default_span_bytes(batch_reads)
+    layout = OutputLayout(config, output_directory, prefix1, "", False)
+    dev_gz = bool(gzip_device) and bool(layout.gz)
+    wbusy = {"download_s": 0.0, "write_s": 0.0, "spans": 0}
+    f = nativeio.FastqFile(fastq1)
+    run = _DealRun(rt, L, f, layout, S, dev_gz, int(gzip_level))
+    chain = run.chain
+    workers = [_DealWorker(k, run, c) for k, c in enumerate(classifiers)]
+    started = []
+    writer = None
+    try:
+        for w in workers:
+            w.open()
+        writer = threading.Thread(target=_write_dealt, name="bdx-deal-writer", args=(run, T, wbusy))
+        writer.start()
+        for w in workers:
+            w.thread.start()
+            started.append(w)
+        for w in started:
+            w.thread.join()
+        if not chain.errors and not chain.ended():  # (every worker left without meeting the end: cannot happen)
+            chain.fail(BdxError("the span workers ended in front of the input's end"))
+    except BaseException as e:  # noqa: BLE001
+        chain.fail(e)
+    finally:
+        for w in started:
+            w.thread.join()
+        if writer is not None:
+            if not started:
+                chain.end_at(0)
+            writer.join()
+        for w in workers:
+            try:
+                w.close()
+            except BaseException as e:  # noqa: BLE001
+                chain.fail(e)
+        f.close()
+    if timings is not None:
+        busy = dict(wbusy)
+        for w in workers:
+            for name, v in w.busy.items():
+                busy[name] = v if name == "gzip_level" else busy.get(name, 0) + v
+        busy["spans_per_device"] = [w.spans for w in workers]
+        busy["span_bytes"] = S
+        busy["wall_s"] = time.perf_counter() - t_wall
+        busy["threads"] = T
+        timings.update(busy)
+    if chain.errors:
+        raise chain.errors[0]

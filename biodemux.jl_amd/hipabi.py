@@ -38,6 +38,8 @@ ABI_SYMBOLS = [
     "bdx_debug_rejected_windows_total", "bdx_last_launches",
     # device FASTQ pipeline (bdx_fastq.hip)
     "bdx_fq_index_device", "bdx_fq_pack_device", "bdx_fq_gather_device",
+    # ... its index by byte spans (_io="device-deal")
+    "bdx_fq_count_lines_device", "bdx_fq_index_span_device",
     # device DEFLATE of the pipeline's gzip output (bdx_deflate.hip)
     "bdx_fq_deflate_chunk", "bdx_fq_deflate_bound", "bdx_fq_deflate_device", "bdx_fq_deflate_levels", "bdx_fq_deflate_level_device",
     # device inflate of the pipeline's .gz input (bdx_inflate.hip)
@@ -246,6 +248,11 @@ def load_library(path: Optional[str] = None):
     L.bdx_fq_index_device.restype = C.c_int32
     L.bdx_fq_index_device.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, vp, vp, C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int64)]
+    L.bdx_fq_count_lines_device.restype = C.c_int32
+    L.bdx_fq_count_lines_device.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.bdx_fq_index_span_device.restype = C.c_int32
+    L.bdx_fq_index_span_device.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, vp,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     L.bdx_fq_pack_device.restype = C.c_int32
     L.bdx_fq_pack_device.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
     L.bdx_fq_gather_device.restype = C.c_int32

@@ -292,6 +292,40 @@ void bdx_host_free(void *p);
 int32_t bdx_fq_index_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_len, int32_t final, int64_t max_reads,
                             int64_t *d_line_off, int32_t *d_line_len, int64_t *n_records, int64_t *next);
 
+/* The index by byte spans: a text cut at ANY byte offsets is indexed span by span, in any order and on any contexts.
+ * The reference frames records by line count alone (four readline calls a record, core.jl:65-75, :96-101), so the
+ * record a line belongs to follows from the number of newlines in front of it, modulo 4; newline counts of disjoint
+ * byte ranges are independent and chain with one addition per range.  Both entries run on the context's stream and
+ * device and synchronise it before they return.
+ *
+ * bdx_fq_count_lines_device: *n_newlines = the number of '\n' bytes in d_text[0, len).  Any pointer alignment.
+ *
+ * bdx_fq_index_span_device: d_text[0, text_len) holds the file's bytes from the span's first byte on: the span
+ * (span_len <= text_len bytes) and a tail behind it.  phase = (newlines in the file in front of the span) mod 4.
+ * starts_line != 0: the span's byte 0 begins a line (it is the file's first byte, or the byte in front of it is
+ * '\n').  final != 0: d_text reaches the end of the file.
+ *   A line that starts inside the window has the global number phase + (newlines in front of its first byte),
+ * whether or not starts_line is set; starts_line only says whether offset 0 is itself a line start — if it is not,
+ * the bytes in front of the window's first newline belong to a line of an earlier span and are no line start here.
+ * A line begins a record when its global number is 0 mod 4.  The output is the line table (4 lines a record,
+ * offsets relative to d_text, lengths without "\n" and without a "\r" in front of it: 4 * max_reads entries of room)
+ * of exactly the records whose first line starts at an offset < span_len; their lines are taken as far into the
+ * tail as they reach.  *n_records: those records.
+ *   *complete = 0, with BDX_OK, when final == 0 and the last such record's fourth line is not terminated inside
+ * text_len: the caller offers a longer tail and calls again (the line table is unspecified then).  With final != 0
+ * the rules of bdx_fq_index_device hold for the last record: an unterminated last line counts, a truncated record is
+ * padded with (off = text_len, len = 0) lines.  When more than max_reads records start in the span the call returns
+ * BDX_E_SPACE with the needed count in *n_records.  BDX_E_INVALID: a negative length, span_len > text_len, phase
+ * outside 0 .. 3, a NULL pointer.
+ *   The partition property: over any text and any span size S >= 1, with span k = bytes [kS, (k + 1)S), the tail
+ * long enough (or the rest of the text with final = 1), phase and starts_line as defined above, the spans' tables,
+ * shifted by kS and concatenated in span order, are the line table bdx_fq_index_device gives for the whole text with
+ * final = 1 — every record once, none lost. */
+int32_t bdx_fq_count_lines_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t len, int64_t *n_newlines);
+int32_t bdx_fq_index_span_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_len, int64_t span_len, int32_t phase,
+                                 int32_t starts_line, int32_t final, int64_t max_reads, int64_t *d_line_off,
+                                 int32_t *d_line_len, int64_t *n_records, int32_t *complete);
+
 /* bdx_fq_pack_device: the sequence lines of records [0, n) packed as the chunk bdx_classify_device takes:
  * d_seq_off[0] = 0, d_seq_off[i + 1] = d_seq_off[i] + length of read i (n + 1 entries).  d_seq holds seq_cap bytes
  * (the sum of the lengths is at most text_len); *seq_bytes (optional) receives that sum. */

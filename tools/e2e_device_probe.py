@@ -2,7 +2,7 @@
 """End-to-end reads/s of execute_demultiplexing on the C2 shape: the native host pipeline (_io="native") against the device
 FASTQ pipeline (_io="device"), each run in a fresh child process (GPU box).
 
-  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device} [--gzip-level 2] | --gunzip | --gunzip-stream | --gunzip-window] [out.json]
+  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device} [--gzip-level 2] | --gunzip | --gunzip-stream | --gunzip-window | --deal] [out.json]
 
 One synthetic FASTQ of N 150 bp reads x 96 barcodes (24 bp), max_error_rate=0.1, on tmpfs (/dev/shm unless E2E_ROOT is
 set); the outputs are checked (total bytes = input bytes).  Prints every run with its stage seconds, then the medians; the
@@ -28,7 +28,11 @@ repository's figures use; every leg reports min, median and max wall seconds and
 series, one run of the windowed leg per window size of 16, 64 and 256 MiB (2^28 bytes, the largest) ("sweep"); the series
 then runs the windowed leg at the sweep's fastest size (E2E_WINDOW overrides it), which is reported as "window_bytes".  The
 stream and windowed legs also report "device_peak_bytes": the largest drop of the device's free memory (hipMemGetInfo, sampled
-every 10 ms by a thread of the child; other processes on the device would show in it too) below its value at the start."""
+every 10 ms by a thread of the child; other processes on the device would show in it too) below its value at the start.
+
+--deal: plain in -> plain out; four legs alternate after one unrecorded warm-up run: "device" (_io="device", the baseline)
+and "deal1", "deal2", "deal3" (_io="device-deal" with devices=[0], [0, 0] and [0, 0, 0]: one, two and three contexts on
+GPU 0, the default span).  REPS=5 is what the repository's figures use; every leg reports min, median and max wall seconds."""
 import json
 import os
 import shutil
@@ -180,6 +184,9 @@ def child(mode: str) -> None:
     shutil.rmtree(out, ignore_errors=True)
     tm = {}
     kw = dict(gzip_output=True) if gz else {}
+    if io.startswith("deal"):  # _io="device-deal" on that many contexts of GPU 0
+        kw["devices"] = [0] * int(io[4:])
+        io = "device-deal"
     if gz in ("dgz", "dgz2"):
         kw["_gzip"] = "device"
     if gz == "dgz2":
@@ -247,6 +254,10 @@ def main() -> None:
         stream = False
         modes = ["device++hsin", "device++sin", "device++win"]
         argv = argv[1:]
+    deal = bool(argv) and argv[0] == "--deal"
+    if deal:
+        modes = ["device", "deal1", "deal2", "deal3"]
+        argv = argv[1:]
     n = int(os.environ.get("N", "10000000"))
     reps = int(os.environ.get("REPS", "3"))
     root = os.environ.get("E2E_ROOT") or "/dev/shm/bdx_e2e_device_probe"
@@ -291,7 +302,7 @@ def main() -> None:
             best = int(os.environ.get("E2E_WINDOW") or min(sweep, key=lambda x: x["seconds"])["window_mib"] << 20)
             env["E2E_WINDOW"] = str(best)
             print(f"SERIES window {best} bytes", flush=True)
-        for rep in range(-1 if gunzip or stream or window else 0, reps):  # (rep -1: the warm-up run, not recorded)
+        for rep in range(-1 if gunzip or stream or window or deal else 0, reps):  # (rep -1: the warm-up run, not recorded)
             for mode in modes[:1] if rep < 0 else modes:
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode], env=env, capture_output=True,
                                    text=True, timeout=600)
@@ -310,6 +321,8 @@ def main() -> None:
                     keys += ("deflate_s",)
                 if mode.endswith(("+din", "+sin", "+win")):
                     keys += ("inflate_s", "compressed_in_bytes", "plain_in_bytes")
+                if mode.startswith("deal"):
+                    keys += ("phase_wait_s", "spans")
                 print(f"RUN {rep} {mode:10s} {r['seconds']:.4f} s  {r['reads_per_s'] / 1e6:6.1f} M reads/s  "
                       + "  ".join(f"{k} {st.get(k, 0):.4f}" for k in keys) + f"  batches {st.get('batches')}", flush=True)
     finally:
