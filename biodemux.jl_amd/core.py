@@ -363,9 +363,8 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
             _timings["pre_s"] = (_dt.datetime.now() - start_time).total_seconds()  # everything before the first batch can be read
         if _io == "device":
             deviceio.demux_device(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers[0], _batch_reads,
-                                  _timings, gzip_device=_gzip == "device", gunzip_device=_gunzip == "device",
-                                  gzip_level=int(_gzip_level), gunzip_stream=_gunzip == "device-stream",
-                                  gunzip_window=(_gunzip_window or deviceio.WINDOW_BYTES) if _gunzip == "device-window" else 0)
+                                  _timings, gzip_device=_gzip == "device", gzip_level=int(_gzip_level), gunzip=_gunzip,
+                                  gunzip_window=_gunzip_window or deviceio.WINDOW_BYTES)
         elif _io == "device-deal":
             deviceio.demux_device_dealt(fastq1, config, output_directory, prefix1, classifiers, _batch_reads, _timings,
                                         gzip_device=_gzip == "device", gzip_level=int(_gzip_level), span_bytes=_span_bytes)

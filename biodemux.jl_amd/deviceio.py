@@ -14,20 +14,20 @@ With ``gzip_device`` (``execute_demultiplexing(..., _gzip="device")``) and gzip 
 the batch's blocks on the device (csrc/bdx_deflate.hip, bdx_fq_deflate_level_device): only finished gzip members come back
 and the writer appends them verbatim (bdx_fq_write_blocks_raw); the files then gunzip to the same bytes.
 
-With ``gunzip_device`` (``execute_demultiplexing(..., _gunzip="device")``) a ``.gz`` input that is a chain of size-tagged
+With ``gunzip="device"`` (``_gunzip="device"``: a _Members, not a _HostText) a ``.gz`` input that is a chain of size-tagged
 gzip members (BGZF, or this library's own output) is not inflated on the host: the upload thread copies the COMPRESSED
 members that cover the batch's byte window and the calling thread inflates them on the device right before the line
 index (csrc/bdx_inflate.hip, bdx_fq_inflate_device, which checks every member's CRC-32 and ISIZE).  The cursor stays in
 plain-text coordinates; the member at a batch's end is simply inflated again by the next batch.
 
-With ``gunzip_stream`` (``execute_demultiplexing(..., _gunzip="device-stream")``) a ``.gz`` input is an ORDINARY gzip file
+With ``gunzip="device-stream"`` (``_gunzip="device-stream"``: a _ResidentText) a ``.gz`` input is an ORDINARY gzip file
 (members of any size, no tags): before the first batch the whole compressed file is uploaded and inflated by
 bdx_fq_inflate_stream_device (csrc/bdx_inflate_stream.hip: speculative block starts, every CRC-32 and ISIZE checked),
 the compressed copy is freed and the text stays RESIDENT in device memory.  A batch's window is then a pointer into it:
 nothing is uploaded per batch.  Peak device memory: the compressed bytes plus three times the plain bytes.
 
-With ``gunzip_window`` (``execute_demultiplexing(..., _gunzip="device-window")``) the same ordinary gzip file, of ANY
-size, goes through the device in WINDOWS of that many compressed bytes (bdx_fq_inflate_window_*, csrc/
+With ``gunzip="device-window"`` (``_gunzip="device-window"``: a _WindowedText) the same ordinary gzip file, of ANY
+size, goes through the device in WINDOWS of ``gunzip_window`` compressed bytes (bdx_fq_inflate_window_*, csrc/
 bdx_inflate_window_core.h): the upload thread copies the next window's compressed bytes while the calling thread works
 on the current batch; the calling thread feeds a window, on the context's stream, whenever the text behind the cursor
 is shorter than the batch wants; what a window left unconsumed (a block and a header at most, as a rule) is put in
@@ -40,10 +40,10 @@ windows before it were written, as with the host inflate; "refused before the fi
 mode alone.
 
 ``execute_demultiplexing(..., _io="device-deal", devices=[...])`` is demux_device_dealt, at the end of this file: the same
-device steps on several contexts.  The reference frames records by line count alone, so the text is cut into byte spans,
-(newlines in front of a span) mod 4 tells which of its lines begin a record, and the spans' counts chain with one
-addition each (_SpanChain); nothing waits for the index of the span before.  Single-end input, plain or inflated by the
-host.
+device steps (_Context.batch) on several contexts.  The reference frames records by line count alone, so the text is cut
+into byte spans, (newlines in front of a span) mod 4 tells which of its lines begin a record, and the spans' counts chain
+with one addition each (_SpanChain); nothing waits for the index of the span before.  Single-end input, plain or
+inflated by the host.
 """
 from __future__ import annotations
 
@@ -52,6 +52,7 @@ import os
 import queue
 import threading
 import time
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 from typing import Optional
 
@@ -201,77 +202,127 @@ def window_bytes(v) -> int:
     return int(v)
 
 
-class _Input:
-    """One FASTQ input: its host bytes (mapped, or inflated in the background; or, for the device inflate, the mapped
-    COMPRESSED members and their table) and its device side (two byte windows, the line table of the current batch).
-    ``io_lib`` is libbdx_io.so, ``classifier`` the context whose stream the inflate and the index run on, ``busy`` the
-    run's counters.  ``resident``: the stream inflate puts the whole text into device memory once (inflate_resident);
-    the windows are then places in it.  ``window`` (compressed bytes, 0: not this mode): the windowed stream inflate —
-    the file is mapped, its text appears in ``res`` a window at a time (feed) and leaves it batch by batch."""
+def _add_stream_info(busy: dict, info) -> None:
+    """the info words of one stream-inflate call onto the run's counters: sums, and the longest segment of all calls"""
+    for name, v in zip(_STREAM_INFO, info.tolist()):
+        busy[name] = max(v, busy.get(name, 0)) if name == "stream_longest_segment" else busy.get(name, 0) + v
 
-    def __init__(self, path: str, rt: _Runtime, io_lib, classifier, busy: dict, batch_reads: int, members=None,
-                 resident: bool = False, window: int = 0):
-        self.path = path
-        self.rt, self.L, self.cl, self.busy, self.batch_reads = rt, io_lib, classifier, busy, batch_reads
-        self.gz = members  # nativeio.GzMembers: this input is inflated on the device
-        self.res = _DevBuf(rt) if resident or window else None  # the resident text and its length
-        self.res_len = 0
-        self.f = nativeio.FastqFile(path) if members is None and not resident and not window else None
-        self.w = None  # the windowed mode: the window object, the mapped file, where it stands
-        if window:
-            self.open_window(int(window))
-        self.comp = [_DevBuf(rt), _DevBuf(rt)]  # compressed form: the members of the window
-        self.wmem = [(0, 0), (0, 0)]            # ... which ones: [first, last)
-        self.d_text = [0, 0]                    # where the window's text starts on the device
+
+def _upload_text(rt: _Runtime, L, f, s_copy: int, buf: _DevBuf, start: int, want: int, or_none: bool = False):
+    """Bytes [start, start + want) of the host text ``f`` (mapped, or inflated so far by the host: waits for them), what
+    is there of them -> the device buffer ``buf``.  -> (bytes, final); with ``or_none`` None, and no buffer, for no bytes"""
+    avail, fin = C.c_int64(0), C.c_int32(0)
+    if L.bdx_fq_wait(f.h, start + want, C.byref(avail), C.byref(fin)) != 0:
+        raise OSError(L.bdx_io_last_error().decode())
+    end = min(avail.value, start + want)
+    nbytes = max(0, end - start)
+    if or_none and not nbytes:
+        return None
+    dst = buf.ensure(nbytes + 64)
+    if nbytes:
+        rt.check(rt.hipMemcpyAsync(dst, L.bdx_fq_data(f.h) + start, nbytes, _H2D, s_copy), "hipMemcpyAsync (upload)")
+        rt.check(rt.hipStreamSynchronize(s_copy), "hipStreamSynchronize (upload)")
+    return nbytes, bool(fin.value) and end >= avail.value
+
+
+class _Input:
+    """One FASTQ input of demux_device: where it stands (``cursor``, in plain-text bytes), per window slot the text of a
+    batch on the device (``win``: (bytes, final), ``d_text``: where it starts) and the line tables of the current batch.
+    ``io_lib`` is libbdx_io.so, ``classifier`` the context the inflate and the index run on, ``busy`` the run's counters.
+    How text gets into a slot is the subclass's business, in these hooks:
+      prepare(s_main, s_copy)           the calling thread, once, before the first batch
+      send(s_copy, slot, want)          the upload thread (through upload(), which counts upload_s)
+      before_index(s_copy, slot, want)  the calling thread, in front of every line index
+      widen(s_copy, slot, want)         the calling thread, after an index that came back short"""
+
+    allowance = 65536  # what a window asks for beyond batch_reads average records
+    inflates = False   # the run reports inflate_s, compressed_in_bytes and plain_in_bytes
+
+    def __init__(self, path: str, rt: _Runtime, io_lib, classifier, busy: dict, batch_reads: int):
+        self.path, self.rt, self.L, self.cl, self.busy, self.batch_reads = path, rt, io_lib, classifier, busy, batch_reads
         self.cursor = 0
         self.avg_record = 330.0  # bytes per record, learned from the batches so far
-        self.text = [_DevBuf(rt), _DevBuf(rt)]
         self.win = [(0, 0), (0, 0)]  # per window slot: (bytes, final)
-        self.d_off = _DevBuf(rt)
-        self.d_len = _DevBuf(rt)
+        self.d_text = [0, 0]         # where the window's text starts on the device
+        self.d_off, self.d_len = _DevBuf(rt), _DevBuf(rt)
         self.d_off.ensure(4 * batch_reads * 8)
         self.d_len.ensure(4 * batch_reads * 4)
 
     def want_bytes(self) -> int:
-        # (the windowed mode keeps what it asks for in device memory: a small allowance; index() doubles it when it was short)
-        return int(self.batch_reads * self.avg_record * 1.05) + (4096 if self.w is not None else 65536)
+        return int(self.batch_reads * self.avg_record * 1.05) + self.allowance
 
     def upload(self, s_copy: int, slot: int, want: int):
         """bytes [cursor, cursor + want) of the input (what is there of them) -> the device window `slot`"""
         t0 = time.perf_counter()
         # (the current device belongs to the thread: the upload thread has to choose it as well)
         self.rt.check(self.rt.hipSetDevice(int(getattr(self.cl, "device", 0))), "hipSetDevice")
-        if self.w is not None:  # windowed: the next window's compressed bytes, beside the current batch's kernels
-            if self.pending is None and self.f_up < self.wsize:
-                self.fetch(s_copy, self.wbytes)
-        elif self.res is not None:  # resident: a window is a place in the text (64 bytes of slack follow its end)
-            end = min(self.res_len, self.cursor + want)
-            self.win[slot] = (max(0, end - self.cursor), end >= self.res_len)
-            self.d_text[slot] = self.res.p + self.cursor
-        elif self.gz is not None:
-            self.upload_members(s_copy, slot, want)
-        else:
-            self.upload_text(s_copy, slot, want)
+        self.send(s_copy, slot, want)
         self.busy["upload_s"] += time.perf_counter() - t0
 
-    def upload_text(self, s_copy: int, slot: int, want: int):
-        """the plain text bytes (mapped, or inflated so far by the host: waits for them) -> the device buffer text[slot]"""
-        rt, L = self.rt, self.L
-        avail, fin = C.c_int64(0), C.c_int32(0)
-        if L.bdx_fq_wait(self.f.h, self.cursor + want, C.byref(avail), C.byref(fin)) != 0:
-            raise OSError(L.bdx_io_last_error().decode())
-        end = min(avail.value, self.cursor + want)
-        nbytes = max(0, end - self.cursor)
-        final = bool(fin.value) and end >= avail.value
-        dst = self.text[slot].ensure(nbytes + 64)
-        if nbytes:
-            src = L.bdx_fq_data(self.f.h) + self.cursor
-            rt.check(rt.hipMemcpyAsync(dst, src, nbytes, _H2D, s_copy), "hipMemcpyAsync (upload)")
-            rt.check(rt.hipStreamSynchronize(s_copy), "hipStreamSynchronize (upload)")
-        self.win[slot] = (nbytes, final)
-        self.d_text[slot] = dst
+    def index(self, s_copy: int, slot: int):
+        """The line table of the batch that starts window `slot` (on the context's stream, after the inflate if there is one)
+        -> (records, bytes they take).  A window that ends before ``batch_reads`` records do is widened to twice its size."""
+        want = self.want_bytes()
+        while True:
+            self.before_index(s_copy, slot, want)
+            nbytes, final = self.win[slot]
+            n, nxt = C.c_int64(0), C.c_int64(0)
+            self.cl._check(self.cl.lib.bdx_fq_index_device(self.cl.h, self.d_text[slot], nbytes, int(final), self.batch_reads,
+                                                           self.d_off.p, self.d_len.p, C.byref(n), C.byref(nxt)))
+            if n.value >= self.batch_reads or final:
+                return n.value, nxt.value
+            want = 2 * max(want, nbytes)  # a record did not fit: a larger window
+            self.widen(s_copy, slot, want)
 
-    def upload_members(self, s_copy: int, slot: int, want: int):
+    def prepare(self, s_main: int, s_copy: int):
+        pass
+
+    def before_index(self, s_copy: int, slot: int, want: int):
+        pass
+
+    def widen(self, s_copy: int, slot: int, want: int):
+        t_up = time.perf_counter()
+        self.upload(s_copy, slot, want)
+        self.busy["device_s"] -= time.perf_counter() - t_up  # (upload_s has it; the driver counts the whole index() call)
+
+    def release(self):
+        """everything below the cursor is uploaded: the host pages can go"""
+
+    def free(self, *bufs: _DevBuf):  # the line tables and the subclass's device buffers: from its close()
+        for b in (*bufs, self.d_off, self.d_len):
+            b.free()
+
+
+class _HostText(_Input):
+    """a plain input, or a .gz the host inflates in the background: the text's bytes go up, two device buffers of them"""
+
+    def __init__(self, path: str, rt: _Runtime, io_lib, classifier, busy: dict, batch_reads: int):
+        self.f, self.text = nativeio.FastqFile(path), [_DevBuf(rt), _DevBuf(rt)]
+        super().__init__(path, rt, io_lib, classifier, busy, batch_reads)
+
+    def send(self, s_copy: int, slot: int, want: int):
+        self.win[slot] = _upload_text(self.rt, self.L, self.f, s_copy, self.text[slot], self.cursor, want)
+        self.d_text[slot] = self.text[slot].p
+
+    def release(self):
+        self.f.release(self.cursor)
+
+    def close(self):
+        self.free(*self.text)
+        self.f.close()
+
+
+class _Members(_Input):
+    """_gunzip="device": the mapped COMPRESSED members and their table; per slot those of the window and their text"""
+
+    inflates = True
+
+    def __init__(self, path: str, rt: _Runtime, io_lib, classifier, busy: dict, batch_reads: int, members):
+        self.gz, self.wmem = members, [(0, 0), (0, 0)]  # the table, and the members of a slot: [first, last)
+        self.comp, self.text = [_DevBuf(rt), _DevBuf(rt)], [_DevBuf(rt), _DevBuf(rt)]
+        super().__init__(path, rt, io_lib, classifier, busy, batch_reads)
+
+    def send(self, s_copy: int, slot: int, want: int):
         """the compressed members that cover the text bytes [cursor, cursor + want) -> the device buffer comp[slot]"""
         g, rt = self.gz, self.rt
         n, po = len(g), g.plain_off
@@ -289,10 +340,56 @@ class _Input:
         self.wmem[slot] = (m0, m1)
         self.win[slot] = (max(0, int(po[m1]) - self.cursor), m1 == n)
 
-    def inflate_resident(self, s_copy: int):
-        """The whole .gz file -> the resident text, on the context's stream (the calling thread, before the first
-        batch): the compressed bytes go up, bdx_fq_inflate_stream_device is called with a guessed capacity and once
-        more with the exact one when that was too small, the compressed copy is freed."""
+    def before_index(self, s_copy: int, slot: int, want: int):
+        """comp[slot] -> text[slot] on the context's stream; the window's text starts at the cursor, somewhere inside
+        the first member"""
+        t_i = time.perf_counter()
+        g, lib, h = self.gz, self.cl.lib, self.cl.h
+        m0, m1 = self.wmem[slot]
+        k = m1 - m0
+        total = int(g.plain_off[m1] - g.plain_off[m0])
+        d_text = self.text[slot].ensure(total + 64)
+        if k:
+            coff = np.ascontiguousarray(g.comp_off[m0:m1] - g.comp_off[m0])
+            poff = np.ascontiguousarray(g.plain_off[m0:m1] - g.plain_off[m0])
+            clen = np.ascontiguousarray(g.comp_len[m0:m1])
+            plen = np.ascontiguousarray(g.isize[m0:m1])
+            status = np.zeros(k, dtype=np.int32)
+            rc = lib.bdx_fq_inflate_device(h, self.comp[slot].p, coff.ctypes.data, clen.ctypes.data, poff.ctypes.data,
+                                           plen.ctypes.data, k, d_text, total, status.ctypes.data)
+            if rc != 0:
+                bad = np.flatnonzero(status)
+                msg = lib.bdx_last_error(h).decode()
+                if len(bad):
+                    msg = f"{self.path}: gzip member {m0 + int(bad[0])} is refused by the device inflate ({msg})"
+                raise BdxError(msg)
+            self.busy["plain_in_bytes"] += total
+        self.d_text[slot] = d_text + (self.cursor - int(g.plain_off[m0]))
+        self.busy["inflate_s"] += time.perf_counter() - t_i
+
+    def release(self):
+        if len(self.gz):
+            m = min(int(np.searchsorted(self.gz.plain_off, self.cursor, side="right")) - 1, len(self.gz) - 1)
+            self.gz.release(int(self.gz.comp_off[m]))
+
+    def close(self):
+        self.free(*self.text, *self.comp)
+        self.gz.close()
+
+
+class _ResidentText(_Input):
+    """_gunzip="device-stream": the stream inflate puts the whole text into device memory once; a window is a place in it"""
+
+    inflates = True
+
+    def __init__(self, path: str, rt: _Runtime, io_lib, classifier, busy: dict, batch_reads: int):
+        self.res, self.res_len = _DevBuf(rt), 0  # the resident text and its length
+        super().__init__(path, rt, io_lib, classifier, busy, batch_reads)
+
+    def prepare(self, s_main: int, s_copy: int):
+        """The whole .gz file -> the resident text, on the context's stream: the compressed bytes go up,
+        bdx_fq_inflate_stream_device is called with a guessed capacity and once more with the exact one when that was
+        too small, the compressed copy is freed."""
         rt, lib, h = self.rt, self.cl.lib, self.cl.h
         g = nativeio.GzMembers(self.path, int(lib.bdx_fq_inflate_member_max()))  # (maps any .gz; its table is not used)
         comp = _DevBuf(rt)
@@ -327,39 +424,65 @@ class _Input:
             self.res_len = int(plen.value)
             self.busy["compressed_in_bytes"] += size
             self.busy["plain_in_bytes"] += self.res_len
-            for name, v in zip(_STREAM_INFO, info.tolist()):
-                self.busy[name] = max(v, self.busy.get(name, 0)) if name == "stream_longest_segment" else self.busy.get(name, 0) + v
+            _add_stream_info(self.busy, info)
             self.busy["inflate_s"] += time.perf_counter() - t_i
         finally:
             comp.free()
             g.close()
 
-    # ---- the windowed stream inflate ----
-    def open_window(self, window: int):
-        lib, h = self.cl.lib, self.cl.h
+    def send(self, s_copy: int, slot: int, want: int):
+        end = min(self.res_len, self.cursor + want)  # (64 bytes of slack follow the text's end)
+        self.win[slot] = (max(0, end - self.cursor), end >= self.res_len)
+        self.d_text[slot] = self.res.p + self.cursor
+
+    def close(self):
+        self.free(self.res)
+
+
+class _WindowedText(_Input):
+    """_gunzip="device-window": the file is mapped, its text appears in ``res`` a window of ``window`` compressed bytes at
+    a time (feed) and leaves it batch by batch.  The upload thread brings the next window's compressed bytes (fetch);
+    the calling thread feeds windows in front of every index until the batch has its text."""
+
+    allowance = 4096  # (what it asks for stays in device memory: a small allowance; index() doubles it when it was short)
+    inflates = True
+
+    def __init__(self, path: str, rt: _Runtime, io_lib, classifier, busy: dict, batch_reads: int, window: int):
+        lib, h = classifier.lib, classifier.h
         chunk = int(STREAM_CHUNK) or int(lib.bdx_fq_inflate_stream_chunk())
         self.wbytes = min(WINDOW_MAX, -(-window // chunk) * chunk)  # a multiple of the chunk size
         self.lead = min(self.wbytes, _WINDOW_LEAD)
-        self.wmap = nativeio.GzMembers(self.path, int(lib.bdx_fq_inflate_member_max()))  # (maps any .gz; its table is not used)
+        self.wmap = nativeio.GzMembers(path, int(lib.bdx_fq_inflate_member_max()))  # (maps any .gz; its table is not used)
         self.wsize = int(self.wmap.size)
-        w = C.c_void_p()
+        self.w = C.c_void_p()  # the window object
         try:
-            self.cl._check(lib.bdx_fq_inflate_window_open(h, int(STREAM_CHUNK), C.byref(w)))
+            classifier._check(lib.bdx_fq_inflate_window_open(h, int(STREAM_CHUNK), C.byref(self.w)))
         except BaseException:
             self.wmap.close()
             raise
-        self.w = w
+        self.res = _DevBuf(rt)  # the text no batch has taken yet: res_len bytes from the plain offset t_base
+        self.res_len = self.t_base = 0
+        self.comp = [_DevBuf(rt), _DevBuf(rt)]  # two windows of compressed bytes
+        self.s_main = 0      # the context's stream (prepare)
         self.f_up = 0        # the file's bytes below it have gone up
         self.pos = 0         # where the window object stands: the sum of what it consumed
         self.released = 0    # the host pages below it were let go
         self.pending = None  # the window that went up and was not fed yet: [buffer, first byte, end, offset in the buffer]
         self.cur = None      # the window fed last, likewise: the file's bytes [pos, end) of it are the remainder
         self.ended = False   # the last window is through
-        self.t_base = 0      # the plain offset of res[0]; res_len bytes of text follow it
         self.ratio = 4.5     # plain bytes per compressed byte, learned from the windows so far
-        self.busy.setdefault("stream_windows", 0)
-        self.busy["stream_window_bytes"] = self.wbytes
-        self.busy.setdefault("stream_text_peak_bytes", 0)
+        busy.setdefault("stream_windows", 0)
+        busy["stream_window_bytes"] = self.wbytes
+        busy.setdefault("stream_text_peak_bytes", 0)
+        super().__init__(path, rt, io_lib, classifier, busy, batch_reads)
+
+    def prepare(self, s_main: int, s_copy: int):
+        self.s_main = s_main
+
+    def send(self, s_copy: int, slot: int, want: int):
+        """the next window's compressed bytes, beside the current batch's kernels"""
+        if self.pending is None and self.f_up < self.wsize:
+            self.fetch(s_copy, self.wbytes)
 
     def fetch(self, s_copy: int, n: int):
         """the file's next n bytes (what is there of them) -> the device buffer the current window is not in, behind
@@ -432,8 +555,7 @@ class _Input:
             self.ratio = max(1.0, plen.value / max(1, used.value))
         self.busy["plain_in_bytes"] += int(plen.value)
         self.busy["stream_windows"] += 1
-        for name, v in zip(_STREAM_INFO, info.tolist()):
-            self.busy[name] = max(v, self.busy.get(name, 0)) if name == "stream_longest_segment" else self.busy.get(name, 0) + v
+        _add_stream_info(self.busy, info)
         self.busy["inflate_s"] += time.perf_counter() - t_i
         return bool(used.value or plen.value or last)
 
@@ -457,8 +579,8 @@ class _Input:
             self.busy["stream_text_peak_bytes"] = max(self.busy["stream_text_peak_bytes"], new.cap)
         self.t_base, self.res_len = self.cursor, keep
 
-    def fill(self, s_copy: int, slot: int, want: int):
-        """windows until `want` bytes of text lie behind the cursor or the file has ended -> the batch's window"""
+    def before_index(self, s_copy: int, slot: int, want: int):
+        """fill: windows until `want` bytes of text lie behind the cursor or the file has ended -> the batch's window"""
         grow = 0
         while not self.ended and self.t_base + self.res_len - self.cursor < want:
             if self.feed(s_copy, grow):
@@ -473,81 +595,33 @@ class _Input:
         self.win[slot] = (nbytes, self.ended and avail <= want)
         self.d_text[slot] = self.res.p + (self.cursor - self.t_base)
 
-    def inflate(self, slot: int):
-        """comp[slot] -> text[slot] on the context's stream (the calling thread); the window's text starts at the
-        cursor, somewhere inside the first member"""
-        t_i = time.perf_counter()
-        g, lib, h = self.gz, self.cl.lib, self.cl.h
-        m0, m1 = self.wmem[slot]
-        k = m1 - m0
-        total = int(g.plain_off[m1] - g.plain_off[m0])
-        d_text = self.text[slot].ensure(total + 64)
-        if k:
-            coff = np.ascontiguousarray(g.comp_off[m0:m1] - g.comp_off[m0])
-            poff = np.ascontiguousarray(g.plain_off[m0:m1] - g.plain_off[m0])
-            clen = np.ascontiguousarray(g.comp_len[m0:m1])
-            plen = np.ascontiguousarray(g.isize[m0:m1])
-            status = np.zeros(k, dtype=np.int32)
-            rc = lib.bdx_fq_inflate_device(h, self.comp[slot].p, coff.ctypes.data, clen.ctypes.data, poff.ctypes.data,
-                                           plen.ctypes.data, k, d_text, total, status.ctypes.data)
-            if rc != 0:
-                bad = np.flatnonzero(status)
-                msg = lib.bdx_last_error(h).decode()
-                if len(bad):
-                    msg = f"{self.path}: gzip member {m0 + int(bad[0])} is refused by the device inflate ({msg})"
-                raise BdxError(msg)
-            self.busy["plain_in_bytes"] += total
-        self.d_text[slot] = d_text + (self.cursor - int(g.plain_off[m0]))
-        self.busy["inflate_s"] += time.perf_counter() - t_i
-
-    def index(self, s_copy: int, slot: int):
-        """The line table of the batch that starts window `slot` (on the context's stream, after the inflate if there is
-        one) -> (records, bytes they take).  A window that ends before ``batch_reads`` records do is uploaded again,
-        twice as large, from the calling thread."""
-        want = self.want_bytes()
-        while True:
-            if self.gz is not None:
-                self.inflate(slot)
-            if self.w is not None:  # the windowed mode feeds, it uploads nothing again
-                self.fill(s_copy, slot, want)
-            nbytes, final = self.win[slot]
-            n, nxt = C.c_int64(0), C.c_int64(0)
-            self.cl._check(self.cl.lib.bdx_fq_index_device(self.cl.h, self.d_text[slot], nbytes, int(final), self.batch_reads,
-                                                           self.d_off.p, self.d_len.p, C.byref(n), C.byref(nxt)))
-            if n.value >= self.batch_reads or final:
-                return n.value, nxt.value
-            want = 2 * max(want, nbytes)  # a record did not fit: a larger window
-            if self.w is not None:
-                continue
-            t_up = time.perf_counter()
-            self.upload(s_copy, slot, want)
-            self.busy["device_s"] -= time.perf_counter() - t_up  # (upload_s has it; the driver counts this whole call)
+    def widen(self, s_copy: int, slot: int, want: int):
+        pass  # (before_index feeds again: nothing goes up a second time)
 
     def release(self):
-        """everything below the cursor is uploaded: the host pages can go"""
-        if self.w is not None:
-            if self.pos > self.released:  # (once a window, not once a batch: dropping pages the runtime may still have pinned is not free)
-                self.wmap.release(self.pos)
-                self.released = self.pos
-            return
-        if self.res is not None:
-            return
-        if self.gz is None:
-            self.f.release(self.cursor)
-        elif len(self.gz):
-            m = min(int(np.searchsorted(self.gz.plain_off, self.cursor, side="right")) - 1, len(self.gz) - 1)
-            self.gz.release(int(self.gz.comp_off[m]))
+        if self.pos > self.released:  # (once a window, not once a batch: dropping pages the runtime may still have pinned is not free)
+            self.wmap.release(self.pos)
+            self.released = self.pos
 
     def close(self):
-        for b in (*self.text, *self.comp, self.d_off, self.d_len, *([self.res] if self.res is not None else [])):
-            b.free()
-        for f in (self.f, self.gz):
-            if f is not None:
-                f.close()
-        if self.w is not None:
-            self.cl.lib.bdx_fq_inflate_window_close(self.w)
-            self.wmap.close()
-            self.w = None
+        self.free(*self.comp, self.res)
+        self.cl.lib.bdx_fq_inflate_window_close(self.w)
+        self.wmap.close()
+
+
+def _open_input(path: str, gunzip: str, window: int, rt: _Runtime, io_lib, classifier, busy: dict, batch_reads: int) -> _Input:
+    """the _Input of ``path`` under ``gunzip`` (the values of _gunzip); a plain input is host text under every one"""
+    args = (path, rt, io_lib, classifier, busy, batch_reads)
+    if gunzip == "host" or not _is_gz(path):
+        return _HostText(*args)
+    if gunzip == "device":
+        members = open_members(path, classifier.lib)
+        try:
+            return _Members(*args, members)
+        except BaseException:
+            members.close()
+            raise
+    return _ResidentText(*args) if gunzip == "device-stream" else _WindowedText(*args, int(window))
 
 
 class _Slots:
@@ -562,147 +636,190 @@ class _Slots:
             self.free.put(s)
 
 
-def _deflate(classifier, d_out: _DevBuf, d_gz: _DevBuf, blocks, n_classes: int, busy: dict):
-    """The batch's gathered blocks in d_out (the streams' blocks are one run of n_classes * len(blocks) blocks: one
-    deflate call, at the level in busy["gzip_level"]) -> finished gzip members in d_gz; -> (their blocks, their bytes)"""
-    t_z = time.perf_counter()
-    lib = classifier.lib
-    cb_all = np.concatenate([cb for _, cb, _ in blocks])
-    d_gz.ensure(int(lib.bdx_fq_deflate_bound(cb_all.ctypes.data, len(cb_all))))
-    zb = np.zeros(len(cb_all), dtype=np.int64)
-    classifier._check(lib.bdx_fq_deflate_level_device(classifier.h, busy["gzip_level"], d_out.p, cb_all.ctypes.data, len(cb_all),
-                                                      d_gz.p, d_gz.cap, zb.ctypes.data))
-    busy["plain_bytes"] += int(cb_all.sum())
-    zblocks, pos = [], 0
-    for k, (_, _, prefix) in enumerate(blocks):
-        cz = zb[k * n_classes:(k + 1) * n_classes].copy()
-        zblocks.append((pos, cz, prefix))
-        pos += int(cz.sum())
-    busy["compressed_bytes"] += pos
-    busy["deflate_s"] += time.perf_counter() - t_z
-    return zblocks, pos
+class _Context:
+    """One device context's share of a pipeline: its two streams, the pinned download slots, the result buffers of a
+    batch, and the batch step itself.  ``busy`` takes device_s, batches and, with ``dev_gz``, the deflate's counters;
+    ``errors`` is the run's list: a download that waits for a slot gives up once it has an entry."""
+
+    def __init__(self, rt: _Runtime, classifier, busy: dict, layout: OutputLayout, dev_gz: bool, gzip_level: int, errors: list):
+        self.rt, self.cl, self.busy, self.layout, self.dev_gz, self.errors = rt, classifier, busy, layout, dev_gz, errors
+        if dev_gz:
+            busy.update(deflate_s=0.0, plain_bytes=0, compressed_bytes=0, gzip_level=int(gzip_level))
+        self.s_main, self.s_copy, self.slots = 0, 0, None
+        self.seq, self.seq_off, self.out, self.gz = (_DevBuf(rt) for _ in range(4))
+        self.v = {k: _DevBuf(rt) for k in ("bc1", "bc2", "keep_start", "keep_end")}
+
+    def open(self):
+        rt = self.rt
+        rt.check(rt.hipSetDevice(int(getattr(self.cl, "device", 0))), "hipSetDevice")
+        self.s_main, self.s_copy = rt.stream(), rt.stream()
+        self.cl.set_stream(self.s_main)
+        self.slots = _Slots(rt)
+
+    def size_results(self, n: int):
+        """room for the results of n records (each pipeline sizes them its own way: once a run, or once a span)"""
+        self.seq_off.ensure((n + 1) * 8)
+        for b in self.v.values():
+            b.ensure(n * 4)
+
+    def batch(self, texts, n: int, t0: float):
+        """The n records of a batch: pack (the first input's reads) -> ONE classify call -> a gather per output stream ->
+        with ``dev_gz`` the deflate (only finished gzip members come back) -> the start of the download.  ``texts``: per input
+        its window and line tables, (d_text, bytes, d_off, d_len); ``t0``: where the batch's device_s began.  -> (slot, blocks)"""
+        cl, lib, layout, v = self.cl, self.cl.lib, self.layout, self.v
+        d_text, nbytes, d_off, d_len = texts[0]
+        self.seq.ensure(nbytes + 64)
+        cl._check(lib.bdx_fq_pack_device(cl.h, d_text, nbytes, d_off, d_len, n, self.seq.p, self.seq.cap, self.seq_off.p, None))
+        cl.classify_device(self.seq.p, self.seq_off.p, n, **{k: b.p for k, b in v.items()})
+        self.out.ensure(sum(texts[i][1] + 64 for i, _, _ in layout.streams))
+        blocks, pos = [], 0
+        for i, prefix, trim in layout.streams:
+            d_text, nbytes, d_off, d_len = texts[i]
+            cb = np.zeros(layout.n_classes, dtype=np.int64)
+            cl._check(lib.bdx_fq_gather_device(cl.h, d_text, nbytes, d_off, d_len, n, v["bc1"].p, v["bc2"].p, layout.stride,
+                                               layout.n_classes, v["keep_start"].p, v["keep_end"].p, int(bool(trim)),
+                                               self.out.p + pos, self.out.cap - pos, cb.ctypes.data))
+            blocks.append((pos, cb, prefix))
+            pos += int(cb.sum())
+        d_src = self.out
+        if self.dev_gz:
+            blocks, pos = self.deflate(blocks)
+            d_src = self.gz
+        self.busy["device_s"] += time.perf_counter() - t0
+        self.busy["batches"] += 1
+        return self.download(d_src, pos), blocks
+
+    def deflate(self, blocks):
+        """The batch's gathered blocks in ``out`` (the streams' blocks are one run of n_classes * len(blocks) blocks: one
+        deflate call, at the level in busy["gzip_level"]) -> finished gzip members in ``gz``; -> (their blocks, their bytes)"""
+        t_z = time.perf_counter()
+        cl, lib, busy, n_classes = self.cl, self.cl.lib, self.busy, self.layout.n_classes
+        cb_all = np.concatenate([cb for _, cb, _ in blocks])
+        self.gz.ensure(int(lib.bdx_fq_deflate_bound(cb_all.ctypes.data, len(cb_all))))
+        zb = np.zeros(len(cb_all), dtype=np.int64)
+        cl._check(lib.bdx_fq_deflate_level_device(cl.h, busy["gzip_level"], self.out.p, cb_all.ctypes.data, len(cb_all), self.gz.p,
+                                                  self.gz.cap, zb.ctypes.data))
+        busy["plain_bytes"] += int(cb_all.sum())
+        zblocks, pos = [], 0
+        for k, (_, _, prefix) in enumerate(blocks):
+            cz = zb[k * n_classes:(k + 1) * n_classes].copy()
+            zblocks.append((pos, cz, prefix))
+            pos += int(cz.sum())
+        busy["compressed_bytes"] += pos
+        busy["deflate_s"] += time.perf_counter() - t_z
+        return zblocks, pos
+
+    def download(self, d_src: _DevBuf, nbytes: int):
+        """Starts the copy of the batch's `nbytes` into a free host slot (the writer hands them back) and records the
+        slot's event behind it: the writer waits for the copy.  -> the slot, or None when the run has failed meanwhile"""
+        rt, slots = self.rt, self.slots
+        while True:
+            try:
+                hs = slots.free.get(timeout=0.05)
+                break
+            except queue.Empty:
+                if self.errors:
+                    return None
+        if self.errors:
+            return None
+        if slots.hbuf[hs] is None or len(slots.hbuf[hs]) < nbytes:
+            slots.hbuf[hs] = pinned_empty(max(nbytes, 1) + (max(nbytes, 1) >> 3), np.uint8)
+        if nbytes:
+            rt.check(rt.hipMemcpyAsync(slots.hbuf[hs].ctypes.data, d_src.p, nbytes, _D2H, self.s_main), "hipMemcpyAsync (download)")
+        rt.check(rt.hipEventRecord(slots.events[hs], self.s_main), "hipEventRecord")
+        return hs
+
+    def close(self):
+        rt = self.rt
+        rt.hipSetDevice(int(getattr(self.cl, "device", 0)))
+        if self.s_main:
+            rt.hipStreamSynchronize(self.s_main)
+            self.cl.set_stream(None)
+        for b in (self.seq, self.seq_off, self.out, self.gz, *self.v.values()):
+            b.free()
+        for e in (self.slots.events if self.slots is not None else ()):
+            rt.hipEventDestroy(e)
+        for s in filter(None, (self.s_main, self.s_copy)):
+            rt.hipStreamDestroy(s)
 
 
-def _download(rt: _Runtime, s_main: int, slots: _Slots, errors: list, d_src: _DevBuf, nbytes: int):
-    """Starts the copy of the batch's `nbytes` into a free host slot (the writer hands them back) and records the
-    slot's event behind it: the writer waits for the copy.  -> the slot, or None when the run has failed meanwhile"""
-    while True:
-        try:
-            hs = slots.free.get(timeout=0.05)
-            break
-        except queue.Empty:
-            if errors:
-                return None
-    if errors:
-        return None
-    if slots.hbuf[hs] is None or len(slots.hbuf[hs]) < nbytes:
-        slots.hbuf[hs] = pinned_empty(max(nbytes, 1) + (max(nbytes, 1) >> 3), np.uint8)
-    if nbytes:
-        rt.check(rt.hipMemcpyAsync(slots.hbuf[hs].ctypes.data, d_src.p, nbytes, _D2H, s_main), "hipMemcpyAsync (download)")
-    rt.check(rt.hipEventRecord(slots.events[hs], s_main), "hipEventRecord")
-    return hs
+def _write_blocks(rt: _Runtime, L, layout: OutputLayout, raw: bool, T: int, busy: dict, slots: _Slots, slot: int, blocks):
+    """What a writer thread does with one batch: waits for its download into ``slots.hbuf[slot]``, appends one block per
+    file and stream, and hands the slot back.  ``raw``: the blocks are finished gzip members, appended as they are."""
+    try:
+        t0 = time.perf_counter()
+        rt.check(rt.hipEventSynchronize(slots.events[slot]), "hipEventSynchronize (download)")
+        t1 = time.perf_counter()
+        base = slots.hbuf[slot].ctypes.data
+        for off, cb, prefix in blocks:
+            paths = layout.c_paths(prefix, np.flatnonzero(cb))
+            if raw:
+                rc = L.bdx_fq_write_blocks_raw(base + off, cb.ctypes.data, layout.n_classes, paths, T)
+            else:
+                rc = L.bdx_fq_write_blocks(base + off, cb.ctypes.data, layout.n_classes, paths, layout.gz, T)
+            if rc != 0:
+                raise OSError(L.bdx_io_last_error().decode())
+        busy["download_s"] += t1 - t0
+        busy["write_s"] += time.perf_counter() - t1
+    finally:
+        slots.free.put(slot)
 
 
-def _write_loop(q_w, slots: _Slots, errors: list, rt: _Runtime, L, layout: OutputLayout, raw: bool, T: int, busy: dict):
-    """The writer thread: per batch, waits for its download and appends one block per file and stream, in batch
-    order.  ``raw``: the blocks are finished gzip members, appended as they are."""
+def _write_loop(q_w, slots: _Slots, errors: list, *writer):
+    """The writer thread: the batches in queue order (``writer``: _write_blocks' first arguments), until the run fails"""
     for slot, blocks in iter(q_w.get, None):
+        if errors:
+            slots.free.put(slot)
+            continue
         try:
-            if errors:
-                continue
-            t0 = time.perf_counter()
-            rt.check(rt.hipEventSynchronize(slots.events[slot]), "hipEventSynchronize (download)")
-            t1 = time.perf_counter()
-            base = slots.hbuf[slot].ctypes.data
-            for off, cb, prefix in blocks:
-                paths = layout.c_paths(prefix, np.flatnonzero(cb))
-                if raw:
-                    rc = L.bdx_fq_write_blocks_raw(base + off, cb.ctypes.data, layout.n_classes, paths, T)
-                else:
-                    rc = L.bdx_fq_write_blocks(base + off, cb.ctypes.data, layout.n_classes, paths, layout.gz, T)
-                if rc != 0:
-                    raise OSError(L.bdx_io_last_error().decode())
-            busy["download_s"] += t1 - t0
-            busy["write_s"] += time.perf_counter() - t1
+            _write_blocks(*writer, slots, slot, blocks)
         except BaseException as e:  # noqa: BLE001 - forwarded to the caller
             errors.append(e)
-        finally:
-            slots.free.put(slot)
 
 
 def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
                  classifier, batch_reads: int, timings: Optional[dict] = None, gzip_device: bool = False,
-                 gunzip_device: bool = False, gzip_level: int = 1, gunzip_stream: bool = False, gunzip_window: int = 0) -> None:
+                 gzip_level: int = 1, gunzip: str = "host", gunzip_window: int = WINDOW_BYTES) -> None:
     """Device counterpart of nativeio.demux_native (same arguments but ``on_batch``: the HIP classifier keeps the
     summary tables itself).  ``classifier`` must be the HIP classifier.  ``gzip_device``: gzip output is compressed by
     bdx_fq_deflate_device after the gathers, only finished gzip members are downloaded and the writer appends them as
     they are (inert when the output is not gzip), at ``gzip_level`` (1 or 2: bdx_fq_deflate_level_device).
-    ``gunzip_device``: every input whose name ends in .gz is uploaded
-    compressed and inflated by bdx_fq_inflate_device (inert for a plain input; ValueError for a .gz that is no chain of
-    size-tagged members of at most bdx_fq_inflate_member_max() bytes).  ``gunzip_stream``: every input whose name ends
-    in .gz is an ordinary gzip file: uploaded whole, inflated by bdx_fq_inflate_stream_device before the first batch
-    and kept resident (inert for a plain input; BdxError naming the file when a member is refused).
-    ``gunzip_window`` (compressed bytes; 0: not this mode): every such input goes through a window object of its own in
-    windows of that size (the module docstring has the flow, the memory bound and when a refusal is raised)."""
+    ``gunzip`` (the values of _gunzip) says who inflates an input whose name ends in .gz, each such input on its own
+    (inert for a plain input), ``gunzip_window`` how many compressed bytes a window of "device-window" has: _open_input
+    picks the class, the module docstring has each one's flow, memory bound and what it refuses, and when."""
     if not hasattr(classifier, "classify_device"):
         raise ValueError("the device FASTQ pipeline (_io='device') needs the HIP classifier")
     t_wall = time.perf_counter()
     busy = {"upload_s": 0.0, "device_s": 0.0, "download_s": 0.0, "write_s": 0.0, "batches": 0}
     L = _io()
-    lib, h, check = classifier.lib, classifier.h, classifier._check
-    rt = _Runtime(lib)
+    rt = _Runtime(classifier.lib)
     rt.check(rt.hipSetDevice(int(getattr(classifier, "device", 0))), "hipSetDevice")
     T = nativeio._threads()
     batch_reads = max(1, int(batch_reads))
     paired = fastq2 is not None
     layout = OutputLayout(config, output_directory, prefix1, prefix2, paired)
-    n_classes = layout.n_classes
     dev_gz = bool(gzip_device) and bool(layout.gz)
-    if dev_gz:
-        busy.update(deflate_s=0.0, plain_bytes=0, compressed_bytes=0, gzip_level=int(gzip_level))
-
-    ins = []
-    s_main = s_copy = 0
-    slots = None
-    dbufs = []
-    errors = []
+    ins, errors = [], []
+    ctx = _Context(rt, classifier, busy, layout, dev_gz, gzip_level, errors)
     q_w: "queue.Queue" = queue.Queue(maxsize=1)
     up = ThreadPoolExecutor(max_workers=1, thread_name_prefix="bdx-upload")
-    fut = None
-    writer = None
+    fut = writer = None
     try:
         for path in (fastq1, fastq2) if paired else (fastq1,):  # (each input judged on its own)
-            members = open_members(path, lib) if gunzip_device and _is_gz(path) else None
-            try:
-                ins.append(_Input(path, rt, L, classifier, busy, batch_reads, members, resident=gunzip_stream and _is_gz(path),
-                                  window=int(gunzip_window) if gunzip_window and _is_gz(path) else 0))
-            except BaseException:
-                if members is not None:
-                    members.close()
-                raise
-        if any(inp.gz is not None or inp.res is not None for inp in ins):
+            ins.append(_open_input(path, gunzip, gunzip_window, rt, L, classifier, busy, batch_reads))
+        if any(inp.inflates for inp in ins):
             busy.update(inflate_s=0.0, compressed_in_bytes=0, plain_in_bytes=0)
-        s_main, s_copy = rt.stream(), rt.stream()
-        classifier.set_stream(s_main)
+        ctx.open()
         for inp in ins:
-            if inp.w is not None:
-                inp.s_main = s_main
-            elif inp.res is not None:
-                inp.inflate_resident(s_copy)
-        d_seq, d_seq_off, d_out, d_gz = _DevBuf(rt), _DevBuf(rt), _DevBuf(rt), _DevBuf(rt)
-        d_v = {k: _DevBuf(rt) for k in ("bc1", "bc2", "keep_start", "keep_end")}
-        dbufs = [d_seq, d_seq_off, d_out, d_gz, *d_v.values()]
-        d_seq_off.ensure((batch_reads + 1) * 8)
-        for b in d_v.values():
-            b.ensure(batch_reads * 4)
-        slots = _Slots(rt)
+            inp.prepare(ctx.s_main, ctx.s_copy)
+        ctx.size_results(batch_reads)
 
         def upload_all(slot: int):
             for inp in ins:
-                inp.upload(s_copy, slot, inp.want_bytes())
+                inp.upload(ctx.s_copy, slot, inp.want_bytes())
 
         writer = threading.Thread(target=_write_loop, name="bdx-device-writer",
-                                  args=(q_w, slots, errors, rt, L, layout, dev_gz, T, busy))
+                                  args=(q_w, ctx.slots, errors, rt, L, layout, dev_gz, T, busy))
         writer.start()
         slot = 0
         fut = up.submit(upload_all, slot)
@@ -712,48 +829,24 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
             if errors:
                 break
             t0 = time.perf_counter()
-            found = [inp.index(s_copy, slot) for inp in ins]  # 2. the line index of each input
+            found = [inp.index(ctx.s_copy, slot) for inp in ins]  # 2. the line index of each input
             ns = [k for k, _ in found]
             n = min(ns)
             last = paired and ns[0] != ns[1]  # lock-step pairs: stop at the shorter file (core.jl:48)
             if n == 0:
                 break
-            # 3. the cursors move behind the batch (the index's cursor is relative to the window = the input's cursor)
-            for inp, (k, nx) in zip(ins, found):
+            for inp, (k, nx) in zip(ins, found):  # 3. the cursors move behind the batch (the index counts from the window's start)
                 if k:
                     inp.avg_record = nx / k
                 inp.cursor += nx
                 inp.release()  # uploaded: the host pages of this batch can go
-            wins = [inp.win[slot][0] for inp in ins]
+            texts = [(inp.d_text[slot], inp.win[slot][0], inp.d_off.p, inp.d_len.p) for inp in ins]
             if not last:  # 4. the next batch's windows go up beside this batch's kernels
                 fut = up.submit(upload_all, slot ^ 1)
-            # 5. pack -> ONE classify call -> the gathers
-            r1 = ins[0]
-            d_seq.ensure(wins[0] + 64)
-            check(lib.bdx_fq_pack_device(h, r1.d_text[slot], wins[0], r1.d_off.p, r1.d_len.p, n, d_seq.p, d_seq.cap,
-                                         d_seq_off.p, None))
-            classifier.classify_device(d_seq.p, d_seq_off.p, n, **{k: b.p for k, b in d_v.items()})
-            d_out.ensure(sum(wins[i] + 64 for i, _, _ in layout.streams))
-            blocks, pos = [], 0
-            for i, prefix, trim in layout.streams:
-                inp = ins[i]
-                cb = np.zeros(n_classes, dtype=np.int64)
-                check(lib.bdx_fq_gather_device(h, inp.d_text[slot], wins[i], inp.d_off.p, inp.d_len.p, n, d_v["bc1"].p,
-                                               d_v["bc2"].p, layout.stride, n_classes, d_v["keep_start"].p,
-                                               d_v["keep_end"].p, int(bool(trim)), d_out.p + pos, d_out.cap - pos,
-                                               cb.ctypes.data))
-                blocks.append((pos, cb, prefix))
-                pos += int(cb.sum())
-            d_src = d_out
-            if dev_gz:  # 6. only finished gzip members come back
-                blocks, pos = _deflate(classifier, d_out, d_gz, blocks, n_classes, busy)
-                d_src = d_gz
-            busy["device_s"] += time.perf_counter() - t0
-            busy["batches"] += 1
-            hs = _download(rt, s_main, slots, errors, d_src, pos)  # 7.
+            hs, blocks = ctx.batch(texts, n, t0)  # 5. pack -> classify -> gathers (-> deflate) -> the download starts
             if hs is None:
                 break
-            q_w.put((hs, blocks))  # 8. the writer waits for the copy and appends the blocks
+            q_w.put((hs, blocks))  # 6. the writer waits for the copy and appends the blocks
             if last:
                 break
             slot ^= 1
@@ -769,18 +862,9 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
         if writer is not None:
             q_w.put(None)
             writer.join()
-        if s_main:
-            rt.hipStreamSynchronize(s_main)
-            classifier.set_stream(None)
-        for b in dbufs:
-            b.free()
+        ctx.close()
         for inp in ins:
             inp.close()
-        for e in (slots.events if slots is not None else ()):
-            rt.hipEventDestroy(e)
-        for s in (s_main, s_copy):
-            if s:
-                rt.hipStreamDestroy(s)
     if timings is not None:
         busy["wall_s"] = time.perf_counter() - t_wall
         busy["threads"] = T
@@ -793,6 +877,7 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
 SPAN_MIN = 16
 _SPAN_TAIL = 1 << 16  # the first tail behind a span; doubled while a record that starts in the span ends behind it
 _AVG_RECORD = 330     # _Input.avg_record's start value
+_DealRun = namedtuple("_DealRun", "rt L f layout S dev_gz gzip_level chain")  # what the workers and the writer of a run share
 
 
 def default_span_bytes(batch_reads: int) -> int:
@@ -905,60 +990,34 @@ class _SpanChain:
 
 
 class _DealWorker:
-    """One context of demux_device_dealt: its streams, device buffers and two pinned download slots, and the thread that
-    takes spans from the chain until the input ends."""
+    """One context of demux_device_dealt: a _Context (streams, result buffers, two pinned download slots), the span's text
+    and line tables, and the thread that takes spans from ``run.chain`` until the input ends (``run``: what the call shares)."""
 
-    def __init__(self, k: int, run: "_DealRun", classifier):
-        self.k, self.run, self.cl = k, run, classifier
-        self.rt = run.rt
+    def __init__(self, k: int, run: _DealRun, classifier):
+        self.run, self.cl, self.rt = run, classifier, run.rt
         self.busy = {"upload_s": 0.0, "device_s": 0.0, "phase_wait_s": 0.0, "batches": 0}
-        if run.dev_gz:
-            self.busy.update(deflate_s=0.0, plain_bytes=0, compressed_bytes=0, gzip_level=run.gzip_level)
-        self.spans = 0
-        self.s_main = self.s_copy = 0
-        self.slots = None
-        self.bufs = {}
-        self.max_reads = 0
+        self.ctx = _Context(run.rt, classifier, self.busy, run.layout, run.dev_gz, run.gzip_level, run.chain.errors)
+        self.text, self.off, self.len = _DevBuf(run.rt), _DevBuf(run.rt), _DevBuf(run.rt)
+        self.spans = self.max_reads = 0
         self.thread = threading.Thread(target=self.loop, name=f"bdx-deal-{k}")
-
-    def buf(self, name: str) -> _DevBuf:
-        if name not in self.bufs:
-            self.bufs[name] = _DevBuf(self.rt)
-        return self.bufs[name]
-
-    def open(self):
-        rt = self.rt
-        rt.check(rt.hipSetDevice(int(getattr(self.cl, "device", 0))), "hipSetDevice")
-        self.s_main, self.s_copy = rt.stream(), rt.stream()
-        self.cl.set_stream(self.s_main)
-        self.slots = _Slots(rt)
 
     def tables(self, max_reads: int):
         self.max_reads = max_reads
-        self.buf("off").ensure(4 * max_reads * 8)
-        self.buf("len").ensure(4 * max_reads * 4)
+        self.off.ensure(4 * max_reads * 8)
+        self.len.ensure(4 * max_reads * 4)
 
     def upload(self, start: int, want: int):
         """bytes [start, start + want) of the input (what is there of them) -> (bytes, final); None behind its end"""
-        run, rt, L = self.run, self.rt, self.run.L
         t0 = time.perf_counter()
-        avail, fin = C.c_int64(0), C.c_int32(0)
-        if L.bdx_fq_wait(run.f.h, start + want, C.byref(avail), C.byref(fin)) != 0:
-            raise OSError(L.bdx_io_last_error().decode())
-        if avail.value <= start:
-            return None
-        end = min(avail.value, start + want)
-        nbytes = end - start
-        dst = self.buf("text").ensure(nbytes + 64)
-        rt.check(rt.hipMemcpyAsync(dst, L.bdx_fq_data(run.f.h) + start, nbytes, _H2D, self.s_copy), "hipMemcpyAsync (upload)")
-        rt.check(rt.hipStreamSynchronize(self.s_copy), "hipStreamSynchronize (upload)")
-        self.busy["upload_s"] += time.perf_counter() - t0
-        return nbytes, bool(fin.value) and end >= avail.value
+        got = _upload_text(self.rt, self.run.L, self.run.f, self.ctx.s_copy, self.text, start, want, or_none=True)
+        if got is not None:
+            self.busy["upload_s"] += time.perf_counter() - t0
+        return got
 
     def span(self, k: int) -> bool:
         """span k through this context -> False when the input ends in front of it"""
         run, chain, cl, lib = self.run, self.run.chain, self.cl, self.cl.lib
-        S, layout = run.S, run.layout
+        S = run.S
         start, tail = k * S, _SPAN_TAIL
         up = self.upload(start, S + tail)
         if up is None:
@@ -969,7 +1028,7 @@ class _DealWorker:
         span_len = min(S, nbytes)
         starts_line = 1 if start == 0 else int(C.c_ubyte.from_address(run.L.bdx_fq_data(run.f.h) + start - 1).value == 10)
         t0 = time.perf_counter()
-        d_text = self.buf("text").p
+        d_text = self.text.p
         count = C.c_int64(0)
         cl._check(lib.bdx_fq_count_lines_device(cl.h, d_text, span_len, C.byref(count)))
         chain.publish(k, count.value)  # at once: the spans behind this one wait for nothing else of it
@@ -981,7 +1040,7 @@ class _DealWorker:
         n, complete = C.c_int64(0), C.c_int32(1)
         while True:
             rc = lib.bdx_fq_index_span_device(cl.h, d_text, nbytes, span_len, phase, starts_line, int(final), self.max_reads,
-                                              self.buf("off").p, self.buf("len").p, C.byref(n), C.byref(complete))
+                                              self.off.p, self.len.p, C.byref(n), C.byref(complete))
             if rc == _E_SPACE:  # more records than the tables hold: the call has said how many
                 self.tables(int(n.value) + (int(n.value) >> 3))
                 continue
@@ -992,39 +1051,17 @@ class _DealWorker:
             t_up = time.perf_counter()
             nbytes, final = self.upload(start, S + tail)
             waited += time.perf_counter() - t_up
-            d_text = self.buf("text").p
+            d_text = self.text.p
         n = int(n.value)
         if n == 0:  # a line longer than the span, or no line of it begins a record: the writer passes it
             self.busy["device_s"] += time.perf_counter() - t0 - waited
             chain.hand_over(k, None)
             return True
-        d_off, d_len, d_seq, d_seq_off, d_out = (self.buf(b) for b in ("off", "len", "seq", "seq_off", "out"))
-        d_v = {b: self.buf(b) for b in ("bc1", "bc2", "keep_start", "keep_end")}
-        d_seq.ensure(nbytes + 64)
-        d_seq_off.ensure((n + 1) * 8)
-        for b in d_v.values():
-            b.ensure(n * 4)
-        cl._check(lib.bdx_fq_pack_device(cl.h, d_text, nbytes, d_off.p, d_len.p, n, d_seq.p, d_seq.cap, d_seq_off.p, None))
-        cl.classify_device(d_seq.p, d_seq_off.p, n, **{b: v.p for b, v in d_v.items()})
-        d_out.ensure(sum(nbytes + 64 for _ in layout.streams))
-        blocks, pos = [], 0
-        for _, prefix, trim in layout.streams:
-            cb = np.zeros(layout.n_classes, dtype=np.int64)
-            cl._check(lib.bdx_fq_gather_device(cl.h, d_text, nbytes, d_off.p, d_len.p, n, d_v["bc1"].p, d_v["bc2"].p, layout.stride,
-                                               layout.n_classes, d_v["keep_start"].p, d_v["keep_end"].p, int(bool(trim)),
-                                               d_out.p + pos, d_out.cap - pos, cb.ctypes.data))
-            blocks.append((pos, cb, prefix))
-            pos += int(cb.sum())
-        d_src = d_out
-        if run.dev_gz:
-            blocks, pos = _deflate(cl, d_out, self.buf("gz"), blocks, layout.n_classes, self.busy)
-            d_src = self.buf("gz")
-        self.busy["device_s"] += time.perf_counter() - t0 - waited
-        self.busy["batches"] += 1
-        hs = _download(self.rt, self.s_main, self.slots, chain.errors, d_src, pos)
+        self.ctx.size_results(n)
+        hs, blocks = self.ctx.batch([(d_text, nbytes, self.off.p, self.len.p)], n, t0 + waited)
         if hs is None:
             raise _ChainFailed()
-        chain.hand_over(k, (self.slots, hs, blocks))
+        chain.hand_over(k, (self.ctx.slots, hs, blocks))
         return True
 
     def loop(self):
@@ -1040,58 +1077,21 @@ class _DealWorker:
             chain.fail(e)
 
     def close(self):
-        rt = self.rt
-        rt.hipSetDevice(int(getattr(self.cl, "device", 0)))
-        if self.s_main:
-            rt.hipStreamSynchronize(self.s_main)
-            self.cl.set_stream(None)
-        for b in self.bufs.values():
+        self.ctx.close()  # (chooses the device for the frees below as well)
+        for b in (self.text, self.off, self.len):
             b.free()
-        for e in (self.slots.events if self.slots is not None else ()):
-            rt.hipEventDestroy(e)
-        for s in (self.s_main, self.s_copy):
-            if s:
-                rt.hipStreamDestroy(s)
-
-
-class _DealRun:
-    """what the workers and the writer of one demux_device_dealt call share"""
-
-    def __init__(self, rt, L, f, layout, S: int, dev_gz: bool, gzip_level: int):
-        self.rt, self.L, self.f, self.layout, self.S = rt, L, f, layout, S
-        self.dev_gz, self.gzip_level = dev_gz, gzip_level
-        self.chain = _SpanChain()
 
 
 def _write_dealt(run: _DealRun, T: int, busy: dict):
-    """The writer thread: takes the spans in span order, waits for each one's download and appends one block per file;
-    hands the pinned slot back to the span's context."""
-    chain, rt, L, layout = run.chain, run.rt, run.L, run.layout
+    """The writer thread: the spans in span order, each one's blocks from its context's slot (_write_blocks hands it back)"""
+    chain = run.chain
     try:
         for k, item in iter(chain.next_in_order, None):
             busy["spans"] += 1
             # every span up to k is uploaded; the span behind k still reads the byte in front of it
             run.f.release(max(0, (k + 1) * run.S - 1))
-            if item is None:
-                continue
-            slots, slot, blocks = item
-            try:
-                t0 = time.perf_counter()
-                rt.check(rt.hipEventSynchronize(slots.events[slot]), "hipEventSynchronize (download)")
-                t1 = time.perf_counter()
-                base = slots.hbuf[slot].ctypes.data
-                for off, cb, prefix in blocks:
-                    paths = layout.c_paths(prefix, np.flatnonzero(cb))
-                    if run.dev_gz:
-                        rc = L.bdx_fq_write_blocks_raw(base + off, cb.ctypes.data, layout.n_classes, paths, T)
-                    else:
-                        rc = L.bdx_fq_write_blocks(base + off, cb.ctypes.data, layout.n_classes, paths, layout.gz, T)
-                    if rc != 0:
-                        raise OSError(L.bdx_io_last_error().decode())
-                busy["download_s"] += t1 - t0
-                busy["write_s"] += time.perf_counter() - t1
-            finally:
-                slots.free.put(slot)
+            if item is not None:
+                _write_blocks(run.rt, run.L, run.layout, run.dev_gz, T, busy, *item)
     except BaseException as e:  # noqa: BLE001
         chain.fail(e)
 
@@ -1120,14 +1120,14 @@ def demux_device_dealt(fastq1: str, config, output_directory: str, prefix1: str,
     dev_gz = bool(gzip_device) and bool(layout.gz)
     wbusy = {"download_s": 0.0, "write_s": 0.0, "spans": 0}
     f = nativeio.FastqFile(fastq1)
-    run = _DealRun(rt, L, f, layout, S, dev_gz, int(gzip_level))
+    run = _DealRun(rt, L, f, layout, S, dev_gz, int(gzip_level), _SpanChain())
     chain = run.chain
     workers = [_DealWorker(k, run, c) for k, c in enumerate(classifiers)]
     started = []
     writer = None
     try:
         for w in workers:
-            w.open()
+            w.ctx.open()
         writer = threading.Thread(target=_write_dealt, name="bdx-deal-writer", args=(run, T, wbusy))
         writer.start()
         for w in workers:

@@ -288,7 +288,7 @@ def test_paired_both_gz_with_unequal_record_counts(tmp_path):
 
 
 def test_both_sides_of_the_capacity_guess(tmp_path):
-    """inflate_resident guesses four times the compressed size: a text that deflates better needs the second call"""
+    """_ResidentText.prepare guesses four times the compressed size: a text that deflates better needs the second call"""
     rng = np.random.default_rng(11)
     bcs = synth.make_barcodes(4, 12, seed=8, min_hamming=4)
     bc = tmp_path / "bc.csv"

@@ -344,3 +344,96 @@ def test_device_errors_propagate_instead_of_hanging(tmp_path):
     # the context is usable afterwards: a good run in the same process
     r = _in_thread(lambda: run_dev(good, bc, str(tmp_path / "o3"), _batch_reads=1000))
     assert r.get("ok"), r
+
+
+# ---- the short-index retry of the modes that upload a window again, and the _timings keys of every mode ----
+def _bgzf_file(path, blob, seed=1):
+    """`blob` as a chain of BGZF members of 1 .. 4000 plain bytes and the empty end marker"""
+    import inflate_cases as IC
+
+    rng = np.random.default_rng(seed)
+    cuts = [0]
+    while cuts[-1] < len(blob):
+        cuts.append(cuts[-1] + int(rng.integers(1, 4001)))
+    with open(path, "wb") as f:
+        for a, b in zip(cuts, cuts[1:]):
+            f.write(IC.zmember("m", blob[a:b], tag="BC", level=int(rng.integers(0, 10))).comp)
+        f.write(IC.zmember("eof", b"", tag="BC").comp)
+    assert gzip.open(path).read() == blob
+
+
+def test_a_record_longer_than_the_window_is_uploaded_again_in_every_mode_that_uploads(tmp_path):
+    """Five short reads, then one record of 200 000 bases (400 KB with its qualities).  With _batch_reads=1 a window is
+    1 * 330 * 1.05 + 65536 = 65 882 bytes at the start and smaller once the short reads set the average: the index of the
+    long record's batch comes back empty and the window is uploaded again at twice the size, three times (132, 264, 528 KB),
+    from the calling thread.  The plain file and the host-inflated .gz upload text again; the size-tagged members upload
+    the compressed members again and inflate them again: the last of the four uploads alone covers the file from the cursor's
+    member on, and the three before it 66, 132 and 264 KB of text each, so more compressed bytes go up than the file has."""
+    seqs, bc = _single_case(tmp_path, n=5)
+    seqs.append(b"ACGT" * 50000)
+    plain = str(tmp_path / "long.fastq")
+    _fastq(plain, seqs)
+    blob = open(plain, "rb").read()
+    ordinary, tagged = str(tmp_path / "ordinary" / "long.fastq.gz"), str(tmp_path / "tagged" / "long.fastq.gz")
+    for p in (ordinary, tagged):
+        os.mkdir(os.path.dirname(p))
+    with gzip.open(ordinary, "wb") as f:
+        f.write(blob)
+    _bgzf_file(tagged, blob)
+    kw = dict(max_error_rate=0.2, trim_side=5, _batch_reads=1)
+    for name, fq, more in (("plain", plain, {}), ("host", ordinary, dict(_gunzip="host")), ("members", tagged, dict(_gunzip="device"))):
+        nat, dev = str(tmp_path / f"nat_{name}"), str(tmp_path / f"dev_{name}")
+        tm = {}
+        a = run_nat(fq, bc, nat, **kw)
+        b = run_dev(fq, bc, dev, _timings=tm, **kw, **more)
+        _same_tree(nat, dev)
+        assert vars(a) == vars(b) and a.total_reads == 6, name
+    assert tm["compressed_in_bytes"] > os.path.getsize(tagged) and tm["batches"] == 6  # (the members leg ran last)
+
+
+_T_CALL = {"setup_s", "pre_s", "close_s", "total_s"}  # execute_demultiplexing's own
+_T_DEVICE = _T_CALL | {"upload_s", "device_s", "download_s", "write_s", "batches", "wall_s", "threads"}
+_T_DEFLATE = {"deflate_s", "plain_bytes", "compressed_bytes", "gzip_level"}
+_T_INFLATE = {"inflate_s", "compressed_in_bytes", "plain_in_bytes"}
+_T_STREAM = _T_INFLATE | {"stream_members", "stream_chunks", "stream_confirmed", "stream_discarded", "stream_no_candidate",
+                          "stream_longest_segment"}
+_T_DEAL = _T_CALL | {"devices", "upload_s", "device_s", "phase_wait_s", "download_s", "write_s", "batches", "spans",
+                     "spans_per_device", "span_bytes", "wall_s", "threads"}
+# mode -> (the input, execute_demultiplexing's arguments, the keys _timings then has: all of them, and no other)
+TIMINGS_KEYS = {
+    "device": ("plain", dict(_io="device"), _T_DEVICE),
+    "device gzip=device": ("plain", dict(_io="device", _gzip="device", gzip_output=True), _T_DEVICE | _T_DEFLATE),
+    "gunzip=device": ("tagged", dict(_io="device", _gunzip="device"), _T_DEVICE | _T_INFLATE),
+    "gunzip=device-stream": ("ordinary", dict(_io="device", _gunzip="device-stream"), _T_DEVICE | _T_STREAM),
+    "gunzip=device-window": ("ordinary", dict(_io="device", _gunzip="device-window"),
+                             _T_DEVICE | _T_STREAM | {"stream_windows", "stream_window_bytes", "stream_text_peak_bytes"}),
+    "deal": ("plain", dict(_io="device-deal", devices=[0, 0]), _T_DEAL),
+    "deal gzip=device": ("plain", dict(_io="device-deal", devices=[0, 0], _gzip="device", gzip_output=True), _T_DEAL | _T_DEFLATE),
+}
+
+
+@pytest.fixture(scope="module")
+def timing_inputs(tmp_path_factory):
+    """2000 ragged reads three times: plain, one ordinary gzip member, a chain of BGZF members"""
+    d = tmp_path_factory.mktemp("timings")
+    seqs, bc = _single_case(d, n=2000)
+    paths = {k: str(d / k / ("reads.fastq" if k == "plain" else "reads.fastq.gz")) for k in ("plain", "ordinary", "tagged")}
+    for p in paths.values():
+        os.mkdir(os.path.dirname(p))
+    _fastq(paths["plain"], seqs)
+    blob = open(paths["plain"], "rb").read()
+    with gzip.open(paths["ordinary"], "wb") as f:
+        f.write(blob)
+    _bgzf_file(paths["tagged"], blob, seed=2)
+    return paths, bc
+
+
+@pytest.mark.parametrize("mode", list(TIMINGS_KEYS))
+def test_timings_keys_of_every_device_mode(tmp_path, timing_inputs, mode):
+    paths, bc = timing_inputs
+    which, kw, keys = TIMINGS_KEYS[mode]
+    tm = {}
+    stats = H.bdx.execute_demultiplexing(paths[which], bc, str(tmp_path / "out"), max_error_rate=0.2, _batch_reads=700,
+                                         _timings=tm, **kw)
+    assert stats.total_reads == 2000
+    assert set(tm) == keys, (sorted(set(tm) - keys), sorted(keys - set(tm)))
