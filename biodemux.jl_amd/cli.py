@@ -66,6 +66,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--devices", type=_device_indices, default=None,
                    help="Comma list of HIP device indices to deal the batches over, e.g. 0,1,2 (this backend only; "
                         "not with --device)")
+    # this backend's own switches: each reaches execute_demultiplexing under its keyword only when it is given, and is
+    # validated there
+    p.add_argument("--check", action="store_true",
+                   help="Check every record (line 1 begins with '@', line 3 with '+', sequence and quality have the same "
+                        "length) and, for paired input, that the read names of both files agree; stop at the first failure")
+    p.add_argument("--io", default=None, help="File pipeline: auto, native, python, device or device-deal")
+    p.add_argument("--gzip", default=None, help="Who compresses gzip output: host or device (with --io device)")
+    p.add_argument("--gzip-level", type=int, default=None, help="Level of the device encoder: 1 or 2 (with --gzip device)")
+    p.add_argument("--gunzip", default=None,
+                   help="Who inflates .gz input: host, device, device-stream or device-window (with --io device)")
+    p.add_argument("--gunzip-window", type=int, default=None,
+                   help="Compressed bytes per window of --gunzip device-window")
+    p.add_argument("--span-bytes", type=int, default=None, help="Bytes per span of --io device-deal")
     return p
 
 
@@ -99,6 +112,11 @@ def main(argv: Optional[List[str]] = None, _execute=None) -> int:
             common["device"] = a.device
         if a.devices is not None:
             common["devices"] = a.devices
+        if a.check:
+            common["_check"] = True
+        for option in ("io", "gzip", "gzip_level", "gunzip", "gunzip_window", "span_bytes"):
+            if getattr(a, option) is not None:
+                common["_" + option] = getattr(a, option)
 
         def paired(f1, f2):
             run(f1, f2, a.barcode_file, a.output_directory, output_prefix1=a.output_prefix1,

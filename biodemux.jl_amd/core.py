@@ -21,7 +21,7 @@ import numpy as np
 from .classification import DemuxStats, filename_for, merge_stats_tables
 from .config import DemuxConfig, build_config
 from .fileio import read_fastq
-from . import deviceio, nativeio
+from . import checks, deviceio, nativeio
 from .hipabi import HipClassifier, load_library
 from .outputs import OutputLayout
 from .reporting import canonical_duration, generate_summary_report
@@ -33,15 +33,22 @@ _PREFIX_RE = re.compile(r"\.fastq(\.gz)?$")
 DEFAULT_BATCH_READS = 1 << 19  # reads per C-ABI call of the file pipeline (the kernels are at full speed from ~10^5 reads on; smaller batches fill the pipeline sooner)
 
 
-def _records(io):
+def _records(io, offsets: Optional[list] = None):
     """FASTQ framing of reader_task (core.jl:96-101): while !eof, four readline() calls; a
-    truncated last record is padded with empty lines exactly as readline at EOF returns ""."""
+    truncated last record is padded with empty lines exactly as readline at EOF returns "".
+    ``offsets`` (a list, for ``_check``) receives the byte offset of every record's first line in the text."""
     data = io.read()
     if not data:
         return
     lines = data.split(b"\n")
     if lines and lines[-1] == b"":
         lines.pop()  # data ended with '\n': no further line exists
+    if offsets is not None:
+        at = 0
+        for i, ln in enumerate(lines):
+            if i % 4 == 0:
+                offsets.append(at)
+            at += len(ln) + 1
     lines = [ln[:-1] if ln.endswith(b"\r") else ln for ln in lines]  # readline strips "\r\n"
     n = len(lines)
     for i in range(0, n, 4):
@@ -49,6 +56,13 @@ def _records(io):
         while len(rec) < 4:
             rec.append(b"")
         yield rec
+
+
+def _broken_rules(rec) -> int:
+    """the record rules of ``_check`` (include/biodemux_hip.h, bdx_fq_check_device) on one framed record"""
+    h, s, p, q = rec
+    return ((checks.HEADER if h[:1] != b"@" else 0) | (checks.PLUS if p[:1] != b"+" else 0)
+            | (checks.LENGTH if len(s) != len(q) else 0))
 
 
 class _Writer:
@@ -84,16 +98,37 @@ def _log(msg: str):
 
 def _demux(fastq1: str, fastq2: Optional[str], config: DemuxConfig, output_directory: str, prefix1: str,
            prefix2: str, classifiers: list, batch_reads: int, on_batch=None,
-           batches_per_device: Optional[list] = None) -> None:
+           batches_per_device: Optional[list] = None, check: bool = False, timings: Optional[dict] = None) -> None:
     """Batch k goes to classifier k % N of the N ``classifiers``, one batch at a time (the plain statement of what
-    nativeio's dealer does with threads); ``batches_per_device`` receives the counts."""
+    nativeio's dealer does with threads); ``batches_per_device`` receives the counts.  ``check``: every batch is held to
+    the record rules (file 1's records, then file 2's) and a paired one to the pair rule before it is classified, and a
+    pair of files with different numbers of records is refused after the last common batch; ``timings`` then receives
+    check_s and checked_records."""
     writer = _Writer(output_directory, config)
     streams = OutputLayout(config, output_directory, prefix1, prefix2, fastq2 is not None).streams
     dealt = [0] * len(classifiers)
+    at1: Optional[list] = [] if check else None  # byte offsets of the records' first lines
+    at2: Optional[list] = [] if check and fastq2 is not None else None
+    done = [0, 0.0]  # records flushed so far, seconds in the checks
+
+    def check_batch(r1: List[list], r2: Optional[List[list]]):
+        t0 = _dt.datetime.now()
+        for path, recs, at in ((fastq1, r1, at1), (fastq2, r2, at2)):
+            for i, rec in enumerate(recs or ()):
+                broken = _broken_rules(rec)
+                if broken:
+                    raise checks.record_error(path, done[0] + i + 1, at[done[0] + i], broken, len(rec[1]), len(rec[3]))
+        for i, (a, b) in enumerate(zip(r1, r2 or ())):
+            if checks.read_name(a[0]) != checks.read_name(b[0]):
+                raise checks.pair_error(fastq1, fastq2, done[0] + i + 1, a[0], b[0])
+        done[1] += (_dt.datetime.now() - t0).total_seconds()
 
     def flush(r1: List[list], r2: Optional[List[list]]):
         if not r1:
             return
+        if check:
+            check_batch(r1, r2)
+            done[0] += len(r1)
         seqs = [rec[1] for rec in r1]
         off = np.zeros(len(seqs) + 1, dtype=np.int64)
         off[1:] = np.cumsum([len(s) for s in seqs])
@@ -127,16 +162,21 @@ def _demux(fastq1: str, fastq2: Optional[str], config: DemuxConfig, output_direc
                 with read_fastq(fastq2) as io2:  # lock-step pairs, core.jl:48-75
                     b1: List[list] = []
                     b2: List[list] = []
-                    for rec1, rec2 in zip(_records(io1), _records(io2)):
+                    it1, it2 = _records(io1, at1), _records(io2, at2)
+                    for rec1, rec2 in zip(it1, it2):
                         b1.append(rec1)
                         b2.append(rec2)
                         if len(b1) >= batch_reads:
                             flush(b1, b2)
                             b1, b2 = [], []
                     flush(b1, b2)
+                    if check:
+                        next(it1, None), next(it2, None)  # (zip never started the second reader of an empty first file)
+                    if check and len(at1) != len(at2):  # (without it: the lock-step stop at the shorter file, core.jl:48)
+                        raise checks.count_error(fastq1, fastq2, min(len(at1), len(at2)), len(at1) > len(at2))
             else:
                 b1 = []
-                for rec1 in _records(io1):
+                for rec1 in _records(io1, at1):
                     b1.append(rec1)
                     if len(b1) >= batch_reads:
                         flush(b1, None)
@@ -146,6 +186,8 @@ def _demux(fastq1: str, fastq2: Optional[str], config: DemuxConfig, output_direc
         writer.close()
         if batches_per_device is not None:
             batches_per_device[:] = dealt
+        if check and timings is not None:
+            timings.update(check_s=done[1], checked_records=done[0] * (2 if fastq2 is not None else 1))
 
 
 def _device_list(device: int, devices, io: str) -> List[int]:
@@ -198,7 +240,7 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
                            _batch_reads: int = DEFAULT_BATCH_READS, _io: str = "auto", device: int = 0,
                            devices=None, _timings: Optional[dict] = None, _gzip: str = "host", _gunzip: str = "host",
                            _gzip_level: int = 1, _gunzip_window: Optional[int] = None, _span_bytes: Optional[int] = None,
-                           **kw):
+                           _check: bool = False, **kw):
     """execute_demultiplexing(FASTQ_file, barcode_file, output_directory; kwargs...)      core.jl:500
     execute_demultiplexing(FASTQ_file1, FASTQ_file2, barcode_file, output_directory; ...)  core.jl:360
 
@@ -250,7 +292,22 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
     as "device-stream" does.  Needs ``_io="device"``; inert for a plain input; a ``.gz`` input that does not begin with
     a gzip header is a ValueError; _timings holds what "device-stream" reports, summed over the windows
     (stream_longest_segment: the maximum), and stream_windows, stream_window_bytes and stream_text_peak_bytes.
+    ``_check`` (a bool, default False: the reference checks nothing, and nothing is checked, enqueued or timed without
+    it): every batch of every input is held to three record rules after its index and before it is packed and
+    classified — line 1 begins with '@', line 3 begins with '+', sequence and quality have the same length — and a
+    paired batch to the pair rule: the read names (the header after its first byte up to the first blank, one trailing
+    "/1" or "/2" dropped) of record i of both files are equal (include/biodemux_hip.h: bdx_fq_check_device,
+    bdx_fq_check_pair_device; csrc/bdx_io.cpp for ``_io="native"``, core._demux for "python").  File 1's records are
+    checked first, then file 2's, then the pairs; the lowest record of the first failing check raises BdxError naming the
+    file, the 1-based record number, the byte offset of its first line in the plain text and the first broken rule
+    (``_io="device-deal"``: the byte offset alone), after the batches before it were written; the failing batch is
+    neither classified, counted nor written.  A paired run whose files hold different numbers of records raises BdxError
+    after the last common batch is written instead of stopping silently at the shorter file.  A truncated last record
+    fails the plus or the length rule.  Not checked: the sequence alphabet, the quality range, the headers behind
+    their first blank.  ``_timings`` then also holds check_s and checked_records.
     Returns the DemuxStats scalar counters (the reference returns nothing)."""
+    if not isinstance(_check, bool):
+        raise ValueError("_check must be True or False")
     if len(args) == 3:
         fastq1, barcode_file, output_directory = args
         fastq2 = None
@@ -364,20 +421,21 @@ def execute_demultiplexing(*args, _classifier_factory: Optional[Callable[[DemuxC
         if _io == "device":
             deviceio.demux_device(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers[0], _batch_reads,
                                   _timings, gzip_device=_gzip == "device", gzip_level=int(_gzip_level), gunzip=_gunzip,
-                                  gunzip_window=_gunzip_window or deviceio.WINDOW_BYTES)
+                                  gunzip_window=_gunzip_window or deviceio.WINDOW_BYTES, check=_check)
         elif _io == "device-deal":
             deviceio.demux_device_dealt(fastq1, config, output_directory, prefix1, classifiers, _batch_reads, _timings,
-                                        gzip_device=_gzip == "device", gzip_level=int(_gzip_level), span_bytes=_span_bytes)
+                                        gzip_device=_gzip == "device", gzip_level=int(_gzip_level), span_bytes=_span_bytes,
+                                        check=_check)
         elif use_native:
             t_call = _dt.datetime.now()
             nativeio.demux_native(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers, _batch_reads,
-                                  on_batch, _timings)
+                                  on_batch, _timings, check=_check)
             if _timings is not None:  # (beyond the pipeline's own wall clock: releasing its batch buffers)
                 _timings["native_call_s"] = (_dt.datetime.now() - t_call).total_seconds()
         else:
             dealt: List[int] = []
             _demux(fastq1, fastq2, config, output_directory, prefix1, prefix2, classifiers, _batch_reads, on_batch,
-                   dealt)
+                   dealt, check=_check, timings=_timings)
             if multi and _timings is not None:
                 _timings["batches_per_device"] = dealt
         # merge_stats (reporting.jl:1-9) over the contexts: a host sum of a few KB, no collective

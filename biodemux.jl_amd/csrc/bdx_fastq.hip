@@ -458,6 +458,129 @@ __global__ void __launch_bounds__(FQ_THREADS) gather_kernel(const uint8_t *t, in
     }
 }
 
+// ---- record and pair checks (bdx_fq_check_device, bdx_fq_check_pair_device) ---------------------------------------------
+constexpr int FQ_CHECK_GRID = 2048;           // most workgroups of a check: 8 per CU, a grid-stride loop beyond
+constexpr int FQ_NAME_LANES = 16;             // lanes that walk one pair of header lines together
+constexpr int FQ_NAME_GROUPS = FQ_THREADS / FQ_NAME_LANES;
+constexpr unsigned long long FQ_NO_KEY = ~0ull;
+
+// The workgroup's smallest key, in thread 0 (every thread calls it): a wave minimum by shuffles, then one word per wave in LDS.
+__device__ inline unsigned long long block_min_key(unsigned long long key) {
+    __shared__ unsigned long long wmin[FQ_WAVES];
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(key, d, 64);
+        key = o < key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0) wmin[threadIdx.x >> 6] = key;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = 1; k < FQ_WAVES; ++k) key = wmin[k] < key ? wmin[k] : key;
+    return key;
+}
+
+// the four table words of one kind of a record: two 16-byte loads (or one) when the table's address allows it
+template <bool kVec>
+__device__ inline void load_record_words(const int64_t *line_off, const int32_t *line_len, int64_t i, int64_t (&off)[4],
+                                         int32_t (&len)[4]) {
+    if (kVec) {
+        const longlong2 a = *reinterpret_cast<const longlong2 *>(line_off + 4 * i);
+        const longlong2 b = *reinterpret_cast<const longlong2 *>(line_off + 4 * i + 2);
+        const int4 l = *reinterpret_cast<const int4 *>(line_len + 4 * i);
+        off[0] = a.x, off[1] = a.y, off[2] = b.x, off[3] = b.y;
+        len[0] = l.x, len[1] = l.y, len[2] = l.z, len[3] = l.w;
+    } else {
+        for (int k = 0; k < 4; ++k) {
+            off[k] = line_off[4 * i + k];
+            len[k] = line_len[4 * i + k];
+        }
+    }
+}
+
+// One lane per record: 48 bytes of table (consecutive lanes read consecutive records: whole cache lines), the first
+// byte of lines 1 and 3.  key = (index << 8) | broken rules; the lowest key of a workgroup that holds a failure goes
+// into *result with one atomicMin — a clean text costs no atomic at all.
+template <bool kVec>
+__global__ void __launch_bounds__(FQ_THREADS) check_kernel(const uint8_t *t, int64_t text_len, const int64_t *line_off,
+                                                           const int32_t *line_len, int64_t n, int32_t rules,
+                                                           unsigned long long *result, int *bad) {
+    unsigned long long key = FQ_NO_KEY;
+    for (int64_t i = (int64_t)blockIdx.x * FQ_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * FQ_THREADS) {
+        int64_t off[4];
+        int32_t len[4];
+        load_record_words<kVec>(line_off, line_len, i, off, len);
+        bool ok = true;
+        for (int k = 0; k < 4; ++k) ok = ok && line_ok(off[k], len[k], text_len);
+        if (!ok) {
+            *bad = 1;
+            continue;
+        }
+        int32_t m = 0;
+        if ((rules & BDX_FQ_CHECK_HEADER) && (len[0] == 0 || t[off[0]] != '@')) m |= BDX_FQ_CHECK_HEADER;
+        if ((rules & BDX_FQ_CHECK_PLUS) && (len[2] == 0 || t[off[2]] != '+')) m |= BDX_FQ_CHECK_PLUS;
+        if ((rules & BDX_FQ_CHECK_LENGTH) && len[1] != len[3]) m |= BDX_FQ_CHECK_LENGTH;
+        if (m && key == FQ_NO_KEY) key = ((unsigned long long)i << 8) | (unsigned)m;  // (a lane's records ascend)
+    }
+    key = block_min_key(key);
+    if (threadIdx.x == 0 && key != FQ_NO_KEY) atomicMin(result, key);
+}
+
+// FQ_NAME_LANES lanes per record.  Lane j looks at byte 1 + 16 s + j of both header lines in step s (byte loads inside
+// the lines only: nothing outside a text is read at any alignment); a byte at or behind a line's end counts as a blank.
+// The group's ballots give each token's end (the first blank) and the first position at which the lines differ; the
+// "/1" / "/2" suffix is judged from the two bytes in front of the token's end.  The names are equal when their lengths
+// are and the first difference lies behind them.  key = index, reduced like check_kernel's.
+__global__ void __launch_bounds__(FQ_THREADS) check_pair_kernel(const uint8_t *t1, int64_t text_len1, const int64_t *line_off1,
+                                                                const int32_t *line_len1, const uint8_t *t2, int64_t text_len2,
+                                                                const int64_t *line_off2, const int32_t *line_len2, int64_t n,
+                                                                unsigned long long *result, int *bad) {
+    const int j = threadIdx.x & (FQ_NAME_LANES - 1);
+    const int shift = (threadIdx.x & 63) & ~(FQ_NAME_LANES - 1);  // the group's first lane in the wave
+    unsigned long long key = FQ_NO_KEY;
+    const int64_t stride = (int64_t)gridDim.x * FQ_NAME_GROUPS;
+    // (every lane of a wave makes the same number of trips: the ballots below are wave-wide)
+    const int64_t trips = (n + stride - 1) / stride;
+    for (int64_t trip = 0; trip < trips; ++trip) {
+        const int64_t i = trip * stride + (int64_t)blockIdx.x * FQ_NAME_GROUPS + threadIdx.x / FQ_NAME_LANES;
+        bool live = i < n;
+        int64_t o1 = 0, o2 = 0, h1 = 0, h2 = 0;
+        if (live) {
+            o1 = line_off1[4 * i], o2 = line_off2[4 * i];
+            const int32_t l1 = line_len1[4 * i], l2 = line_len2[4 * i];
+            if (!line_ok(o1, l1, text_len1) || !line_ok(o2, l2, text_len2)) {
+                *bad = 1;
+                live = false;
+            }
+            h1 = l1, h2 = l2;
+        }
+        int64_t end1 = -1, end2 = -1, diff = -1;  // not known yet
+        bool open = live;
+        for (int64_t p0 = 1; __ballot(open) != 0ull; p0 += FQ_NAME_LANES) {
+            const int64_t p = p0 + j;
+            const uint8_t b1 = open && p < h1 ? t1[o1 + p] : (uint8_t)' ';
+            const uint8_t b2 = open && p < h2 ? t2[o2 + p] : (uint8_t)' ';
+            const unsigned g1 = (unsigned)(__ballot(b1 == ' ' || b1 == '\t') >> shift) & 0xFFFFu;
+            const unsigned g2 = (unsigned)(__ballot(b2 == ' ' || b2 == '\t') >> shift) & 0xFFFFu;
+            const unsigned gd = (unsigned)(__ballot(b1 != b2) >> shift) & 0xFFFFu;
+            if (open) {
+                if (end1 < 0 && g1) end1 = p0 + (__ffs(g1) - 1);
+                if (end2 < 0 && g2) end2 = p0 + (__ffs(g2) - 1);
+                if (diff < 0 && gd) diff = p0 + (__ffs(gd) - 1);
+                open = end1 < 0 || end2 < 0;
+            }
+        }
+        if (live) {
+            // token = bytes [1, end): the name drops one "/1" or "/2" the token ends in
+            int64_t n1 = end1 - 1, n2 = end2 - 1;
+            if (n1 >= 2 && t1[o1 + end1 - 2] == '/' && (t1[o1 + end1 - 1] == '1' || t1[o1 + end1 - 1] == '2')) n1 -= 2;
+            if (n2 >= 2 && t2[o2 + end2 - 2] == '/' && (t2[o2 + end2 - 1] == '1' || t2[o2 + end2 - 1] == '2')) n2 -= 2;
+            const bool same = n1 == n2 && (diff < 0 || diff >= 1 + n1);
+            if (!same && key == FQ_NO_KEY) key = (unsigned long long)i;
+        }
+    }
+    key = block_min_key(key);
+    if (threadIdx.x == 0 && key != FQ_NO_KEY) atomicMin(result, key);
+}
+
 unsigned grid_for(int64_t items, int64_t per_block) {
     const int64_t g = (items + per_block - 1) / per_block;
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>(g, 1 << 20));
@@ -713,6 +836,80 @@ int32_t bdx_fq_gather_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_l
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, read_back(ctx, bad + 1, &flag, 4));
     if (flag) return bdx_fail(ctx, BDX_E_INVALID, "a line of the line table lies outside the text");
+    return BDX_OK;
+}
+
+// what both checks read back: the smallest key (8 bytes) and the line flag behind it
+static int32_t check_result(bdx_ctx *ctx, unsigned long long *key) {
+    struct {
+        unsigned long long key;
+        int flag, pad;
+    } res = {FQ_NO_KEY, 0, 0};
+    HIP_TRY(ctx, read_back(ctx, ctx->fq[FQ_SMALL].p, &res, 16));
+    if (res.flag) return bdx_fail(ctx, BDX_E_INVALID, "a line of the line table lies outside the text");
+    *key = res.key;
+    return BDX_OK;
+}
+
+static hipError_t check_begin(bdx_ctx *ctx) {
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = ctx->fq[FQ_SMALL].ensure(64);
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->fq[FQ_SMALL].p, 0xFF, 8, ctx->stream);  // no key yet
+    if (e == hipSuccess) e = hipMemsetAsync((char *)ctx->fq[FQ_SMALL].p + 8, 0, 8, ctx->stream);
+    return e;
+}
+
+int32_t bdx_fq_check_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_len, const int64_t *d_line_off,
+                            const int32_t *d_line_len, int64_t n, int32_t rules, int64_t *first_bad, int32_t *broken) {
+    if (!ctx) return BDX_E_INVALID;
+    if (!first_bad || !broken) return bdx_fail(ctx, BDX_E_INVALID, "first_bad / broken is NULL");
+    *first_bad = -1;
+    *broken = 0;
+    if (n < 0 || text_len < 0) return bdx_fail(ctx, BDX_E_INVALID, "n / text_len is negative");
+    if (rules <= 0 || (rules & ~7) != 0) return bdx_fail(ctx, BDX_E_INVALID, "rules must be a mask of 1, 2 and 4 (got %d)", (int)rules);
+    if (n > 0xFFFFFFFFLL) return bdx_fail(ctx, BDX_E_INVALID, "more than 2^32 - 1 records in one call");
+    if (n == 0) return BDX_OK;
+    if (!d_text || !d_line_off || !d_line_len) return bdx_fail(ctx, BDX_E_INVALID, "NULL device pointer");
+    HIP_TRY(ctx, check_begin(ctx));
+    unsigned long long *result = (unsigned long long *)ctx->fq[FQ_SMALL].p;
+    int *bad = (int *)(result + 1);
+    const dim3 grid((unsigned)std::min<int64_t>((n + FQ_THREADS - 1) / FQ_THREADS, FQ_CHECK_GRID));
+    if ((((uintptr_t)d_line_off | (uintptr_t)d_line_len) & 15) == 0)
+        check_kernel<true><<<grid, dim3(FQ_THREADS), 0, ctx->stream>>>(d_text, text_len, d_line_off, d_line_len, n, rules, result, bad);
+    else
+        check_kernel<false><<<grid, dim3(FQ_THREADS), 0, ctx->stream>>>(d_text, text_len, d_line_off, d_line_len, n, rules, result, bad);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long key = FQ_NO_KEY;
+    const int32_t rc = check_result(ctx, &key);
+    if (rc != BDX_OK) return rc;
+    if (key != FQ_NO_KEY) {
+        *first_bad = (int64_t)(key >> 8);
+        *broken = (int32_t)(key & 0xFF);
+    }
+    return BDX_OK;
+}
+
+int32_t bdx_fq_check_pair_device(bdx_ctx *ctx, const uint8_t *d_text1, int64_t text_len1, const int64_t *d_line_off1,
+                                 const int32_t *d_line_len1, const uint8_t *d_text2, int64_t text_len2,
+                                 const int64_t *d_line_off2, const int32_t *d_line_len2, int64_t n, int64_t *first_bad) {
+    if (!ctx) return BDX_E_INVALID;
+    if (!first_bad) return bdx_fail(ctx, BDX_E_INVALID, "first_bad is NULL");
+    *first_bad = -1;
+    if (n < 0 || text_len1 < 0 || text_len2 < 0) return bdx_fail(ctx, BDX_E_INVALID, "n / text_len is negative");
+    if (n > 0xFFFFFFFFLL) return bdx_fail(ctx, BDX_E_INVALID, "more than 2^32 - 1 records in one call");
+    if (n == 0) return BDX_OK;
+    if (!d_text1 || !d_line_off1 || !d_line_len1 || !d_text2 || !d_line_off2 || !d_line_len2)
+        return bdx_fail(ctx, BDX_E_INVALID, "NULL device pointer");
+    HIP_TRY(ctx, check_begin(ctx));
+    unsigned long long *result = (unsigned long long *)ctx->fq[FQ_SMALL].p;
+    const dim3 grid((unsigned)std::min<int64_t>((n + FQ_NAME_GROUPS - 1) / FQ_NAME_GROUPS, FQ_CHECK_GRID));
+    check_pair_kernel<<<grid, dim3(FQ_THREADS), 0, ctx->stream>>>(d_text1, text_len1, d_line_off1, d_line_len1, d_text2, text_len2,
+                                                                   d_line_off2, d_line_len2, n, result, (int *)(result + 1));
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long key = FQ_NO_KEY;
+    const int32_t rc = check_result(ctx, &key);
+    if (rc != BDX_OK) return rc;
+    if (key != FQ_NO_KEY) *first_bad = (int64_t)key;
     return BDX_OK;
 }
 

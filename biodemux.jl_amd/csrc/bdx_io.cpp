@@ -609,6 +609,120 @@ int64_t bdx_fq_seq_bytes(const int32_t *line_len, int64_t nrec) {
     return s;
 }
 
+// ---- opt-in record and pair checks: the host side of bdx_fq_check_device / bdx_fq_check_pair_device --------------------
+// (include/biodemux_hip.h has the contract: the rules, the name of a header line, what is refused).  The text is the
+// file's bytes that are there (a streamed .gz: inflated so far — the tables of a batch never reach beyond them).
+// Both split the records over the calling thread's pool; -1 with a message in bdx_io_last_error when refused.
+static int64_t text_there(const bdx_fq_file *f) { return f->streaming ? f->avail.load(std::memory_order_acquire) : f->size; }
+
+static bool host_line_ok(int64_t off, int32_t len, int64_t size) { return off >= 0 && len >= 0 && off + len <= size; }
+
+// the name of the header line d[off, off + len): its first byte -> *start (relative to off), its length returned
+static int64_t header_name(const uint8_t *d, int64_t off, int64_t len, int64_t *start) {
+    *start = 1;
+    int64_t end = 1;
+    while (end < len && d[off + end] != ' ' && d[off + end] != '\t') ++end;
+    int64_t n = end - 1;
+    if (n >= 2 && d[off + end - 2] == '/' && (d[off + end - 1] == '1' || d[off + end - 1] == '2')) n -= 2;
+    return n;
+}
+
+// lowest key over [0, n) of key(i) (or -1 from it for "record i is fine"), -2 when a line lies outside its text
+extern "C++" {
+template <class Key>
+static int64_t lowest_key(int64_t n, int32_t nthreads, Key key) {
+    const int T = std::max(1, std::min<int>(nthreads, (int)(n >> 14) + 1));
+    const int64_t per = (n + T - 1) / T;
+    std::vector<int64_t> found((size_t)T, -1);
+    parallel_for(T, [&](const int t) {
+        const int64_t a = per * t, b = std::min(n, a + per);
+        for (int64_t i = a; i < b; ++i) {
+            const int64_t k = key(i);
+            if (k == -1) continue;
+            if (k == -2 || found[(size_t)t] == -1) found[(size_t)t] = k;
+            if (k == -2) break;
+        }
+    });
+    int64_t best = -1;
+    for (int t = 0; t < T; ++t) {
+        if (found[(size_t)t] == -2) return -2;
+        if (best == -1 && found[(size_t)t] >= 0) best = found[(size_t)t];  // (the slices ascend)
+    }
+    return best;
+}
+}  // extern "C++"
+
+int32_t bdx_fq_check(const bdx_fq_file *f, const int64_t *line_off, const int32_t *line_len, int64_t n, int32_t rules,
+                     int64_t *first_bad, int32_t *broken, int32_t nthreads) {
+    if (!first_bad || !broken) {
+        g_io_err = "first_bad / broken is NULL";
+        return -1;
+    }
+    *first_bad = -1;
+    *broken = 0;
+    const char *why = n < 0 ? "n is negative" : (rules <= 0 || (rules & ~7) != 0) ? "rules must be a mask of 1, 2 and 4"
+                      : n > 0xFFFFFFFFLL ? "more than 2^32 - 1 records in one call" : nullptr;
+    if (!why && n > 0 && (!f || !line_off || !line_len)) why = "NULL pointer";
+    if (why) {
+        g_io_err = why;
+        return -1;
+    }
+    if (n == 0) return 0;
+    const uint8_t *d = f->data;
+    const int64_t size = text_there(f);
+    const int64_t key = lowest_key(n, nthreads, [=](const int64_t i) -> int64_t {
+        const int64_t *o = line_off + 4 * i;
+        const int32_t *l = line_len + 4 * i;
+        for (int k = 0; k < 4; ++k)
+            if (!host_line_ok(o[k], l[k], size)) return -2;
+        int32_t m = 0;
+        if ((rules & 1) && (l[0] == 0 || d[o[0]] != '@')) m |= 1;
+        if ((rules & 2) && (l[2] == 0 || d[o[2]] != '+')) m |= 2;
+        if ((rules & 4) && l[1] != l[3]) m |= 4;
+        return m ? (i << 8) | m : -1;
+    });
+    if (key == -2) {
+        g_io_err = "a line of the line table lies outside the text";
+        return -1;
+    }
+    if (key >= 0) {
+        *first_bad = key >> 8;
+        *broken = (int32_t)(key & 0xFF);
+    }
+    return 0;
+}
+
+int32_t bdx_fq_check_pair(const bdx_fq_file *f1, const int64_t *line_off1, const int32_t *line_len1, const bdx_fq_file *f2,
+                          const int64_t *line_off2, const int32_t *line_len2, int64_t n, int64_t *first_bad, int32_t nthreads) {
+    if (!first_bad) {
+        g_io_err = "first_bad is NULL";
+        return -1;
+    }
+    *first_bad = -1;
+    const char *why = n < 0 ? "n is negative" : n > 0xFFFFFFFFLL ? "more than 2^32 - 1 records in one call" : nullptr;
+    if (!why && n > 0 && (!f1 || !line_off1 || !line_len1 || !f2 || !line_off2 || !line_len2)) why = "NULL pointer";
+    if (why) {
+        g_io_err = why;
+        return -1;
+    }
+    if (n == 0) return 0;
+    const uint8_t *d1 = f1->data, *d2 = f2->data;
+    const int64_t size1 = text_there(f1), size2 = text_there(f2);
+    const int64_t key = lowest_key(n, nthreads, [=](const int64_t i) -> int64_t {
+        const int64_t o1 = line_off1[4 * i], o2 = line_off2[4 * i];
+        if (!host_line_ok(o1, line_len1[4 * i], size1) || !host_line_ok(o2, line_len2[4 * i], size2)) return -2;
+        int64_t s1, s2;
+        const int64_t n1 = header_name(d1, o1, line_len1[4 * i], &s1), n2 = header_name(d2, o2, line_len2[4 * i], &s2);
+        return (n1 == n2 && (n1 == 0 || memcmp(d1 + o1 + s1, d2 + o2 + s2, (size_t)n1) == 0)) ? -1 : i;
+    });
+    if (key == -2) {
+        g_io_err = "a line of the line table lies outside the text";
+        return -1;
+    }
+    *first_bad = key;
+    return 0;
+}
+
 // One output stream of a batch: records of file `src` (with its line tables) are appended to
 // class_paths[cls[i]] in input order.  trim != 0: keep_start/keep_end (1-based inclusive, -1 =
 // untrimmed) are applied to sequence and quality (core.jl:162-173).  force_gzip: config.gzip_output.

@@ -58,7 +58,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import nativeio
+from . import checks, nativeio
 from .hipabi import BdxError, pinned_empty
 from .outputs import OutputLayout
 
@@ -624,6 +624,48 @@ def _open_input(path: str, gunzip: str, window: int, rt: _Runtime, io_lib, class
     return _ResidentText(*args) if gunzip == "device-stream" else _WindowedText(*args, int(window))
 
 
+def _fetch(rt: _Runtime, stream: int, d_ptr: int, dtype, count: int) -> np.ndarray:
+    """a small download: ``count`` items of ``dtype`` at the device address ``d_ptr`` (waits for ``stream``)"""
+    out = np.zeros(max(count, 1), dtype=dtype)
+    if count:
+        rt.check(rt.hipMemcpyAsync(out.ctypes.data, d_ptr, count * out.itemsize, _D2H, stream), "hipMemcpyAsync (download)")
+    rt.check(rt.hipStreamSynchronize(stream), "hipStreamSynchronize")
+    return out[:count]
+
+
+def _check_records(rt: _Runtime, cl, stream: int, path: str, text, n: int, base: int, done, busy: dict):
+    """_check: the n records of one input's batch against the three record rules (bdx_fq_check_device on the context's
+    stream).  ``text``: (d_text, bytes, d_off, d_len); ``base``: the window's offset in the plain text; ``done``: the
+    records in front of the batch, None where only byte offsets are known.  -> the BdxError of the lowest record that
+    breaks a rule (its line lengths come by a small download), or None"""
+    d_text, nbytes, d_off, d_len = text
+    bad, broken = C.c_int64(-1), C.c_int32(0)
+    cl._check(cl.lib.bdx_fq_check_device(cl.h, d_text, nbytes, d_off, d_len, n, checks.ALL_RULES, C.byref(bad), C.byref(broken)))
+    busy["checked_records"] += n
+    if bad.value < 0:
+        return None
+    i = int(bad.value)
+    off = _fetch(rt, stream, d_off + 4 * i * 8, np.int64, 4)
+    ln = _fetch(rt, stream, d_len + 4 * i * 4, np.int32, 4)
+    return checks.record_error(path, None if done is None else done + i + 1, base + int(off[0]), int(broken.value), int(ln[1]), int(ln[3]))
+
+
+def _check_pairs(rt: _Runtime, cl, stream: int, paths, texts, n: int, done: int):
+    """_check: the read names of the n record pairs of a batch (bdx_fq_check_pair_device) -> the BdxError of the lowest
+    pair whose names differ (the two header lines come by a small download), or None"""
+    (t1, b1, o1, l1), (t2, b2, o2, l2) = texts
+    bad = C.c_int64(-1)
+    cl._check(cl.lib.bdx_fq_check_pair_device(cl.h, t1, b1, o1, l1, t2, b2, o2, l2, n, C.byref(bad)))
+    if bad.value < 0:
+        return None
+    i, heads = int(bad.value), []
+    for d_text, _, d_off, d_len in texts:
+        off = int(_fetch(rt, stream, d_off + 4 * i * 8, np.int64, 1)[0])
+        ln = int(_fetch(rt, stream, d_len + 4 * i * 4, np.int32, 1)[0])
+        heads.append(_fetch(rt, stream, d_text + off, np.uint8, ln).tobytes())
+    return checks.pair_error(*paths, done + i + 1, *heads)
+
+
 class _Slots:
     """The pinned download buffers: batch k is downloaded into one while the writer appends batch k - 1 from the other.
     ``free`` holds the slots the writer is done with, ``events[s]`` fires when the copy into ``hbuf[s]`` has landed."""
@@ -779,14 +821,19 @@ def _write_loop(q_w, slots: _Slots, errors: list, *writer):
 
 def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
                  classifier, batch_reads: int, timings: Optional[dict] = None, gzip_device: bool = False,
-                 gzip_level: int = 1, gunzip: str = "host", gunzip_window: int = WINDOW_BYTES) -> None:
+                 gzip_level: int = 1, gunzip: str = "host", gunzip_window: int = WINDOW_BYTES, check: bool = False) -> None:
     """Device counterpart of nativeio.demux_native (same arguments but ``on_batch``: the HIP classifier keeps the
     summary tables itself).  ``classifier`` must be the HIP classifier.  ``gzip_device``: gzip output is compressed by
     bdx_fq_deflate_device after the gathers, only finished gzip members are downloaded and the writer appends them as
     they are (inert when the output is not gzip), at ``gzip_level`` (1 or 2: bdx_fq_deflate_level_device).
     ``gunzip`` (the values of _gunzip) says who inflates an input whose name ends in .gz, each such input on its own
     (inert for a plain input), ``gunzip_window`` how many compressed bytes a window of "device-window" has: _open_input
-    picks the class, the module docstring has each one's flow, memory bound and what it refuses, and when."""
+    picks the class, the module docstring has each one's flow, memory bound and what it refuses, and when.
+    ``check`` (_check): after the line index of a batch and before its cursors move, every input's records are held to
+    the record rules and a paired batch to the pair rule (bdx_fq_check_device, bdx_fq_check_pair_device); at the first
+    failure the loop ends as at the input's end — the writer appends what it holds — and the BdxError is raised then.
+    Two files of a pair with different numbers of records are refused likewise, behind the last common batch.
+    timings then also holds check_s (a part of device_s) and checked_records."""
     if not hasattr(classifier, "classify_device"):
         raise ValueError("the device FASTQ pipeline (_io='device') needs the HIP classifier")
     t_wall = time.perf_counter()
@@ -804,6 +851,10 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
     q_w: "queue.Queue" = queue.Queue(maxsize=1)
     up = ThreadPoolExecutor(max_workers=1, thread_name_prefix="bdx-upload")
     fut = writer = None
+    refused = None  # (_check) a failed check: raised once the writer has appended every batch in front of it
+    done = 0        # records of the batches so far
+    if check:
+        busy.update(check_s=0.0, checked_records=0)
     try:
         for path in (fastq1, fastq2) if paired else (fastq1,):  # (each input judged on its own)
             ins.append(_open_input(path, gunzip, gunzip_window, rt, L, classifier, busy, batch_reads))
@@ -833,14 +884,26 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
             ns = [k for k, _ in found]
             n = min(ns)
             last = paired and ns[0] != ns[1]  # lock-step pairs: stop at the shorter file (core.jl:48)
+            texts = [(inp.d_text[slot], inp.win[slot][0], inp.d_off.p, inp.d_len.p) for inp in ins]
+            if check:  # 2b. the batch's records, file by file, then the pairs' names
+                t_c = time.perf_counter()
+                for inp, text in zip(ins, texts):
+                    refused = refused or _check_records(rt, classifier, ctx.s_main, inp.path, text, n, inp.cursor, done, busy)
+                if paired:
+                    refused = refused or _check_pairs(rt, classifier, ctx.s_main, (fastq1, fastq2), texts, n, done)
+                busy["check_s"] += time.perf_counter() - t_c
+                if refused is not None:
+                    break
+                if last:  # (raised behind this batch, the last both files have)
+                    refused = checks.count_error(fastq1, fastq2, done + n, ns[0] > ns[1])
             if n == 0:
                 break
+            done += n
             for inp, (k, nx) in zip(ins, found):  # 3. the cursors move behind the batch (the index counts from the window's start)
                 if k:
                     inp.avg_record = nx / k
                 inp.cursor += nx
                 inp.release()  # uploaded: the host pages of this batch can go
-            texts = [(inp.d_text[slot], inp.win[slot][0], inp.d_off.p, inp.d_len.p) for inp in ins]
             if not last:  # 4. the next batch's windows go up beside this batch's kernels
                 fut = up.submit(upload_all, slot ^ 1)
             hs, blocks = ctx.batch(texts, n, t0)  # 5. pack -> classify -> gathers (-> deflate) -> the download starts
@@ -871,13 +934,15 @@ def demux_device(fastq1: str, fastq2: Optional[str], config, output_directory: s
         timings.update(busy)
     if errors:
         raise errors[0]
+    if refused is not None:
+        raise refused
 
 
 # ---- the device pipeline dealt over several contexts by byte spans (_io="device-deal") ----------------------------------
 SPAN_MIN = 16
 _SPAN_TAIL = 1 << 16  # the first tail behind a span; doubled while a record that starts in the span ends behind it
 _AVG_RECORD = 330     # _Input.avg_record's start value
-_DealRun = namedtuple("_DealRun", "rt L f layout S dev_gz gzip_level chain")  # what the workers and the writer of a run share
+_DealRun = namedtuple("_DealRun", "rt L f layout S dev_gz gzip_level chain path check")  # what the workers and the writer of a run share
 
 
 def default_span_bytes(batch_reads: int) -> int:
@@ -996,6 +1061,8 @@ class _DealWorker:
     def __init__(self, k: int, run: _DealRun, classifier):
         self.run, self.cl, self.rt = run, classifier, run.rt
         self.busy = {"upload_s": 0.0, "device_s": 0.0, "phase_wait_s": 0.0, "batches": 0}
+        if run.check:
+            self.busy.update(check_s=0.0, checked_records=0)
         self.ctx = _Context(run.rt, classifier, self.busy, run.layout, run.dev_gz, run.gzip_level, run.chain.errors)
         self.text, self.off, self.len = _DevBuf(run.rt), _DevBuf(run.rt), _DevBuf(run.rt)
         self.spans = self.max_reads = 0
@@ -1057,6 +1124,15 @@ class _DealWorker:
             self.busy["device_s"] += time.perf_counter() - t0 - waited
             chain.hand_over(k, None)
             return True
+        if run.check:  # the span's records; a failure goes to the writer in the span's place, which raises it in span order
+            t_c = time.perf_counter()
+            refused = _check_records(self.rt, cl, self.ctx.s_main, run.path, (d_text, nbytes, self.off.p, self.len.p), n, start, None,
+                                     self.busy)
+            self.busy["check_s"] += time.perf_counter() - t_c
+            if refused is not None:
+                self.busy["device_s"] += time.perf_counter() - t0 - waited
+                chain.hand_over(k, refused)
+                return True
         self.ctx.size_results(n)
         hs, blocks = self.ctx.batch([(d_text, nbytes, self.off.p, self.len.p)], n, t0 + waited)
         if hs is None:
@@ -1090,6 +1166,8 @@ def _write_dealt(run: _DealRun, T: int, busy: dict):
             busy["spans"] += 1
             # every span up to k is uploaded; the span behind k still reads the byte in front of it
             run.f.release(max(0, (k + 1) * run.S - 1))
+            if isinstance(item, BaseException):  # (_check) the span was refused: every span in front of it is written
+                raise item
             if item is not None:
                 _write_blocks(run.rt, run.L, run.layout, run.dev_gz, T, busy, *item)
     except BaseException as e:  # noqa: BLE001
@@ -1098,7 +1176,7 @@ def _write_dealt(run: _DealRun, T: int, busy: dict):
 
 def demux_device_dealt(fastq1: str, config, output_directory: str, prefix1: str, classifiers: list, batch_reads: int,
                        timings: Optional[dict] = None, gzip_device: bool = False, gzip_level: int = 1,
-                       span_bytes: Optional[int] = None) -> None:
+                       span_bytes: Optional[int] = None, check: bool = False) -> None:
     """The device pipeline of demux_device for ONE single-end input (plain, or a .gz the host inflates), dealt over the
     contexts ``classifiers`` by byte spans.  The text is cut into spans of ``span_bytes`` bytes (default:
     default_span_bytes(batch_reads)); a record belongs to the span its first line starts in (bdx_fq_index_span_device
@@ -1108,7 +1186,11 @@ def demux_device_dealt(fastq1: str, config, output_directory: str, prefix1: str,
     span order (_SpanChain).  Files, counters and reports are those of demux_device; the gzip members of
     ``gzip_device`` depend on the input and the span size alone, not on the contexts.  Device memory of a context:
     the span with its tail three times (text, packed reads, blocks; the members as well with ``gzip_device``), 48 bytes
-    a record of line table and 16 of results, and the context's own scratch."""
+    a record of line table and 16 of results, and the context's own scratch.
+    ``check`` (_check): every span's records are held to the record rules after its index (bdx_fq_check_device); a span
+    that fails hands its BdxError to the writer instead of blocks, which raises it when the spans in front of it are
+    written.  The message names the record's byte offset in the text and no record number: the span chain carries
+    phases, not record counts.  timings then also holds check_s and checked_records."""
     if not classifiers or not all(hasattr(c, "classify_device") for c in classifiers):
         raise ValueError("the device FASTQ pipeline (_io='device-deal') needs the HIP classifier")
     t_wall = time.perf_counter()
@@ -1120,7 +1202,7 @@ def demux_device_dealt(fastq1: str, config, output_directory: str, prefix1: str,
     dev_gz = bool(gzip_device) and bool(layout.gz)
     wbusy = {"download_s": 0.0, "write_s": 0.0, "spans": 0}
     f = nativeio.FastqFile(fastq1)
-    run = _DealRun(rt, L, f, layout, S, dev_gz, int(gzip_level), _SpanChain())
+    run = _DealRun(rt, L, f, layout, S, dev_gz, int(gzip_level), _SpanChain(), fastq1, bool(check))
     chain = run.chain
     workers = [_DealWorker(k, run, c) for k, c in enumerate(classifiers)]
     started = []

@@ -40,6 +40,9 @@ ABI_SYMBOLS = [
     "bdx_fq_index_device", "bdx_fq_pack_device", "bdx_fq_gather_device",
     # ... its index by byte spans (_io="device-deal")
     "bdx_fq_count_lines_device", "bdx_fq_index_span_device",
+    # ... its opt-in record and pair checks (_check=True); their host counterparts bdx_fq_check / bdx_fq_check_pair are
+    # libbdx_io.so's, bound in nativeio
+    "bdx_fq_check_device", "bdx_fq_check_pair_device",
     # device DEFLATE of the pipeline's gzip output (bdx_deflate.hip)
     "bdx_fq_deflate_chunk", "bdx_fq_deflate_bound", "bdx_fq_deflate_device", "bdx_fq_deflate_levels", "bdx_fq_deflate_level_device",
     # device inflate of the pipeline's .gz input (bdx_inflate.hip)
@@ -258,6 +261,10 @@ def load_library(path: Optional[str] = None):
     L.bdx_fq_gather_device.restype = C.c_int32
     L.bdx_fq_gather_device.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32,
                                        vp, C.c_int64, vp]
+    L.bdx_fq_check_device.restype = C.c_int32
+    L.bdx_fq_check_device.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    L.bdx_fq_check_pair_device.restype = C.c_int32
+    L.bdx_fq_check_pair_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.bdx_fq_deflate_chunk.restype = C.c_int32
     L.bdx_fq_deflate_chunk.argtypes = []
     L.bdx_fq_deflate_bound.restype = C.c_int64

@@ -17,6 +17,8 @@ from typing import Optional
 
 import numpy as np
 
+from . import checks
+from .hipabi import BdxError
 from .outputs import OutputLayout
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -84,6 +86,12 @@ def _load():
         L.bdx_fq_members_release.argtypes = [vp, C.c_int64]
         L.bdx_fq_members_close.restype = None
         L.bdx_fq_members_close.argtypes = [vp]
+        L.bdx_fq_data.restype = vp
+        L.bdx_fq_data.argtypes = [vp]
+        L.bdx_fq_check.restype = C.c_int32
+        L.bdx_fq_check.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32]
+        L.bdx_fq_check_pair.restype = C.c_int32
+        L.bdx_fq_check_pair.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64), C.c_int32]
         _lib = L
     return _lib
 
@@ -147,6 +155,26 @@ class FastqFile:
             so = np.empty(n + 1, dtype=np.int64)
         self.L.bdx_fq_pack(self.h, off.ctypes.data, ln.ctypes.data, n, seq.ctypes.data, so.ctypes.data, nthreads)
         return (seq[:total] if total else np.zeros(0, dtype=np.uint8)), so[:n + 1]
+
+    def check(self, off, ln, n: int, rules: int, nthreads: int):
+        """bdx_fq_check over the first n records of a line table -> (first_bad, broken): the lowest record that breaks a
+        rule of ``rules`` and the rules it breaks, or (-1, 0)"""
+        bad, broken = C.c_int64(-1), C.c_int32(0)
+        if self.L.bdx_fq_check(self.h, off.ctypes.data, ln.ctypes.data, n, rules, C.byref(bad), C.byref(broken), nthreads) != 0:
+            raise BdxError(self.L.bdx_io_last_error().decode())
+        return int(bad.value), int(broken.value)
+
+    def check_pair(self, off, ln, other: "FastqFile", off2, ln2, n: int, nthreads: int) -> int:
+        """bdx_fq_check_pair -> the lowest record whose read name differs from the same record's of ``other``, or -1"""
+        bad = C.c_int64(-1)
+        if self.L.bdx_fq_check_pair(self.h, off.ctypes.data, ln.ctypes.data, other.h, off2.ctypes.data, ln2.ctypes.data, n,
+                                    C.byref(bad), nthreads) != 0:
+            raise BdxError(self.L.bdx_io_last_error().decode())
+        return int(bad.value)
+
+    def line(self, off, ln, k: int) -> bytes:
+        """line k of a line table, from the host text"""
+        return C.string_at(self.L.bdx_fq_data(self.h) + int(off[k]), int(ln[k]))
 
     def close(self):
         if self.h:
@@ -226,10 +254,16 @@ class _NativeRun:
     """The threads of one demux_native call and what they share: reader -> q_in -> one classify thread per context -> the
     reorder step -> q_out -> writer, and the batch buffer sets coming back through ``free``."""
 
-    def __init__(self, fastq1, fastq2, layout, classifiers, batch_reads, on_batch):
+    def __init__(self, fastq1, fastq2, layout, classifiers, batch_reads, on_batch, check=False):
         self.layout, self.classifiers, self.batch_reads, self.on_batch = layout, classifiers, batch_reads, on_batch
         N = len(classifiers)
         self.busy = {"index_s": 0.0, "pack_s": 0.0, "classify_s": 0.0, "write_s": 0.0, "batches": 0}
+        self.paths, self.check = (fastq1, fastq2), bool(check)
+        # a failed check (_check): raised once every batch in front of it is written — it is no entry of ``errors``, at the
+        # sight of which the classify threads drop what they hold
+        self.refused: Optional[BaseException] = None
+        if check:
+            self.busy.update(check_s=0.0, checked_records=0)
         self.L = _load()
         self.T = _threads()
         # (developer knobs: host threads of the reader's / the writer's parallel sections — both default to the whole quota)
@@ -271,8 +305,9 @@ class _NativeRun:
 
     def reader(self):
         f1, f2, TR, busy = self.f1, self.f2, self.TR, self.busy
+        uneven = None  # (_check) the files of a pair hold different numbers of records: raised behind the last common batch
         try:
-            bid = 0
+            bid = done = 0
             while True:
                 # (a batch dropped on an error path never comes back through `free`: poll, and stop once anything failed —
                 # the reader must always reach its final q_in.put(None), or the classify threads wait for it forever)
@@ -296,8 +331,18 @@ class _NativeRun:
                     last = n1 != n2
                 else:
                     n, last = n1, False
+                if self.check:
+                    tc = time.perf_counter()
+                    self.refused = self.check_batch(done, n, off1, ln1, off2, ln2)
+                    if self.refused is None and f2 is not None and n1 != n2:
+                        uneven = checks.count_error(*self.paths, done + n, n1 > n2)
+                    busy["check_s"] += time.perf_counter() - tc
+                    if self.refused is not None:
+                        break
+                    t0 += time.perf_counter() - tc  # (index_s does not count it)
                 if n == 0:
                     break
+                done += n
                 t1 = time.perf_counter()
                 seq, so = f1.pack(off1, ln1, n, TR, buf.get("seq"), buf.get("so"))
                 if seq.base is not None:
@@ -310,10 +355,27 @@ class _NativeRun:
                 bid += 1
                 if last:
                     break
+            if self.refused is None:
+                self.refused = uneven
         except BaseException as e:  # noqa: BLE001 - forwarded to the caller
             self.errors.append(e)
         finally:
             self.q_in.put(None)
+
+    def check_batch(self, done: int, n: int, off1, ln1, off2, ln2):
+        """_check: the first n records of the batch (``done`` records lie in front of it) against the record rules, file 1
+        then file 2, then the pairs' names (bdx_fq_check, bdx_fq_check_pair) -> the BdxError of the first failure, or None"""
+        files = ((self.paths[0], self.f1, off1, ln1),) + (((self.paths[1], self.f2, off2, ln2),) if self.f2 is not None else ())
+        for path, f, off, ln in files:
+            bad, broken = f.check(off, ln, n, checks.ALL_RULES, self.TR)
+            self.busy["checked_records"] += n
+            if bad >= 0:
+                return checks.record_error(path, done + bad + 1, int(off[4 * bad]), broken, int(ln[4 * bad + 1]), int(ln[4 * bad + 3]))
+        if self.f2 is not None:
+            bad = self.f1.check_pair(off1, ln1, self.f2, off2, ln2, n, self.TR)
+            if bad >= 0:
+                return checks.pair_error(*self.paths, done + bad + 1, self.f1.line(off1, ln1, 4 * bad), self.f2.line(off2, ln2, 4 * bad))
+        return None
 
     def classify(self, cl, b: _Batch):
         """One batch through one context: fills in the batch's classes -> (verdicts, seconds in classify)."""
@@ -424,15 +486,20 @@ class _NativeRun:
 
 
 def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: str, prefix1: str, prefix2: str,
-                 classifiers: list, batch_reads: int, on_batch=None, timings: Optional[dict] = None) -> None:
+                 classifiers: list, batch_reads: int, on_batch=None, timings: Optional[dict] = None,
+                 check: bool = False) -> None:
     """Native counterpart of core._demux: index -> pack -> ONE C-ABI classify call -> in-order write, as a pipeline of
     threads (reader | one classify thread per context | writer; the native calls release the GIL).  The classify
     threads take the batches from the reader as they come free and a reorder step hands the results to the writer
     strictly by batch id, so per-file order is input order exactly as with the reference's single writer task
-    (core.jl:139-148) and the files are those of a single context.  ``on_batch`` is called under a lock."""
+    (core.jl:139-148) and the files are those of a single context.  ``on_batch`` is called under a lock.
+    ``check`` (_check): the reader holds every batch to the record rules and a paired one to the pair rule right after its
+    index (bdx_fq_check, bdx_fq_check_pair on the reader's threads); at the first failure it reads no further, the batches
+    in front of it go through classify and the writer as usual, and the BdxError is raised then; timings also holds
+    check_s and checked_records."""
     t_wall = time.perf_counter()
     layout = OutputLayout(config, output_directory, prefix1, prefix2, fastq2 is not None)
-    run = _NativeRun(fastq1, fastq2, layout, list(classifiers), batch_reads, on_batch)
+    run = _NativeRun(fastq1, fastq2, layout, list(classifiers), batch_reads, on_batch, check)
     run.run()
     if timings is not None:  # busy seconds of the three overlapped stages (reader = index + pack | classify | writer)
         busy = run.busy
@@ -446,3 +513,5 @@ def demux_native(fastq1: str, fastq2: Optional[str], config, output_directory: s
         timings.update(busy)
     if run.errors:
         raise run.errors[0]
+    if run.refused is not None:
+        raise run.refused

@@ -346,6 +346,44 @@ int32_t bdx_fq_gather_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_l
                              int32_t stride, int32_t n_classes, const int32_t *d_keep_start, const int32_t *d_keep_end,
                              int32_t trim, uint8_t *d_out, int64_t out_cap, int64_t *class_bytes);
 
+/* Opt-in record and pair checks over a line table (csrc/bdx_fastq.hip; the reference frames records by line count alone
+ * and checks nothing, core.jl:65-75, :175-190).  Three record rules, selected by a bit mask:
+ *   BDX_FQ_CHECK_HEADER  a record breaks it when line 1 is empty or its first byte is not '@'
+ *   BDX_FQ_CHECK_PLUS    ... when line 3 is empty or its first byte is not '+'
+ *   BDX_FQ_CHECK_LENGTH  ... when len(line 2) != len(line 4)
+ * Lengths are those of the line table: without "\n" and without a "\r" in front of it.  The padded lines of a truncated
+ * last record (off = text_len, len = 0) are ordinary empty lines to these rules, so a record cut after line 1 or 2 breaks
+ * the plus rule, one cut after line 3 the length rule unless its sequence line is empty: only a cut after an empty
+ * sequence line passes, and that is the same text as a whole record with an empty sequence and an empty quality line.
+ *
+ * One pair rule.  The NAME of a header line is its bytes after the first one (whatever that is: '@' is the header rule's
+ * business), up to but not including the first ' ' or '\t', or to the end of the line, with ONE trailing "/1" or "/2"
+ * dropped if that token ends in one.  An empty line has the empty name.  Two records pair when their names have the
+ * same length and the same bytes.
+ *
+ * Not checked: the sequence alphabet, the quality range, anything of a header behind the first blank.
+ *
+ * Both entries run on the context's stream and device and synchronise before they return.
+ * bdx_fq_check_device: *first_bad = the lowest index in [0, n) of a record that breaks a rule selected in `rules`, or
+ * -1 if there is none; *broken = the selected rules that record breaks, or 0.
+ * bdx_fq_check_pair_device: *first_bad = the lowest index in [0, n) at which record i of the first table and record i of
+ * the second do not pair, or -1.  Only header lines are read.
+ * n == 0 is BDX_OK with -1.  BDX_E_INVALID (with -1 / 0 stored when the result pointers are there): a NULL pointer, a
+ * negative length or count, `rules` with bits outside 7 or 0, more than 2^32 - 1 records, a line (of the lines the call
+ * reads: all four / the headers) that lies outside its text ("a line of the line table lies outside the text").  No byte
+ * outside [d_text, d_text + text_len) is read, whatever the alignment of d_text.  A correct call on the same context
+ * works after every refusal.
+ * The host counterparts, with the same contract over bdx_fq_file texts and host tables, are bdx_fq_check and
+ * bdx_fq_check_pair of csrc/bdx_io.cpp (libbdx_io.so); the device entries are tested against them. */
+#define BDX_FQ_CHECK_HEADER 1
+#define BDX_FQ_CHECK_PLUS 2
+#define BDX_FQ_CHECK_LENGTH 4
+int32_t bdx_fq_check_device(bdx_ctx *ctx, const uint8_t *d_text, int64_t text_len, const int64_t *d_line_off,
+                            const int32_t *d_line_len, int64_t n, int32_t rules, int64_t *first_bad, int32_t *broken);
+int32_t bdx_fq_check_pair_device(bdx_ctx *ctx, const uint8_t *d_text1, int64_t text_len1, const int64_t *d_line_off1,
+                                 const int32_t *d_line_len1, const uint8_t *d_text2, int64_t text_len2,
+                                 const int64_t *d_line_off2, const int32_t *d_line_len2, int64_t n, int64_t *first_bad);
+
 /* Device DEFLATE for the pipeline's gzip output (csrc/bdx_deflate.hip).  The input is what bdx_fq_gather_device
  * leaves: per-class blocks back to back in device memory (any byte offsets), their sizes in the host array class_bytes.
  * Every non-empty block is cut into chunks of at most bdx_fq_deflate_chunk() bytes and every chunk becomes one

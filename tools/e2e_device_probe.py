@@ -2,7 +2,7 @@
 """End-to-end reads/s of execute_demultiplexing on the C2 shape: the native host pipeline (_io="native") against the device
 FASTQ pipeline (_io="device"), each run in a fresh child process (GPU box).
 
-  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device} [--gzip-level 2] | --gunzip | --gunzip-stream | --gunzip-window | --deal] [out.json]
+  N=10000000 REPS=3 python tools/e2e_device_probe.py [--gzip {host,device} [--gzip-level 2] | --gunzip | --gunzip-stream | --gunzip-window | --deal | --check] [out.json]
 
 One synthetic FASTQ of N 150 bp reads x 96 barcodes (24 bp), max_error_rate=0.1, on tmpfs (/dev/shm unless E2E_ROOT is
 set); the outputs are checked (total bytes = input bytes).  Prints every run with its stage seconds, then the medians; the
@@ -32,7 +32,13 @@ every 10 ms by a thread of the child; other processes on the device would show i
 
 --deal: plain in -> plain out; four legs alternate after one unrecorded warm-up run: "device" (_io="device", the baseline)
 and "deal1", "deal2", "deal3" (_io="device-deal" with devices=[0], [0, 0] and [0, 0, 0]: one, two and three contexts on
-GPU 0, the default span).  REPS=5 is what the repository's figures use; every leg reports min, median and max wall seconds."""
+GPU 0, the default span).  REPS=5 is what the repository's figures use; every leg reports min, median and max wall seconds.
+
+--check: what the opt-in checks (_check=True) cost; plain in -> plain out through _io="device".  Legs "device" (_check
+off) and "device-chk" (on), single-end, and "pair" / "pair-chk" for a paired run (R2: the same headers, the sequences
+reversed; only R2 is written).  With E2E_PARENT naming a built checkout of the commit to compare against, the legs "parent"
+and "parent-pair" run the same calls with THAT checkout's package: the off legs are judged against them.  All legs alternate
+after one unrecorded warm-up run; the checked legs also report check_s."""
 import json
 import os
 import shutil
@@ -174,7 +180,25 @@ class FreeMemory:
         return None if self.first is None else int(self.first - self.low)
 
 
+CHECK_LEGS = ("device", "device-chk", "pair", "pair-chk")
+PARENT_LEGS = ("parent", "parent-pair")
+
+
+def make_pair_input(root: str, n: int) -> None:
+    """synthetic_R2.fastq beside synthetic.fastq: the same records with every sequence reversed"""
+    import numpy as np
+
+    fq = os.path.join(root, "synthetic_R2.fastq")
+    if os.path.exists(fq) and os.path.getsize(fq) == n * 319:
+        return
+    rec = np.fromfile(os.path.join(root, "synthetic.fastq"), dtype=np.uint8).reshape(n, 319)
+    rec[:, 15:165] = rec[:, 164:14:-1]
+    rec.tofile(fq)
+
+
 def child(mode: str) -> None:
+    if mode in PARENT_LEGS:  # the package of the checkout to compare against
+        sys.path.insert(0, os.environ["E2E_PARENT"])
     import biodemux_jl_amd as bdx
 
     root = os.environ["E2E_ROOT"]
@@ -184,6 +208,13 @@ def child(mode: str) -> None:
     shutil.rmtree(out, ignore_errors=True)
     tm = {}
     kw = dict(gzip_output=True) if gz else {}
+    fastqs = [fq]
+    if mode in CHECK_LEGS[1:] + PARENT_LEGS:
+        io = "device"
+        if "pair" in mode:
+            fastqs.append(os.path.join(root, "synthetic_R2.fastq"))
+        if mode.endswith("-chk"):
+            kw["_check"] = True
     if io.startswith("deal"):  # _io="device-deal" on that many contexts of GPU 0
         kw["devices"] = [0] * int(io[4:])
         io = "device-deal"
@@ -211,7 +242,9 @@ def child(mode: str) -> None:
     if gin == "din":
         kw["_gunzip"] = "device"
     t = time.perf_counter()
-    bdx.execute_demultiplexing(fq, bc, out, max_error_rate=0.1, _io=io, _timings=tm, **kw)
+    if len(fastqs) == 1:
+        fastqs = [fq]  # (the .gz legs have renamed it)
+    bdx.execute_demultiplexing(*fastqs, bc, out, max_error_rate=0.1, _io=io, _timings=tm, **kw)
     dt = time.perf_counter() - t
     if sampler is not None:
         tm["device_peak_bytes"] = sampler.stop()
@@ -258,6 +291,11 @@ def main() -> None:
     if deal:
         modes = ["device", "deal1", "deal2", "deal3"]
         argv = argv[1:]
+    check = bool(argv) and argv[0] == "--check"
+    if check:
+        parent = bool(os.environ.get("E2E_PARENT"))
+        modes = (["parent"] if parent else []) + ["device", "device-chk"] + (["parent-pair"] if parent else []) + ["pair", "pair-chk"]
+        argv = argv[1:]
     n = int(os.environ.get("N", "10000000"))
     reps = int(os.environ.get("REPS", "3"))
     root = os.environ.get("E2E_ROOT") or "/dev/shm/bdx_e2e_device_probe"
@@ -271,6 +309,8 @@ def main() -> None:
     if stream or window:
         make_stream_gz_input(root)
         gz_bytes = os.path.getsize(os.path.join(root, "synthetic.stream.fastq.gz"))
+    if check:
+        make_pair_input(root, n)
     gen_s = time.perf_counter() - t0
     env = dict(os.environ, E2E_ROOT=root, N=str(n))
     runs = []
@@ -302,7 +342,7 @@ def main() -> None:
             best = int(os.environ.get("E2E_WINDOW") or min(sweep, key=lambda x: x["seconds"])["window_mib"] << 20)
             env["E2E_WINDOW"] = str(best)
             print(f"SERIES window {best} bytes", flush=True)
-        for rep in range(-1 if gunzip or stream or window or deal else 0, reps):  # (rep -1: the warm-up run, not recorded)
+        for rep in range(-1 if gunzip or stream or window or deal or check else 0, reps):  # (rep -1: the warm-up run, not recorded)
             for mode in modes[:1] if rep < 0 else modes:
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode], env=env, capture_output=True,
                                    text=True, timeout=600)
@@ -323,6 +363,8 @@ def main() -> None:
                     keys += ("inflate_s", "compressed_in_bytes", "plain_in_bytes")
                 if mode.startswith("deal"):
                     keys += ("phase_wait_s", "spans")
+                if mode.endswith("-chk"):
+                    keys += ("check_s",)
                 print(f"RUN {rep} {mode:10s} {r['seconds']:.4f} s  {r['reads_per_s'] / 1e6:6.1f} M reads/s  "
                       + "  ".join(f"{k} {st.get(k, 0):.4f}" for k in keys) + f"  batches {st.get('batches')}", flush=True)
     finally:
